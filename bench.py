@@ -58,6 +58,31 @@ def insert_bytes(st: dict, slots_per_insert: float = REF_SLOTS_PER_PROBE) -> flo
     return (28.0 + 4.0 * slots_per_insert) * st["gins"]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, blocks_streams) -> None:
+    """--dump-outputs: what the timed path returned to its caller in the last timed step -- every block's T per-worker DNA
+    streams -- so that two builds can be compared output for output on the same seeded input:
+      dna_stream_bytes.npy  float64 [n_blocks, T]: the length of every stream
+      dna_streams.npy       float32: the streams' bytes, concatenated in block, worker order
+    If the bytes would take the files past 64 MB, dna_streams.npy holds a fixed sample (seed 0) of them, at the positions
+    that dna_streams_index.npy (float64, ascending) lists."""
+    os.makedirs(out_dir, exist_ok=True)
+    lens = np.array([[len(s) for s in streams] for streams in blocks_streams], dtype=np.float64)
+    data = np.frombuffer(b"".join(s for streams in blocks_streams for s in streams), dtype=np.uint8)
+    np.save(os.path.join(out_dir, "dna_stream_bytes.npy"), lens)
+    index_path = os.path.join(out_dir, "dna_streams_index.npy")
+    room = DUMP_LIMIT_BYTES - lens.nbytes - 4096   # (.npy headers)
+    if 4 * data.size > room:
+        idx = np.sort(np.random.default_rng(0).choice(data.size, room // 12, replace=False))   # 4 B value + 8 B position each
+        np.save(index_path, idx.astype(np.float64))
+        data = data[idx]
+    elif os.path.exists(index_path):
+        os.remove(index_path)
+    np.save(os.path.join(out_dir, "dna_streams.npy"), data.astype(np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -85,7 +110,11 @@ def main() -> None:
                          "fqsqueezer_amd/sharded.py): strong scaling.  The default for N > 1, with --partition")
     ap.add_argument("--replicas", action="store_true", help="N > 1: N independent files, one per GPU (weak scaling) instead of one sharded file")
     ap.add_argument("--no-partition", action="store_true", help="sharded: table replicas on every rank instead of partitioned tables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the timed steps, write the DNA streams the last timed step returned as DIR/*.npy (see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -97,6 +126,8 @@ def main() -> None:
         a.reads = a.reads or 2_000_000; a.genome = a.genome or 50_000_000; a.gs = a.gs or 3100
     else:
         a.reads = a.reads or 1_000_000; a.genome = a.genome or 7_500_000; a.gs = a.gs or 8
+    if a.dump_outputs and (a.sharded or world > 1):
+        raise SystemExit("--dump-outputs covers the one-GPU line only")
     emu = os.environ.get("FQSX_BENCH_EMU")   # tests only: the launcher path of the sharded line on CPUs (gloo + the emulated kernels)
     if emu:
         if not a.sharded:
@@ -150,7 +181,8 @@ def main() -> None:
     capacity = {}     # table occupancy / device memory at the end of the most recent pass (fqsx_dna_capacity)
     block_done = []   # host clock after every block of the most recent pass (a block call returns when its streams are back)
 
-    def one_step(profile: bool = False):
+    def one_step(profile: bool = False, sink=None):
+        """sink: a list that receives every block's T per-worker DNA streams (copied to Python bytes as they come back)"""
         codec = DnaCodec(header, device=local_rank, chunked_tables=a.chunked_tables)
         if profile:
             codec.set_profiling(True)
@@ -158,7 +190,12 @@ def main() -> None:
         block_done.clear()
         block_done.append(time.perf_counter())
         for g, (d_b, d_o, off) in enumerate(dev_blocks):
-            out_bytes += codec.encode_block_dev(d_b.data_ptr(), d_o.data_ptr(), off, g, collect=False)
+            if sink is None:
+                out_bytes += codec.encode_block_dev(d_b.data_ptr(), d_o.data_ptr(), off, g, collect=False)
+            else:
+                streams = codec.encode_block_dev(d_b.data_ptr(), d_o.data_ptr(), off, g)
+                sink.append(streams)
+                out_bytes += sum(len(s) for s in streams)
             block_done.append(time.perf_counter())
         res = (out_bytes, codec.stats() if profile else None, codec.kernel_times() if profile else None)
         capacity.clear()
@@ -176,14 +213,17 @@ def main() -> None:
     barrier()
     t0 = time.perf_counter()
     dna_bytes = 0
-    for _ in range(a.steps):
-        dna_bytes, _, _ = one_step()
+    last_streams = [] if a.dump_outputs else None
+    for i in range(a.steps):
+        dna_bytes, _, _ = one_step(sink=last_streams if i == a.steps - 1 else None)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last_streams)
 
     if rank != 0:
         if world > 1:

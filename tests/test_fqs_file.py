@@ -1,5 +1,7 @@
 """Complete .fqs files written around the DNA path: byte identity with the reference's own files and
-round trip through the unmodified reference decompressor (oracle/_ref/fqs-1.1 d)."""
+round trip through the unmodified reference decompressor (oracle/_ref/fqs-1.1 d; its verdict on the files is also kept as
+data in tests/golden/c4_ragged_ref_decode.json, so that the round trip is checked where the binary is not built)."""
+import hashlib
 import os
 import subprocess
 
@@ -21,6 +23,20 @@ def _decode_with_reference(data: bytes, tmp_path):
     out = tmp_path / "x.fq"
     subprocess.check_call([REF, "d", "-out", str(out), str(f)], stdout=subprocess.DEVNULL)
     return out.read_bytes().split(b"\n")[1::4]
+
+
+def _check_reference_decodes(data: bytes, rec, order: str, T: int, tmp_path):
+    """The reference decoder reads `data` back into the reads of `rec`: `data` is byte for byte the file the reference wrote for
+    them and decoded with `fqs-1.1 d` (tools/make_golden.py c4), and the read lines it decoded are `rec`'s, in the file's order.
+    Where oracle/_ref/fqs-1.1 is built, it decodes `data` here as well."""
+    g = json.load(open(os.path.join(GOLD, "c4_ragged_ref_decode.json")))[f"{order}_t{T}"]
+    order_idx = range(len(rec)) if order == "o" else np.concatenate(hp.sorted_order(rec))
+    want = [rec.seq[int(i)] for i in order_idx]
+    assert len(data) == g["file_bytes"] and hashlib.sha256(data).hexdigest() == g["file_sha256"], "not the file the reference decoded"
+    assert len(want) == g["decoded_reads"]
+    assert hashlib.sha256(b"".join(x + b"\n" for x in want)).hexdigest() == g["decoded_sha256"], "the reference decoded other reads"
+    if os.path.exists(REF):
+        assert _decode_with_reference(data, tmp_path)[:len(want)] == want
 
 
 def _lib(request):
@@ -54,17 +70,10 @@ def test_full_mode_paired_files_match_reference_digests(built, name, om, qm, im,
     check_full_file_digest(compress_records_pe(r1, r2, T, om, 1, lib_path=EMU_LIB, quality_mode=QM[qm], id_mode=IM[im]), name)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference binary not built")
 @pytest.mark.parametrize("order", ["o", "s"])
 def test_reference_decoder_reads_our_file(built, tmp_path, order):
     rec = c4_records()
-    data = compress_records(rec, 5, order, 1, lib_path=EMU_LIB)
-    got = _decode_with_reference(data, tmp_path)
-    if order == "o":
-        want = [rec.seq[i] for i in range(len(rec))]
-    else:
-        want = [rec.seq[int(i)] for i in np.concatenate(hp.sorted_order(rec))]
-    assert got[:len(want)] == want
+    _check_reference_decodes(compress_records(rec, 5, order, 1, lib_path=EMU_LIB), rec, order, 5, tmp_path)
 
 
 @pytest.mark.gpu
@@ -82,10 +91,8 @@ def test_gpu_full_mode_files_identical_to_reference():
 def test_gpu_file_identical_to_reference_and_decodes(tmp_path):
     data = compress_records(c1_records(), 4, "o", 1)
     assert data == open(os.path.join(GOLD, "c1_10k_o_t4.fqs"), "rb").read()
-    if os.path.exists(REF):
-        rec = c4_records()
-        got = _decode_with_reference(compress_records(rec, 64, "s", 1), tmp_path)
-        assert got[:len(rec)] == [rec.seq[int(i)] for i in np.concatenate(hp.sorted_order(rec))]
+    rec = c4_records()
+    _check_reference_decodes(compress_records(rec, 64, "s", 1), rec, "s", 64, tmp_path)
 
 
 @pytest.mark.gpu

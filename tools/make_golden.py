@@ -7,6 +7,8 @@ Fixtures (data only -- inputs are re-generated deterministically by fqsqueezer_a
   c2_1M_s_t{1,8,64}.json    per-block SHA-256 + sizes of the reference DNA streams,
                             1M x 100bp, G=5Mbp, seed 2, -om s -gs 5   (BASELINE configs[1])
   c4_ragged_{o,s}_t3.fqs   3000 ragged reads (30-160 bp, N runs, duplicates), G=60kbp, seed 4, -gs 1
+  c4_ragged_ref_decode.json  the c4 reads at -t 5 (-om o / s) and -t 64 (-om s): size and SHA-256 of the reference's file, and
+                            the SHA-256 of the read lines `fqs-1.1 d` decodes from it (the reference decoder's verdict, kept as data)
   c5_pe4k_{o,s}_t{1,4}.fqs  4000 pairs x 100bp (fragments 300-600), G=60kbp, seed 5, `-p`, -gs 1 (paired-end path)
   c6_20k_gs300_s_t2.json    20k x 100bp, G=1Mbp, seed 6, -gs 300 (k = 12/17/21/26: 4 GiB p-mer vector, 256-way partial look-ups)
   c9_20k150_gs3100_s_t2.json  20k x 150bp, G=200kbp, seed 9, DEFAULT -gs 3100 (k = 13/18/21/27: 16 GiB p-mer vector, up to 1024-way
@@ -101,6 +103,7 @@ def main():
                 f.write(i + b"\n" + sq + b"\n+\n" + q + b"\n")
         for om in "os":
             run_ref(fq, os.path.join(GOLD, f"c4_ragged_{om}_t3.fqs"), om, 3, 1, a.work)
+        c4_ref_decode(a, fq)
     if a.only in ("", "c5"):
         from fqsqueezer_amd.synth import synth_pairs
         r1, r2 = synth_pairs(4000, 100, 60000, 5)
@@ -390,6 +393,18 @@ def c22(a):
     meta = {"pairs": npairs, "len": 150, "genome": G, "seed": seed, "gs": 15, "om": "s", "qm": "o", "im": "o", "threads": 8,
             "paired": True, "varied_ids": True}
     json.dump(fdigest(out, meta), open(os.path.join(GOLD, "c22_pe1M_s_oo_t8.json"), "w"))
+
+
+def c4_ref_decode(a, fq):
+    d = {}
+    for om, t in (("o", 5), ("s", 5), ("s", 64)):
+        out, dec = os.path.join(a.work, f"c4_{om}_t{t}.fqs"), os.path.join(a.work, f"c4_{om}_t{t}.fq")
+        run_ref(fq, out, om, t, 1, a.work)
+        subprocess.check_call([REF, "d", "-out", dec, out], stdout=subprocess.DEVNULL)
+        data, lines = open(out, "rb").read(), open(dec, "rb").read().split(b"\n")[1::4]
+        d[f"{om}_t{t}"] = {"om": om, "threads": t, "gs": 1, "file_bytes": len(data), "file_sha256": hashlib.sha256(data).hexdigest(),
+                           "decoded_reads": len(lines), "decoded_sha256": hashlib.sha256(b"".join(x + b"\n" for x in lines)).hexdigest()}
+    json.dump(d, open(os.path.join(GOLD, "c4_ragged_ref_decode.json"), "w"), indent=1)
 
 
 def ragged():
