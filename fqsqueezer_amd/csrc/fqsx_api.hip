@@ -10,11 +10,14 @@
 //
 // which is the barrier structure of the reference worker loop (fqs/application.cpp:610-669)
 // with kernel boundaries in place of CBarrier.  Built with hipcc for gfx950; the FQSX_EMU
-// build (tests/emu only) runs the same kernels as plain loops for debugging without a GPU.
+// build (tests/emu only) runs the same kernels as plain loops for debugging without a GPU.  Every codec here is a
+// device context (fqsx_rt.h): the runtime steps have their HIP and their emulation implementation side by side there,
+// so that both builds run this file's host orchestration alike.
 #include "fqsx_kernels.h"
 #include "fqsx_qual.h"
 #include "../../include/fqsx.h"
 #include "fqsx_vm.h"
+#include "fqsx_rt.h"
 #include <sys/resource.h>
 
 #ifndef FQSX_EMU
@@ -28,7 +31,6 @@
 #include <string>
 #include <vector>
 
-static thread_local std::string g_err;
 extern "C" const char *fqsx_last_error(void) { return g_err.c_str(); }
 extern "C" const char *fqsx_version(void) {
 #ifdef FQSX_EMU
@@ -51,12 +53,7 @@ FQ_DEV bool phase_skip(const DevCfg &cfg) { return (cfg.err[0] | cfg.err[1]) != 
 // grid = 3 * T: (owner, mailbox kind), plus -- single-end encoding -- workgroups that clear the workers' local tables
 // (ClearKmersToHT, dna.cpp:2475-2488: the insert phase does not touch them), which saves that launch
 // 128 threads: wave 0 inserts, wave 1 touches the buckets of the batches ahead (insert_prefetch_body)
-#ifndef FQSX_EMU
-extern "C" __global__ __launch_bounds__(128)
-#else
-static
-#endif
-void k_insert_phase(DevCfg cfg, u64 nb_slots, u64 ns_slots) {
+FQ_KERNEL128 void k_insert_phase(DevCfg cfg, u64 nb_slots, u64 ns_slots) {
   FQ_SHARED InsShared sm;
   if (phase_skip(cfg)) return;
 #ifndef FQSX_EMU
@@ -214,12 +211,8 @@ FQ_KERNEL64 void k_pe_demand(DevCfg cfg, u32 *demand, u32 seg1) {
 // the bucketed form of the phase (fqsx_pe.h): count, offsets + growth check, scatter, per-owner inserts
 FQ_KERNEL void k_pe_bucket_count(DevCfg cfg) {
   if (phase_skip(cfg)) return;
-#ifndef FQSX_EMU
-  const u32 total = cfg.T * cfg.pe_cap, stride = gridDim.x * blockDim.x;
-  for (u32 g = blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) pe_bucket_count_body(cfg, g);
-#else
-  for (u32 g = 0; g < cfg.T * cfg.pe_cap; ++g) pe_bucket_count_body(cfg, g);
-#endif
+  const u32 total = cfg.T * cfg.pe_cap, stride = FQ_GRID_STRIDE(u32);
+  for (u32 g = FQ_GRID_FIRST(u32); g < total; g += stride) pe_bucket_count_body(cfg, g);
 }
 FQ_KERNEL64 void k_pe_bucket_offsets(DevCfg cfg, u32 seg1) {   // one wave
   if (phase_skip(cfg)) return;
@@ -241,12 +234,8 @@ FQ_KERNEL64 void k_pe_bucket_offsets(DevCfg cfg, u32 seg1) {   // one wave
 }
 FQ_KERNEL void k_pe_bucket_scatter(DevCfg cfg) {
   if (phase_skip(cfg)) return;
-#ifndef FQSX_EMU
-  const u32 total = cfg.T * cfg.pe_cap, stride = gridDim.x * blockDim.x;
-  for (u32 g = blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) pe_bucket_scatter_body(cfg, g);
-#else
-  for (u32 g = 0; g < cfg.T * cfg.pe_cap; ++g) pe_bucket_scatter_body(cfg, g);
-#endif
+  const u32 total = cfg.T * cfg.pe_cap, stride = FQ_GRID_STRIDE(u32);
+  for (u32 g = FQ_GRID_FIRST(u32); g < total; g += stride) pe_bucket_scatter_body(cfg, g);
 }
 FQ_KERNEL64 void k_pe_insert_buckets(DevCfg cfg) {   // grid = T (owner); also leaves the counters zero for the next phase
   FQ_SHARED InsShared sm;
@@ -266,12 +255,8 @@ FQ_KERNEL64 void k_pe_insert(DevCfg cfg) {
 // re-insert the occupied slots of sub-tables first, first + step, ... (n_sub of them) of `o` into the (empty, larger) table `n`
 FQ_KERNEL void k_rehash_ptab(PTab o, PTab n, u32 n_sub, u32 first, u32 step, u32 sys) {
   const u64 ocap = o.cap_mask + 1, total = ocap * n_sub;
-#ifndef FQSX_EMU
-  const u64 gstride = (u64)gridDim.x * blockDim.x;
-  for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gstride) {
-#else
-  for (u64 g = 0; g < total; ++g) {
-#endif
+  const u64 gstride = FQ_GRID_STRIDE(u64);
+  for (u64 g = FQ_GRID_FIRST(u64); g < total; g += gstride) {
     const u32 sub = first + (u32)(g / ocap) * step;
     const u64 k = o.key[(u64)sub * o.stride + (g % ocap)], v = o.val[(u64)sub * o.stride + (g % ocap)];
     if (k == 0 && v == 0) continue;
@@ -289,24 +274,16 @@ FQ_KERNEL void k_rehash_ptab(PTab o, PTab n, u32 n_sub, u32 first, u32 step, u32
 // against the re-insert kernel that follows does not hang on how the runtime treats a memset into a mapped range)
 // sys: the words are a sub-table other GPUs will map (system-scope release at the end, see DevCfg.sys_scope)
 FQ_KERNEL void k_zero_words(u64 *p, u64 n, u32 sys) {
-#ifndef FQSX_EMU
-  const u64 gstride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gstride) p[i] = 0;
-#else
-  for (u64 i = 0; i < n; ++i) p[i] = 0;
-#endif
+  const u64 gstride = FQ_GRID_STRIDE(u64);
+  for (u64 i = FQ_GRID_FIRST(u64); i < n; i += gstride) p[i] = 0;
   if (sys) fq_release_system();
 }
 // (sub-tables first, first + step, ...: all of them on one GPU; a rank's own ones when the tables are partitioned)
 FQ_KERNEL void k_rehash_ktab(KTab o, KTab n, u32 n_sub, u32 first, u32 step, u32 sys) {
   const u64 ocap = o.nb * FQSX_BKT;
   const u64 total = ocap * n_sub;
-#ifndef FQSX_EMU
-  const u64 gstride = (u64)gridDim.x * blockDim.x;
-  for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gstride) {
-#else
-  for (u64 g = 0; g < total; ++g) {
-#endif
+  const u64 gstride = FQ_GRID_STRIDE(u64);
+  for (u64 g = FQ_GRID_FIRST(u64); g < total; g += gstride) {
     u32 sub = first + (u32)(g / ocap) * step;
     u64 it = o.slots[(u64)sub * o.stride + (g % ocap)];
     if (!it) continue;
@@ -317,12 +294,8 @@ FQ_KERNEL void k_rehash_ktab(KTab o, KTab n, u32 n_sub, u32 first, u32 step, u32
 }
 FQ_KERNEL void k_rehash_ctx(const u64 *o, u64 ocap_mask, u64 *n, u64 ncap_mask, u32 T) {
   const u64 ocap = ocap_mask + 1, total = ocap * T;
-#ifndef FQSX_EMU
-  const u64 gstride = (u64)gridDim.x * blockDim.x;
-  for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gstride) {
-#else
-  for (u64 g = 0; g < total; ++g) {
-#endif
+  const u64 gstride = FQ_GRID_STRIDE(u64);
+  for (u64 g = FQ_GRID_FIRST(u64); g < total; g += gstride) {
     u32 w = (u32)(g / ocap);
     const u64 *src = o + 4 * g;
     u64 q1 = src[1];
@@ -372,11 +345,7 @@ FQ_KERNEL64 void k_shard_counts(DevCfg cfg, u32 *dst, u32 status) {   // grid = 
 // of rank q.  One thread per (kind, owner): neighbouring threads read neighbouring words of a matrix row.
 FQ_KERNEL void k_shard_colsum(DevCfg cfg, const u32 *C, u32 *cs) {
   const u32 T = cfg.T, G = cfg.shard_world;
-#ifndef FQSX_EMU
-  const u32 stride = gridDim.x * blockDim.x, first = blockIdx.x * blockDim.x + threadIdx.x;
-#else
-  const u32 stride = 1, first = 0;
-#endif
+  const u32 stride = FQ_GRID_STRIDE(u32), first = FQ_GRID_FIRST(u32);
   for (u32 i = first; i < 3 * T; i += stride) {
     const u32 kind = i / T, o = i % T;
     const u32 *Ck = C + (u64)kind * T * T;
@@ -406,9 +375,7 @@ FQ_KERNEL64 void k_shard_need(DevCfg cfg, const u32 *cs, u64 *out, u64 *stats_be
       const u64 n = (u64)t.filled[o] + tot[o];
       need = n > need ? n : need;
     }
-#if FQ_WAVE > 1
-    for (int off = 32; off > 0; off >>= 1) { const u64 y = __shfl_xor(need, off, 64); need = y > need ? y : need; }
-#endif
+    need = wave_max64(need);
     if (FQ_LANE == 0) out[which] = need;
   }
   if (FQ_LANE == 0) out[2] = cfg.err[0];
@@ -455,23 +422,8 @@ FQ_KERNEL64 void k_shard_siv_sum(DevCfg cfg, const u64 *before, const u64 *gathe
 // for the growth rule (k_shard_need).  They ride along with the all-gather: out[which * n_max + j] = filled of this rank's
 // j-th own sub-table of the s- (which 0) / b-mer (1) table ...
 // (n_arr = 3: the pair table's counters behind them -- a partitioned pair table, cfg.pe_part)
-FQ_KERNEL64 void k_shard_fill_pack(DevCfg cfg, u64 *out, u32 n_max, u32 n_arr) {
-  for (u32 i = FQ_LANE; i < n_arr * n_max; i += FQ_WAVE) {
-    const u32 which = i / n_max, o = cfg.shard_rank + (i % n_max) * cfg.shard_world;
-    out[i] = o < cfg.T ? (which == 2 ? cfg.g_pe.filled : which ? cfg.g_b.filled : cfg.g_s.filled)[o] : 0;
-  }
-}
-// ... and the other ranks' counters into this rank's copy of the arrays
-FQ_KERNEL64 void k_shard_fill_unpack(DevCfg cfg, const u64 *gathered, u64 stride, u64 off, u32 n_max, u32 n_arr) {
-  for (u32 q = 0; q < cfg.shard_world; ++q) {
-    if (q == cfg.shard_rank) continue;
-    for (u32 i = FQ_LANE; i < n_arr * n_max; i += FQ_WAVE) {
-      const u32 which = i / n_max, o = q + (i % n_max) * cfg.shard_world;
-      if (o < cfg.T) (which == 2 ? cfg.g_pe.filled : which ? cfg.g_b.filled : cfg.g_s.filled)[o] = (u32)gathered[(u64)q * stride + off + i];
-    }
-  }
-}
-// (partitioned tables: the statistics' delta and the counters in one launch, and the sum and the counters behind the all-gather)
+// ... together with the statistics' delta in one launch, and -- behind the all-gather -- the sum and the other ranks'
+// counters into this rank's copy of the arrays
 FQ_KERNEL64 void k_shard_pack2(DevCfg cfg, const u64 *before, u64 *out_siv, u64 *out_fill, u32 n_max, u32 n_arr) {
   for (u32 i = FQ_LANE; i < 2; i += FQ_WAVE) out_siv[i] = cfg.siv_stats[i] - before[i];
   for (u32 i = FQ_LANE; i < n_arr * n_max; i += FQ_WAVE) {
@@ -580,11 +532,7 @@ FQ_DEV void shard_merge_body(const DevCfg &cfg, u32 kind, u32 o, const u64 *recv
 FQ_KERNEL void k_shard_collect(DevCfg cfg, u32 kind, u64 *out) {
   const Mail &m = cfg.mail[kind];
   const u32 total = m.dst_off[cfg.T];
-#ifndef FQSX_EMU
-  const u32 stride = gridDim.x * blockDim.x, first = blockIdx.x * blockDim.x + threadIdx.x;
-#else
-  const u32 stride = 1, first = 0;
-#endif
+  const u32 stride = FQ_GRID_STRIDE(u32), first = FQ_GRID_FIRST(u32);
   for (u32 e = first; e < total; e += stride) {
     const u64 x = m.sorted[e];
     if (kind == MAIL_P) { out[e] = (x << 2) | siv_test(&cfg, x); continue; }
@@ -596,11 +544,7 @@ FQ_KERNEL void k_shard_collect(DevCfg cfg, u32 kind, u64 *out) {
 }
 // ... and their application to this rank's replica of another rank's sub-tables (layout-free: find or claim the slot)
 FQ_KERNEL void k_shard_apply(DevCfg cfg, u32 kind, const u64 *items, u32 n) {
-#ifndef FQSX_EMU
-  const u32 stride = gridDim.x * blockDim.x, first = blockIdx.x * blockDim.x + threadIdx.x;
-#else
-  const u32 stride = 1, first = 0;
-#endif
+  const u32 stride = FQ_GRID_STRIDE(u32), first = FQ_GRID_FIRST(u32);
   for (u32 e = first; e < n; e += stride) {
     const u64 item = items[e];
     if (kind == MAIL_P && cfg.siv_part) {   // a transition an owner on another rank logged: only the count index is a replica
@@ -628,11 +572,7 @@ FQ_KERNEL void k_shard_apply(DevCfg cfg, u32 kind, const u64 *items, u32 n) {
     u64 *slot = tab_find_or_claim(t, t.slots + (u64)sub * t.stride, v, item, claimed);
     if (!slot) continue;
     if (claimed) {
-#ifndef FQSX_EMU
-      atomicAdd(&t.filled[sub], 1u);
-#else
-      t.filled[sub] += 1;
-#endif
+      atomic_add32(&t.filled[sub], 1u);
       continue;
     }
     u64 old = *(volatile u64 *)slot;   // (counts of a k-mer only grow: the larger value is the later one)
@@ -646,28 +586,9 @@ FQ_KERNEL void k_shard_apply(DevCfg cfg, u32 kind, const u64 *items, u32 n) {
 
 // ---------------------------------------------------------------------------------------
 // backend
-#ifndef FQSX_EMU
-#define HIPCHK(x)                                                                             \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess) {                                                                   \
-      g_err = std::string(#x) + ": " + hipGetErrorString(e_);                                 \
-      return FQSX_E_HIP;                                                                      \
-    }                                                                                         \
-  } while (0)
-#endif
-
-struct fqsx_dna {
+struct fqsx_dna : DevCtx {   // (a new fqsx_dna() starts with every field zero unless it says otherwise here)
   DevCfg cfg;
   u32 T;
-  int device;
-#ifndef FQSX_EMU
-  hipStream_t stream;
-  hipEvent_t ev0, ev1;
-#endif
-  bool profiling;
-  double k_ms[3];
-  u64 k_n[3];
   // capacities (host mirror)
   u64 gs_cap, gb_cap, ls_cap, lb_cap, ctx_cap, out_cap, gpe_cap, lpe_cap;
   u32 pe_cap;
@@ -683,9 +604,6 @@ struct fqsx_dna {
   std::vector<u32> h_demand, h_filled;
   std::vector<u8> h_out;
   std::vector<u64> h_lens;
-  std::vector<void *> allocs;
-  std::vector<u64> alloc_bytes;   // size of allocs[i]
-  u64 dev_bytes, dev_bytes_peak;  // device memory held now / at most so far (fqsx_dna_capacity)
   u32 n_growths;                  // growth events of the global k-mer / pair tables
   u32 tab_small_pct;              // ... while the table is below 256 MB: to this load (40: it doubles; FQSX_TAB_AFTER_PCT sets both)
   u32 tab_load_pct, tab_after_pct;   // a global k-mer sub-table is grown before an insert phase would fill it beyond load_pct %, to a
@@ -698,7 +616,7 @@ struct fqsx_dna {
   u64 cur_need_lb, cur_need_ls, cur_need_lpe;
   bool cur_decode;
   // sharded mode (fqsx_shard_*): exchange scratch
-  u32 shard_rank, shard_world;
+  u32 shard_rank, shard_world = 1;
   u8 *d_vmap;
   u64 *d_xbuf;        // received entries / upsert items
   u64 xbuf_cap;
@@ -736,147 +654,37 @@ struct fqsx_dna {
 
 namespace {
 
-int dalloc(fqsx_dna *c, void **p, u64 bytes, bool zero) {
-  if (bytes == 0) bytes = 8;
-#ifndef FQSX_EMU
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) {
-    g_err = "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e);
-    return FQSX_E_NOMEM;
-  }
-  if (zero) HIPCHK(hipMemsetAsync(*p, 0, bytes, c->stream));
-#else
-  *p = zero ? calloc(1, bytes) : malloc(bytes);
-  if (!*p) { g_err = "host allocation failed"; return FQSX_E_NOMEM; }
-#endif
-  c->allocs.push_back(*p);
-  c->alloc_bytes.push_back(bytes);
-  c->dev_bytes += bytes;
-  c->dev_bytes_peak = std::max(c->dev_bytes_peak, c->dev_bytes);
-  return FQSX_OK;
-}
-void dfree(fqsx_dna *c, void *p) {
-  if (!p) return;
-  auto it = std::find(c->allocs.begin(), c->allocs.end(), p);
-  if (it != c->allocs.end()) {
-    const size_t i = it - c->allocs.begin();
-    c->dev_bytes -= c->alloc_bytes[i];
-    c->alloc_bytes.erase(c->alloc_bytes.begin() + i);
-    c->allocs.erase(it);
-  }
-#ifndef FQSX_EMU
-  (void)hipFree(p);
-#else
-  free(p);
-#endif
-}
-int dzero(fqsx_dna *c, void *p, u64 bytes) {
-#ifndef FQSX_EMU
-  HIPCHK(hipMemsetAsync(p, 0, bytes, c->stream));
-#else
-  (void)c;
-  memset(p, 0, bytes);
-#endif
-  return FQSX_OK;
-}
-int h2d(fqsx_dna *c, void *d, const void *h, u64 bytes) {
-#ifndef FQSX_EMU
-  HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
-#else
-  (void)c;
-  memcpy(d, h, bytes);
-#endif
-  return FQSX_OK;
-}
-int d2d(fqsx_dna *c, void *d, const void *s, u64 bytes) {
-#ifndef FQSX_EMU
-  HIPCHK(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, c->stream));
-#else
-  (void)c;
-  memcpy(d, s, bytes);
-#endif
-  return FQSX_OK;
-}
 #define FQSX_PIN_BYTES (64u * 1024u)
 // small transfer through the pinned scratch: begin (asynchronous), ... more launches ..., end (waits, copies out)
-int d2h_small_begin(fqsx_dna *c, const void *d, u64 bytes) {
-#ifndef FQSX_EMU
-  HIPCHK(hipMemcpyAsync(c->h_pin, d, bytes, hipMemcpyDeviceToHost, c->stream));
-#else
-  memcpy(c->h_pin, d, bytes);
-#endif
-  return FQSX_OK;
-}
+int d2h_small_begin(fqsx_dna *c, const void *d, u64 bytes) { return d2h(c, c->h_pin, d, bytes); }
 int d2h_small_end(fqsx_dna *c, void *h, u64 bytes) {
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   memcpy(h, c->h_pin, bytes);
   return FQSX_OK;
 }
-int d2h_sync(fqsx_dna *c, void *h, const void *d, u64 bytes) {
-#ifndef FQSX_EMU
-  HIPCHK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-#else
-  (void)c;
-  memcpy(h, d, bytes);
-#endif
-  return FQSX_OK;
-}
 
-#ifndef FQSX_EMU
-#define LAUNCH(c, kidx, kern, grid, block, ...)                                     \
-  do {                                                                              \
-    if ((c)->profiling) HIPCHK(hipEventRecord((c)->ev0, (c)->stream));              \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, (c)->stream, __VA_ARGS__); \
-    HIPCHK(hipGetLastError());                                                      \
-    if ((c)->profiling) {                                                           \
-      HIPCHK(hipEventRecord((c)->ev1, (c)->stream));                                \
-      HIPCHK(hipEventSynchronize((c)->ev1));                                        \
-      float ms_ = 0;                                                                \
-      HIPCHK(hipEventElapsedTime(&ms_, (c)->ev0, (c)->ev1));                        \
-      (c)->k_ms[kidx] += ms_;                                                       \
-      (c)->k_n[kidx] += 1;                                                          \
-    }                                                                               \
-  } while (0)
-#else
-#define LAUNCH(c, kidx, kern, grid, block, ...)       \
-  do {                                                \
-    fq_emu_nblocks = (grid);                          \
-    for (u32 b_ = 0; b_ < (u32)(grid); ++b_) {        \
-      fq_emu_block = b_;                              \
-      kern(__VA_ARGS__);                              \
-    }                                                 \
-    (c)->k_n[kidx] += 1;                              \
-  } while (0)
-#endif
-
-#ifndef FQSX_EMU
-#define REHASH_GRID 2048
-#else
-#define REHASH_GRID 1  /* the emulated kernel body already walks every slot */
-#endif
+#define REHASH_GRID FQ_GRID(2048)
 
 // The T streams a quality / id kernel left in [T][out_cap] (lengths lens_host, already read back and checked against out_cap)
 // -> one contiguous host buffer: a compaction launch and ONE transfer instead of a transfer and a synchronisation per worker
-int collect_streams(fqsx_dna *c, u32 T, const u8 *d_out, u64 out_cap, const u64 *d_lens, const std::vector<u64> &lens_host,
-                    std::vector<u8> &h_out, const u8 **streams, u64 *lens) {
+// (d_compact / compact_cap: the caller's compaction buffer, grown here)
+int collect_streams(DevCtx *c, u8 *&d_compact, u64 &compact_cap, u32 T, const u8 *d_out, u64 out_cap, const u64 *d_lens,
+                    const std::vector<u64> &lens_host, std::vector<u8> &h_out, const u8 **streams, u64 *lens) {
   int rc;
   void *p = nullptr;
   u64 total = 0;
   for (u32 t = 0; t < T; ++t) total += lens_host[t];
-  if (total > c->compact_cap) {
-    dfree(c, c->d_compact);
-    c->d_compact = nullptr; c->compact_cap = 0;
+  if (total > compact_cap) {
+    dfree(c, d_compact);
+    d_compact = nullptr; compact_cap = 0;
     if ((rc = dalloc(c, &p, total + total / 2 + 4096, false))) return rc;
-    c->d_compact = (u8 *)p;
-    c->compact_cap = total + total / 2 + 4096;
+    d_compact = (u8 *)p;
+    compact_cap = total + total / 2 + 4096;
   }
   h_out.resize(total ? total : 1);
   if (total) {
-    LAUNCH(c, 2, k_compact_generic, T, 64, d_out, out_cap, d_lens, c->d_compact);
-    if ((rc = d2h_sync(c, h_out.data(), c->d_compact, total))) return rc;
+    LAUNCH(c, 2, k_compact_generic, T, 64, d_out, out_cap, d_lens, d_compact);
+    if ((rc = d2h_sync(c, h_out.data(), d_compact, total))) return rc;
   }
   u64 pos = 0;
   for (u32 t = 0; t < T; ++t) {
@@ -967,15 +775,18 @@ void vtab_free(fqsx_dna *c, fqsx_dna::VmTab &v) {
   v = fqsx_dna::VmTab();
 }
 // the address range of T sub-tables with `cap` 8-byte slots each (*stride: slots from one sub-table to the next); nothing mapped yet
+// the smallest chunk: on the GPU at least 2 MiB (and 2 MiB-aligned, vtab_reserve_raw): with 4 KiB-granular chunks the 1 M-read
+// file ran 7 % slower than on hipMalloc'ed tables (blocks 0-69: 10 %) -- page-table fragments of the size of the chunk
+u64 vm_min_chunk(const fqsx_dna *c) {
+#ifndef FQSX_EMU
+  return std::max<u64>(c->vm_gran, 2ull << 20);
+#else
+  return c->vm_gran;
+#endif
+}
 int vtab_reserve_raw(fqsx_dna *c, fqsx_dna::VmTab &v, u64 cap, u64 *stride_out, u32 n_chunks = 0) {
   const u32 T = n_chunks ? n_chunks : c->T;
-#ifndef FQSX_EMU
-  // a chunk is at least 2 MiB (and 2 MiB-aligned, below): with 4 KiB-granular chunks the 1 M-read file ran 7 % slower than on
-  // hipMalloc'ed tables (blocks 0-69: 10 %) -- page-table fragments of the size of the chunk
-  const u64 min_chunk = std::max<u64>(c->vm_gran, 2ull << 20);
-#else
-  const u64 min_chunk = c->vm_gran;
-#endif
+  const u64 min_chunk = vm_min_chunk(c);
   // (a sub-table is one chunk: its capacity rounded up to the chunk granule -- at most 2 MiB of slack per sub-table)
   const u64 gran_slots = min_chunk / sizeof(u64);
   const u64 stride = (cap + gran_slots - 1) / gran_slots * gran_slots;
@@ -1091,9 +902,7 @@ int grow_global(fqsx_dna *c, KTab &t, u64 &cap_field, u64 new_cap) {
       for (u32 j = 0; j < nb; ++j)
         if ((rc = vtab_create_own(c, nv, first + j * G))) return rc;
       LAUNCH(c, 2, k_rehash_ktab, REHASH_GRID, 256, t, n, nb, first, G, c->cfg.sys_scope);
-#ifndef FQSX_EMU
-      HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+      DEVCHK(dev_sync(c));
       if (old_chunked)
         for (u32 j = 0; j < nb; ++j) vtab_drop(c, v, first + j * G);
     }
@@ -1103,9 +912,7 @@ int grow_global(fqsx_dna *c, KTab &t, u64 &cap_field, u64 new_cap) {
   } else {
     if ((rc = ktab_alloc(c, n, c->T, new_cap, t.k, t.cbits, false))) return rc;
     LAUNCH(c, 2, k_rehash_ktab, REHASH_GRID, 256, t, n, c->T, 0u, 1u, 0u);
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
     dfree(c, t.slots);
   }
   t = n;
@@ -1164,9 +971,7 @@ int grow_gpe(fqsx_dna *c, u64 new_cap) {
       for (u32 j = 0; j < nb; ++j)
         if ((rc = vtab_create_own(c, nk, first + j * G)) || (rc = vtab_create_own(c, nv, first + j * G))) return rc;
       LAUNCH(c, 2, k_rehash_ptab, REHASH_GRID, 256, c->cfg.g_pe, n, nb, first, G, c->cfg.sys_scope);
-#ifndef FQSX_EMU
-      HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+      DEVCHK(dev_sync(c));
       if (old_chunked)
         for (u32 j = 0; j < nb; ++j) { vtab_drop(c, c->vm_pk, first + j * G); vtab_drop(c, c->vm_pv, first + j * G); }
     }
@@ -1178,9 +983,7 @@ int grow_gpe(fqsx_dna *c, u64 new_cap) {
   } else {
     if ((rc = ptab_alloc(c, n, c->T, new_cap, false))) return rc;
     LAUNCH(c, 2, k_rehash_ptab, REHASH_GRID, 256, c->cfg.g_pe, n, c->T, 0u, 1u, 0u);
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
     dfree(c, c->cfg.g_pe.key);
     dfree(c, c->cfg.g_pe.val);
   }
@@ -1195,9 +998,7 @@ int grow_ctx(fqsx_dna *c, u64 new_cap) {
   int rc = dalloc(c, &p, new_cap * c->T * sizeof(CtxSlot), true);
   if (rc) return rc;
   LAUNCH(c, 2, k_rehash_ctx, REHASH_GRID, 256, (const u64 *)c->cfg.ctx, c->cfg.ctx_cap_mask, (u64 *)p, new_cap - 1, c->T);
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   dfree(c, c->cfg.ctx);
   c->cfg.ctx = (CtxSlot *)p;
   c->cfg.ctx_cap_mask = new_cap - 1;
@@ -1224,27 +1025,14 @@ int mail_alloc(fqsx_dna *c, u32 kind, u32 cap) {
   return FQSX_OK;
 }
 
-// one encode / decode launch over segment `seg` (T workgroups); timed with HIP events when profiling is on
+// one encode / decode launch over segment `seg` (T workgroups), kernel index 0: timed when profiling is on, counted always
 int launch_segment(fqsx_dna *c, bool decode, u32 n_reads, u32 S, u32 seg) {
   EncArgs a;
   a.cfg = c->cfg;
   a.n_reads = n_reads; a.S = S; a.seg = seg; a.pad = (u32)c->k_n[0];   // (launch index: time stamps of the timing build)
-#ifndef FQSX_EMU
-  if (c->profiling) HIPCHK(hipEventRecord(c->ev0, c->stream));
-  const int e = decode ? fqsx_launch_decode(c->stream, a) : c->paired ? fqsx_launch_encode_pe(c->stream, a) : fqsx_launch_encode_se(c->stream, a);
-  if (e) { g_err = std::string("encode/decode kernel launch: ") + hipGetErrorString((hipError_t)e); return FQSX_E_HIP; }
-  if (c->profiling) {
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->k_ms[0] += ms;
-  }
-#else
-  if (decode) fqsx_emu_decode(a); else if (c->paired) fqsx_emu_encode_pe(a); else fqsx_emu_encode_se(a);
-#endif
-  c->k_n[0] += 1;
-  return FQSX_OK;
+  return dev_launch(c, 0, true, [&] {
+    return decode ? fqsx_launch_decode(c->stream, a) : c->paired ? fqsx_launch_encode_pe(c->stream, a) : fqsx_launch_encode_se(c->stream, a);
+  });
 }
 
 // Sizes the per-block buffers and fixes the block's schedule (number of synchronisation points S)
@@ -1388,9 +1176,7 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
     for (u32 t = 0; t < T; ++t) memcpy(flat.data() + doff[t], dec_streams[t], dec_lens[t]);
     if ((rc = h2d(c, (void *)cfg.din, flat.data(), doff[T]))) return rc;
     if ((rc = h2d(c, (void *)cfg.din_off, doff.data(), (T + 1) * sizeof(u64)))) return rc;
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
   }
 
   c->cur_n_reads = n_reads; c->cur_S = (u32)S; c->cur_gen = generation;
@@ -1483,11 +1269,7 @@ int block_segment(fqsx_dna *c, u32 seg) {
       // encoding: nothing is read back inside a block -- the growth checks are the device's (phase_skip)
       LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, seg + 1, c->d_demand);   // (group offsets, demand words and growth check included)
       if (c->paired) {   // pair table: triples grouped by owner (count, offsets + growth check, scatter), then every owner's own group
-#ifndef FQSX_EMU
-        const u32 bgrid = (u32)std::min<u64>(1024, ((u64)T * cfg.pe_cap + 255) / 256);
-#else
-        const u32 bgrid = 1;   // (the emulated kernel body already walks every triple)
-#endif
+        const u32 bgrid = FQ_GRID((u32)std::min<u64>(1024, ((u64)T * cfg.pe_cap + 255) / 256));
         LAUNCH(c, 2, k_pe_bucket_count, bgrid, 256, cfg);
         LAUNCH(c, 2, k_pe_bucket_offsets, 1, 64, cfg, seg + 1);
         LAUNCH(c, 2, k_pe_bucket_scatter, bgrid, 256, cfg);
@@ -1665,9 +1447,7 @@ int create_impl(fqsx_dna *c, const u8 *h) {
     if ((rc = dalloc(c, &p, (u64)T * SM_TOTAL_U16 * sizeof(u16), false))) return rc;
     cfg.small = (u16 *)p;
     if ((rc = h2d(c, cfg.small, tpl.data(), tpl.size() * sizeof(u16)))) return rc;
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
     for (u32 t = 1; t < T; ++t)
       if ((rc = d2d(c, cfg.small + (u64)t * SM_TOTAL_U16, cfg.small, tpl.size() * sizeof(u16)))) return rc;
     if ((rc = dalloc(c, &p, (u64)T * SM_LAZY_ENTRIES, true))) return rc;
@@ -1685,9 +1465,7 @@ int create_impl(fqsx_dna *c, const u8 *h) {
     cfg.ws = (WState *)p;
     for (u32 t = 0; t < T; ++t)
       if ((rc = h2d(c, cfg.ws + t, ws.data(), sizeof(WState)))) return rc;
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
   }
   for (u32 k = 0; k < 3; ++k) {
     if ((rc = dalloc(c, &p, (u64)T * sizeof(u32), true))) return rc;
@@ -1720,9 +1498,7 @@ int create_impl(fqsx_dna *c, const u8 *h) {
     c->d_vmap = (u8 *)p;
     cfg.vmap = c->d_vmap;
     if ((rc = h2d(c, c->d_vmap, ident, 256))) return rc;
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
   }
   cfg.shard_rank = 0; cfg.shard_world = 1; cfg.shard_cnt = nullptr;
   if ((rc = dalloc(c, &p, sizeof(u32) * 4, true))) return rc;
@@ -1737,18 +1513,11 @@ int create_impl(fqsx_dna *c, const u8 *h) {
   c->d_lens = (u64 *)p;
   if ((rc = dalloc(c, &p, (2 * (u64)T + 2) * sizeof(u64), true))) return rc;
   c->d_end = (u64 *)p;
-#ifndef FQSX_EMU
-  HIPCHK(hipHostMalloc((void **)&c->h_pin, FQSX_PIN_BYTES));
-#else
-  c->h_pin = (u8 *)malloc(FQSX_PIN_BYTES);
-#endif
-  c->filled_valid = false;
+  if ((rc = pinned_alloc((void **)&c->h_pin, FQSX_PIN_BYTES))) return rc;
   c->h_demand.assign(4 * T + 1, 0);
   c->h_filled.assign(T, 0);
   c->h_lens.assign(T + 64, 0);
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   return FQSX_OK;
 }
 
@@ -1771,60 +1540,14 @@ int fqsx_dna_create_on_partition(const uint8_t *h, int device, uint32_t part, ui
     g_err = "unsupported k-mer lengths";
     return FQSX_E_ARG;
   }
-#ifndef FQSX_EMU
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g_err = "no HIP device available (libfqsx has no CPU path)";
-    return FQSX_E_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) { g_err = "bad device ordinal"; return FQSX_E_ARG; }
-  HIPCHK(hipSetDevice(device));
-#endif
   fqsx_dna *c = new fqsx_dna();
   c->T = h[4];
-  c->device = device;
-  c->profiling = false;
-  c->k_ms[0] = c->k_ms[1] = c->k_ms[2] = 0;
-  c->k_n[0] = c->k_n[1] = c->k_n[2] = 0;
-  c->out_cap = 0;
-  c->mail_cap[0] = c->mail_cap[1] = c->mail_cap[2] = 0;
-  c->dev_bases_cap = c->dev_off_cap = 0;
-  c->d_bases = nullptr;
-  c->d_off = nullptr;
-  c->d_compact = nullptr;
-  c->compact_cap = 0;
-  c->din_cap = c->dout_cap = 0;
-  c->shard_rank = 0; c->shard_world = 1;
-  c->comm_set = false; c->shard_apply_own = false;
-  memset(&c->comm, 0, sizeof(c->comm));
-  for (int k = 0; k < 3; ++k) { c->d_xrecv[k] = nullptr; c->xrecv_cap[k] = 0; }
-  c->d_items = c->d_gathered = c->d_small = nullptr; c->items_cap = c->gathered_cap = 0;
-  c->sh_phases = c->sh_collectives = c->sh_a2a_words = c->sh_gather_words = 0;
-  c->part = false; c->part_fallback = false; c->vm_gran = 0; c->vm_own_bytes = 0;
-  c->dev_bytes = c->dev_bytes_peak = 0; c->n_growths = 0;
-  c->h_pin = nullptr; c->d_end = nullptr; c->filled_valid = false;
-  c->d_vmap = nullptr; c->d_xbuf = nullptr; c->xbuf_cap = 0; c->d_cglob = nullptr;
-  c->cur_n_reads = c->cur_S = c->cur_gen = 0;
-  c->cur_need_lb = c->cur_need_ls = c->cur_need_lpe = 0;
-  c->cur_decode = false;
-#ifndef FQSX_EMU
-  hipError_t se;
-  if (n_parts > 1) {   // a stream whose kernels only run on this partition's compute units
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { g_err = "hipGetDeviceProperties failed"; delete c; return FQSX_E_HIP; }
-    const u32 ncu = (u32)prop.multiProcessorCount, lo = (u32)((u64)part * ncu / n_parts), hi = (u32)(((u64)part + 1) * ncu / n_parts);
-    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-    for (u32 i = lo; i < hi; ++i) mask[i / 32] |= 1u << (i % 32);
-    se = hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)mask.size(), mask.data());
-  } else
-    se = hipStreamCreate(&c->stream);
-  if (se != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
-    g_err = "hipStreamCreate / hipEventCreate failed";
+  int rc = dev_open(c, device, part, n_parts);
+  if (rc) {
     delete c;
-    return FQSX_E_HIP;
+    return rc;
   }
-#endif
-  int rc = create_impl(c, h);
+  rc = create_impl(c, h);
   if (!rc && getenv("FQSX_CHUNKED_TABLES") && atoi(getenv("FQSX_CHUNKED_TABLES"))) rc = fqsx_dna_use_chunked_tables(c);
   if (rc) {
     fqsx_dna_destroy(c);
@@ -1836,44 +1559,28 @@ int fqsx_dna_create_on_partition(const uint8_t *h, int device, uint32_t part, ui
 
 void fqsx_dna_destroy(fqsx_dna *c) {
   if (!c) return;
-#ifndef FQSX_EMU
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-#endif
+  dev_close(c);   // (the stream is drained before anything is handed back)
   vtab_free(c, c->vm_s);
   vtab_free(c, c->vm_b);
   vtab_free(c, c->vm_pk);
   vtab_free(c, c->vm_pv);
   vtab_free(c, c->vm_siv);
   fqsx_vm::mesh_close(c->mesh);
-  std::vector<void *> a = c->allocs;
-  for (void *p : a) dfree(c, p);
-#ifndef FQSX_EMU
-  if (c->h_pin) (void)hipHostFree(c->h_pin);
-  (void)hipEventDestroy(c->ev0);
-  (void)hipEventDestroy(c->ev1);
-  (void)hipStreamDestroy(c->stream);
-#else
-  free(c->h_pin);
-#endif
+  pinned_free(c->h_pin);
   delete c;
 }
 
 int fqsx_dna_encode_block_dev(fqsx_dna *c, const uint8_t *d_bases, const uint64_t *d_off, const uint64_t *h_off,
                               uint32_t n_reads, uint32_t generation, const uint8_t **streams, uint64_t *lens) {
   if (!c || !d_bases || !d_off || !h_off || !streams || !lens) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   return encode_block_impl(c, d_bases, d_off, h_off, n_reads, generation, streams, lens);
 }
 
 int fqsx_dna_encode_block(fqsx_dna *c, const uint8_t *bases, const uint64_t *off, uint32_t n_reads, uint32_t generation,
                           const uint8_t **streams, uint64_t *lens) {
   if (!c || !bases || !off || !streams || !lens) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   int rc;
   void *p = nullptr;
   u64 nb = off[n_reads] + 64, no = ((u64)n_reads + 1) * sizeof(u64);
@@ -1897,9 +1604,7 @@ int fqsx_dna_encode_block(fqsx_dna *c, const uint8_t *bases, const uint64_t *off
 int fqsx_dna_decode_block(fqsx_dna *c, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *off, uint32_t n_reads,
                           uint32_t generation, uint8_t *bases_out) {
   if (!c || !streams || !lens || !off || !bases_out) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   int rc;
   void *p = nullptr;
   u64 no = ((u64)n_reads + 1) * sizeof(u64);
@@ -1919,9 +1624,7 @@ int fqsx_dna_decode_block(fqsx_dna *c, const uint8_t *const *streams, const uint
 int fqsx_shard_config(fqsx_dna *c, uint32_t rank, uint32_t world) {
   if (!c || world == 0 || rank >= world || world > c->T) { g_err = "bad rank / world size"; return FQSX_E_ARG; }
   if (c->part && world > 1) { g_err = "a codec with chunked tables cannot be sharded afterwards (fqsx_shard_partition_tables after the attach)"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   const u32 T = c->T;
   c->shard_rank = rank; c->shard_world = world;
   c->cfg.shard_rank = rank; c->cfg.shard_world = world;
@@ -1945,9 +1648,7 @@ int fqsx_shard_config(fqsx_dna *c, uint32_t rank, uint32_t world) {
     c->d_small = (u64 *)p;
     c->h_cglob.assign(3ull * T * T + T + 1, 0);
   }
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   return FQSX_OK;
 }
 
@@ -1958,9 +1659,7 @@ int fqsx_shard_begin_block(fqsx_dna *c, const uint8_t *bases /*[codec]*/, const 
   // the step-wise driver exchanges the three k-mer mailboxes only: the pair-table triples of a paired-end file travel with
   // the native loop's all-gather (shard_phase_native), nowhere else -- a world of several ranks would leave the pair table empty
   if (c->paired && c->shard_world > 1) { g_err = "paired-end files are sharded through fqsx_shard_attach + fqsx_shard_encode_block (the step-wise fqsx_shard_* driver does not exchange the pair-table triples)"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   int rc = block_prepare(c, bases, off, h_off, n_reads, generation);
   *n_segments = c->cur_S + 1;
   return rc;
@@ -1969,9 +1668,7 @@ int fqsx_shard_begin_block(fqsx_dna *c, const uint8_t *bases /*[codec]*/, const 
 // encode launch of segment `seg` for this rank's workers, then the per-(source, owner) counts of their mailboxes
 int fqsx_shard_encode(fqsx_dna *c, uint32_t seg, uint32_t *counts /*[codec] [3][T][T]*/) {
   if (!c || !counts) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   const u32 T = c->T;
   DevCfg &cfg = c->cfg;
   int rc;
@@ -1989,9 +1686,7 @@ int fqsx_shard_encode(fqsx_dna *c, uint32_t seg, uint32_t *counts /*[codec] [3][
 // the entries of this rank's workers in send order (destination rank, owner, source, push) -> send[kind]
 int fqsx_shard_pack(fqsx_dna *c, const uint32_t *counts_sum /*[codec] summed over ranks*/, uint64_t *const send[3] /*[codec]*/) {
   if (!c || !counts_sum || !send) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   const u32 T = c->T;
   DevCfg &cfg = c->cfg;
   int rc;
@@ -2007,9 +1702,7 @@ int fqsx_shard_pack(fqsx_dna *c, const uint32_t *counts_sum /*[codec] summed ove
     const u64 n = tot[k * (T + 1) + T];
     if (n && (rc = d2d(c, send[k], cfg.mail[k].sorted, n * sizeof(u64)))) return rc;
   }
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   return FQSX_OK;
 }
 
@@ -2017,9 +1710,7 @@ int fqsx_shard_pack(fqsx_dna *c, const uint32_t *counts_sum /*[codec] summed ove
 // demand for the s- / b-mer tables (occupied + incoming slots of its fullest sub-table)
 int fqsx_shard_merge(fqsx_dna *c, const uint64_t *const recv[3] /*[codec]*/, uint64_t need[2]) {
   if (!c || !recv || !need) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   const u32 T = c->T;
   DevCfg &cfg = c->cfg;
   int rc;
@@ -2039,9 +1730,7 @@ int fqsx_shard_merge(fqsx_dna *c, const uint64_t *const recv[3] /*[codec]*/, uin
 // applied entry for the other ranks' replicas; siv_delta = this rank's contribution to (no_updates, no_filled)
 int fqsx_shard_insert(fqsx_dna *c, uint64_t need_s, uint64_t need_b, uint64_t *const items[3] /*[codec]*/, uint64_t siv_delta[2]) {
   if (!c || !items || !siv_delta) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   const u32 T = c->T;
   DevCfg &cfg = c->cfg;
   int rc;
@@ -2054,18 +1743,14 @@ int fqsx_shard_insert(fqsx_dna *c, uint64_t need_s, uint64_t need_b, uint64_t *c
   siv_delta[0] = after[0] - c->siv_before[0];
   siv_delta[1] = after[1] - c->siv_before[1];
   for (u32 k = 0; k < 3; ++k) LAUNCH(c, 2, k_shard_collect, REHASH_GRID, 256, cfg, k, items[k]);
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   return FQSX_OK;
 }
 
 // another rank's items of one kind into this rank's replica
 int fqsx_shard_apply(fqsx_dna *c, uint32_t kind, const uint64_t *items /*[codec]*/, uint64_t n) {
   if (!c || kind > 2 || (!items && n)) { g_err = "bad argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   if (n) LAUNCH(c, 2, k_shard_apply, REHASH_GRID, 256, c->cfg, kind, items, (u32)n);
   return FQSX_OK;
 }
@@ -2073,24 +1758,18 @@ int fqsx_shard_apply(fqsx_dna *c, uint32_t kind, const uint64_t *items /*[codec]
 // end of the phase: the p-mer vector's statistics become the sum over the ranks, the local tables are cleared
 int fqsx_shard_end_phase(fqsx_dna *c, const uint64_t siv_delta_sum[2]) {
   if (!c || !siv_delta_sum) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   int rc;
   u64 now[2] = {c->siv_before[0] + siv_delta_sum[0], c->siv_before[1] + siv_delta_sum[1]};
   if ((rc = h2d(c, c->cfg.siv_stats, now, 2 * sizeof(u64)))) return rc;
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   return clear_local_tables(c);
 }
 
 // streams of the block (only those of this rank's workers are meaningful)
 int fqsx_shard_finish_block(fqsx_dna *c, const uint64_t *h_off, const uint8_t **streams, uint64_t *lens) {
   if (!c || !h_off || !streams || !lens) { g_err = "null argument"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   return block_finish(c, h_off, streams, lens, nullptr);
 }
 
@@ -2126,9 +1805,7 @@ int shard_vote(fqsx_dna *c, int fail, const char *what) {
   const std::string mine = g_err;
   int rc;
   if ((rc = h2d(c, word, &v, sizeof(v)))) return rc;
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));   // (v is a stack variable)
-#endif
+  DEVCHK(dev_sync(c));   // (v is a stack variable)
   COMMCHK(c->comm.allreduce_sum_u32(c->comm.ctx, word, 1), "all-reduce of the phase's status vote");
   if ((rc = d2h_sync(c, &v, word, sizeof(v)))) return rc;
   c->sh_collectives += 1;
@@ -2152,11 +1829,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
   LAUNCH(c, 2, k_shard_need, 1, 64, cfg, (const u32 *)c->d_colsum, c->d_small + 2, c->d_small);
   // ---- the phase's one host round trip: every transfer size, the table demand, the error word
   u64 small[3];
-#ifndef FQSX_EMU
-  HIPCHK(hipMemcpyAsync(c->h_cglob.data(), c->d_cglob, NC * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-#else
-  memcpy(c->h_cglob.data(), c->d_cglob, NC * sizeof(u32));
-#endif
+  if ((rc = d2h(c, c->h_cglob.data(), c->d_cglob, NC * sizeof(u32)))) return rc;
   if ((rc = d2h_sync(c, small, c->d_small + 2, sizeof(small)))) return rc;
   const u32 *C = c->h_cglob.data();
   if (C[NC - 1]) {   // a device error somewhere in the world: every rank sees the same word and leaves here
@@ -2323,12 +1996,7 @@ int tables_to_chunks(fqsx_dna *c) {
   // default geometry has 4 MiB ranges); smaller vectors stay replicas.  The count index (1/256 of the vector) stays a replica.
   if (c->shard_world > 1 && !(getenv("FQSX_SIV_REPLICA") && atoi(getenv("FQSX_SIV_REPLICA")))) {
     const u64 siv_bytes = (1ull << (2 * c->cfg.pmer)) / 4, range_bytes = siv_bytes / 4096;
-#ifndef FQSX_EMU
-    const u64 min_chunk = std::max<u64>(c->vm_gran, 2ull << 20);
-#else
-    const u64 min_chunk = c->vm_gran;
-#endif
-    if (range_bytes >= min_chunk && range_bytes % c->vm_gran == 0 && c->cfg.pmer_mod_shift == 2 * c->cfg.pmer - 12) {
+    if (range_bytes >= vm_min_chunk(c) && range_bytes % c->vm_gran == 0 && c->cfg.pmer_mod_shift == 2 * c->cfg.pmer - 12) {
       rlimit rl;   // (own chunks keep a descriptor each in the emulation build; exports are transient)
       if (getrlimit(RLIMIT_NOFILE, &rl) == 0 && rl.rlim_cur < 16384 && rl.rlim_cur < rl.rlim_max) {
         rl.rlim_cur = std::min<rlim_t>(rl.rlim_max, 16384);
@@ -2352,9 +2020,7 @@ int tables_to_chunks(fqsx_dna *c) {
       c->cfg.p_log_n = c->d_plog_n;
     }
   }
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   return FQSX_OK;
 }
 }  // namespace
@@ -2366,9 +2032,7 @@ int fqsx_dna_use_chunked_tables(fqsx_dna *c) {
   if (!c) { g_err = "null argument"; return FQSX_E_ARG; }
   if (c->part) return FQSX_OK;
   if (c->k_n[0] || c->shard_world > 1) { g_err = "chunked tables are chosen before the first block (sharded codecs: fqsx_shard_partition_tables)"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   return tables_to_chunks(c);
 }
 
@@ -2378,9 +2042,7 @@ int fqsx_shard_partition_tables(fqsx_dna *c) {
   if (!c || !c->comm_set) { g_err = "no transport attached (fqsx_shard_attach)"; return FQSX_E_ARG; }
   if (c->part && (c->shard_world == 1 || !c->mesh.peer.empty())) return FQSX_OK;
   if (c->part || c->k_n[0]) { g_err = "the tables can only be partitioned before the first block"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   const u32 G = c->shard_world, me = c->shard_rank;
   int rc;
   c->part_fallback = false;
@@ -2398,7 +2060,7 @@ int fqsx_shard_partition_tables(fqsx_dna *c) {
     if ((rc = xbuf_fit(c, c->d_items, c->items_cap, 2))) return rc;
     if ((rc = xbuf_fit(c, c->d_gathered, c->gathered_cap, 2ull * G))) return rc;
     if ((rc = h2d(c, c->d_items, mine, sizeof(mine)))) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    DEVCHK(dev_sync(c));
     COMMCHK(c->comm.allgather_u64(c->comm.ctx, c->d_items, 2, c->d_gathered), "all-gather of the ranks' PCI bus ids");
     if ((rc = d2h_sync(c, all.data(), c->d_gathered, all.size() * sizeof(u64)))) return rc;
     std::string why;
@@ -2413,7 +2075,7 @@ int fqsx_shard_partition_tables(fqsx_dna *c) {
     u32 v = why.empty() ? 0u : 1u;
     u32 *word = c->d_cglob;
     if ((rc = h2d(c, word, &v, sizeof(v)))) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    DEVCHK(dev_sync(c));
     COMMCHK(c->comm.allreduce_sum_u32(c->comm.ctx, word, 1), "all-reduce of the peer-access check");
     if ((rc = d2h_sync(c, &v, word, sizeof(v)))) return rc;
     if (v) {
@@ -2436,9 +2098,7 @@ int fqsx_shard_partition_tables(fqsx_dna *c) {
   // ---- the (still empty) tables again, partitioned; nobody looks a k-mer up before every rank's chunks are cleared
   if ((rc = tables_to_chunks(c))) return rc;
   COMMCHK(c->comm.allgather_u64(c->comm.ctx, c->d_items, 1, c->d_gathered), "barrier after the table partition");
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   return FQSX_OK;
 }
 
@@ -2446,9 +2106,7 @@ int fqsx_shard_encode_block(fqsx_dna *c, const uint8_t *bases, const uint64_t *o
                             uint32_t generation, const uint8_t **streams, uint64_t *lens) {
   if (!c || !bases || !off || !h_off || !streams || !lens) { g_err = "null argument"; return FQSX_E_ARG; }
   if (!c->comm_set) { g_err = "no transport attached (fqsx_shard_attach)"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   int rc = block_prepare(c, bases, off, h_off, n_reads, generation);
   for (u32 seg = 0; !rc && seg <= c->cur_S; ++seg) rc = shard_phase_native(c, seg);
   if (rc) return rc;
@@ -2528,10 +2186,8 @@ void rccl_abort(void *ctx) {
   if (x && !x->aborted) { x->aborted = true; (void)g_rccl.CommAbort(x->comm); }
 }
 }  // namespace
-#endif
 
 int fqsx_rccl_unique_id(uint8_t id[128]) {
-#ifndef FQSX_EMU
   if (!id) return FQSX_E_ARG;
   if (!rccl_load()) return FQSX_E_HIP;
   static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
@@ -2539,17 +2195,11 @@ int fqsx_rccl_unique_id(uint8_t id[128]) {
   if (g_rccl.GetUniqueId(&u) != ncclSuccess) { g_err = "ncclGetUniqueId failed"; return FQSX_E_HIP; }
   memcpy(id, &u, 128);
   return FQSX_OK;
-#else
-  (void)id;
-  g_err = "the emulation build has no RCCL transport";
-  return FQSX_E_NO_DEVICE;
-#endif
 }
 int fqsx_rccl_comm_create(fqsx_dna *c, const uint8_t id[128], uint32_t rank, uint32_t world, fqsx_comm *out) {
-#ifndef FQSX_EMU
   if (!c || !id || !out || world == 0 || rank >= world) { g_err = "bad argument"; return FQSX_E_ARG; }
   if (!rccl_load()) return FQSX_E_HIP;
-  HIPCHK(hipSetDevice(c->device));
+  DEVCHK(dev_enter(c));
   ncclUniqueId u;
   memcpy(&u, id, 128);
   RcclCtx *x = new RcclCtx();
@@ -2564,66 +2214,49 @@ int fqsx_rccl_comm_create(fqsx_dna *c, const uint8_t id[128], uint32_t rank, uin
   out->allgather_u64 = rccl_allgather;
   out->abort = rccl_abort;
   return FQSX_OK;
-#else
-  (void)c; (void)id; (void)rank; (void)world; (void)out;
-  g_err = "the emulation build has no RCCL transport";
-  return FQSX_E_NO_DEVICE;
-#endif
 }
 // the communicator of one codec for the next one (a file per codec, one communicator per process: ncclCommInitRank takes
 // seconds): from now on the collectives run on `c`'s stream
 int fqsx_rccl_comm_rebind(fqsx_comm *m, fqsx_dna *c) {
-#ifndef FQSX_EMU
   if (!m || !m->ctx || !c) { g_err = "bad argument"; return FQSX_E_ARG; }
   ((RcclCtx *)m->ctx)->stream = c->stream;
   return FQSX_OK;
-#else
-  (void)m; (void)c;
-  g_err = "the emulation build has no RCCL transport";
-  return FQSX_E_NO_DEVICE;
-#endif
 }
 // out[0] = ranks of the communicator as RCCL counts them, out[1] = this process's rank in it
 int fqsx_rccl_comm_info(fqsx_comm *m, uint32_t out[2]) {
-#ifndef FQSX_EMU
   if (!m || !m->ctx || !out) { g_err = "bad argument"; return FQSX_E_ARG; }
   RcclCtx *x = (RcclCtx *)m->ctx;
   int n = 0, r = 0;
   if (g_rccl.CommCount(x->comm, &n) != ncclSuccess || g_rccl.CommUserRank(x->comm, &r) != ncclSuccess) { g_err = "ncclCommCount / ncclCommUserRank failed"; return FQSX_E_HIP; }
   out[0] = (u32)n; out[1] = (u32)r;
   return FQSX_OK;
-#else
-  (void)m; (void)out;
-  g_err = "the emulation build has no RCCL transport";
-  return FQSX_E_NO_DEVICE;
-#endif
 }
 void fqsx_rccl_comm_destroy(fqsx_comm *m) {
-#ifndef FQSX_EMU
   if (!m || !m->ctx) return;
   RcclCtx *x = (RcclCtx *)m->ctx;
   if (g_rccl.CommDestroy && !x->aborted) (void)g_rccl.CommDestroy(x->comm);
   delete x;
   m->ctx = nullptr;
-#else
-  (void)m;
-#endif
 }
+#else   // the emulation build has no RCCL transport
+static int no_rccl() { g_err = "the emulation build has no RCCL transport"; return FQSX_E_NO_DEVICE; }
+int fqsx_rccl_unique_id(uint8_t *) { return no_rccl(); }
+int fqsx_rccl_comm_create(fqsx_dna *, const uint8_t *, uint32_t, uint32_t, fqsx_comm *) { return no_rccl(); }
+int fqsx_rccl_comm_rebind(fqsx_comm *, fqsx_dna *) { return no_rccl(); }
+int fqsx_rccl_comm_info(fqsx_comm *, uint32_t *) { return no_rccl(); }
+void fqsx_rccl_comm_destroy(fqsx_comm *) {}
+#endif
 
 int fqsx_dna_stats(fqsx_dna *c, uint64_t out[64]) {
   if (!c || !out) return FQSX_E_ARG;
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   LAUNCH(c, 2, k_gather_stats, 1, 64, c->cfg, c->d_lens + c->T);
   return d2h_sync(c, out, c->d_lens + c->T, 64 * sizeof(u64));
 }
 
 int fqsx_dna_capacity(fqsx_dna *c, uint64_t out[16]) {
   if (!c || !out) return FQSX_E_ARG;
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(c->device));
-#endif
+  DEVCHK(dev_enter(c));
   const u32 T = c->T;
   std::vector<u32> f(T);
   int rc;
@@ -2684,12 +2317,8 @@ FQ_KERNEL64 void k_qual_encode(QualCfg cfg, u32 n_reads) {
 }
 FQ_KERNEL void k_qual_rehash(const u64 *o, u64 ocap_mask, u64 *n, u64 ncap_mask, u32 T, u32 slot_u64) {
   const u64 ocap = ocap_mask + 1, total = ocap * T;
-#ifndef FQSX_EMU
-  const u64 gstride = (u64)gridDim.x * blockDim.x;
-  for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gstride) {
-#else
-  for (u64 g = 0; g < total; ++g) {
-#endif
+  const u64 gstride = FQ_GRID_STRIDE(u64);
+  for (u64 g = FQ_GRID_FIRST(u64); g < total; g += gstride) {
     const u64 *src = o + g * slot_u64;
     const u64 key = src[0];
     if (key == ~0ull) continue;
@@ -2707,14 +2336,14 @@ FQ_KERNEL void k_qual_rehash(const u64 *o, u64 ocap_mask, u64 *n, u64 ncap_mask,
   }
 }
 
-struct fqsx_qual {
+struct fqsx_qual : DevCtx {
   QualCfg cfg;
   u32 T;
-  int device;
   u64 cap, out_cap, q_cap, off_cap;
   u8 *d_q;
   u64 *d_off;
-  fqsx_dna mem;   // allocation bookkeeping / stream (reuses the helpers above)
+  u8 *d_compact;   // the T streams back to back (collect_streams)
+  u64 compact_cap;
   std::vector<u32> h_filled;
   std::vector<u64> h_lens;
   std::vector<u8> h_out;
@@ -2726,29 +2355,18 @@ extern "C" {
 // fqsx_dna_set_profiling / fqsx_dna_kernel_times); out[0] = accumulated milliseconds, out[1] = launches
 int fqsx_qual_set_profiling(fqsx_qual *q, int enable) {
   if (!q) return FQSX_E_ARG;
-  q->mem.profiling = enable != 0;
+  q->profiling = enable != 0;
   return FQSX_OK;
 }
 int fqsx_qual_kernel_times(fqsx_qual *q, double out[2]) {
   if (!q || !out) return FQSX_E_ARG;
-  out[0] = q->mem.k_ms[0];
-  out[1] = (double)q->mem.k_n[0];
+  out[0] = q->k_ms[0];
+  out[1] = (double)q->k_n[0];
   return FQSX_OK;
 }
 void fqsx_qual_destroy(fqsx_qual *q) {
   if (!q) return;
-  fqsx_dna *c = &q->mem;
-#ifndef FQSX_EMU
-  (void)hipSetDevice(q->device);
-  (void)hipStreamSynchronize(c->stream);
-#endif
-  std::vector<void *> a = c->allocs;
-  for (void *p : a) dfree(c, p);
-#ifndef FQSX_EMU
-  (void)hipEventDestroy(c->ev0);
-  (void)hipEventDestroy(c->ev1);
-  (void)hipStreamDestroy(c->stream);
-#endif
+  dev_close(q);
   delete q;
 }
 
@@ -2757,22 +2375,13 @@ int fqsx_qual_create(const uint8_t *h, int device, fqsx_qual **out) {
     g_err = "malformed header or quality_mode none";
     return FQSX_E_ARG;
   }
-#ifndef FQSX_EMU
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (libfqsx has no CPU path)"; return FQSX_E_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_err = "bad device ordinal"; return FQSX_E_ARG; }
-  HIPCHK(hipSetDevice(device));
-#endif
   fqsx_qual *q = new fqsx_qual();
+  int rc = dev_open(q, device);
+  if (rc) {
+    delete q;
+    return rc;
+  }
   q->T = h[4];
-  q->device = device;
-  fqsx_dna *c = &q->mem;
-  c->T = q->T; c->device = device; c->profiling = false;
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamCreate(&c->stream));
-  HIPCHK(hipEventCreate(&c->ev0));
-  HIPCHK(hipEventCreate(&c->ev1));
-#endif
   QualCfg &cfg = q->cfg;
   memset(&cfg, 0, sizeof(cfg));
   cfg.T = q->T;
@@ -2787,22 +2396,15 @@ int fqsx_qual_create(const uint8_t *h, int device, fqsx_qual **out) {
   cfg.ctx_mask = (1ull << (cfg.bits * cfg.nctx)) - 1ull;
   cfg.slot_u64 = 1 + (cfg.n_sym + 1 + 3) / 4;
   q->cap = 1u << 12;
-  q->out_cap = q->q_cap = q->off_cap = 0;
-  q->d_q = nullptr; q->d_off = nullptr;
-  int rc;
   void *p = nullptr;
   auto fail = [&](int r) { fqsx_qual_destroy(q); return r; };
-  if ((rc = dalloc(c, &p, q->cap * q->T * cfg.slot_u64 * sizeof(u64), false))) return fail(rc);
+  if ((rc = dalloc(q, &p, q->cap * q->T * cfg.slot_u64 * sizeof(u64), false))) return fail(rc);
   cfg.tab = (u64 *)p;
-#ifndef FQSX_EMU
-  HIPCHK(hipMemsetAsync(cfg.tab, 0xff, q->cap * q->T * cfg.slot_u64 * sizeof(u64), c->stream));
-#else
-  memset(cfg.tab, 0xff, q->cap * q->T * cfg.slot_u64 * sizeof(u64));
-#endif
+  if ((rc = dfill_ff(q, cfg.tab, q->cap * q->T * cfg.slot_u64 * sizeof(u64)))) return fail(rc);
   cfg.cap_mask = q->cap - 1;
-  if ((rc = dalloc(c, &p, q->T * sizeof(u32), true))) return fail(rc);
+  if ((rc = dalloc(q, &p, q->T * sizeof(u32), true))) return fail(rc);
   cfg.filled = (u32 *)p;
-  if ((rc = dalloc(c, &p, (q->T + 2) * sizeof(u64), true))) return fail(rc);   // lengths and, behind them, the error word: one transfer
+  if ((rc = dalloc(q, &p, (q->T + 2) * sizeof(u64), true))) return fail(rc);   // lengths and, behind them, the error word: one transfer
   cfg.lens = (u64 *)p;
   cfg.err = (u32 *)(cfg.lens + q->T);
   q->h_filled.assign(q->T, 0);
@@ -2826,12 +2428,10 @@ int fqsx_qual_encode_block_dev(fqsx_qual *q, const uint8_t *d_quals, const uint6
 // quals (host) or d_quals / d_off_in (already in device memory); off = host copy of the offsets
 static int qual_encode_impl(fqsx_qual *q, const uint8_t *quals, const uint8_t *d_quals, const uint64_t *d_off_in, const uint64_t *off,
                             uint32_t n_reads, const uint8_t **streams, uint64_t *lens) {
-  fqsx_dna *c = &q->mem;
+  DevCtx *c = q;
   QualCfg &cfg = q->cfg;
   const u32 T = q->T;
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(q->device));
-#endif
+  DEVCHK(dev_enter(c));
   int rc;
   void *p = nullptr;
   u64 max_w = 0;
@@ -2848,15 +2448,9 @@ static int qual_encode_impl(fqsx_qual *q, const uint8_t *quals, const uint8_t *d
   if (need * 2 > q->cap) {
     const u64 ncap = pow2_at_least(need * 2);
     if ((rc = dalloc(c, &p, ncap * T * cfg.slot_u64 * sizeof(u64), false))) return rc;
-#ifndef FQSX_EMU
-    HIPCHK(hipMemsetAsync(p, 0xff, ncap * T * cfg.slot_u64 * sizeof(u64), c->stream));
-#else
-    memset(p, 0xff, ncap * T * cfg.slot_u64 * sizeof(u64));
-#endif
+    if ((rc = dfill_ff(c, p, ncap * T * cfg.slot_u64 * sizeof(u64)))) return rc;
     LAUNCH(c, 2, k_qual_rehash, REHASH_GRID, 256, (const u64 *)cfg.tab, cfg.cap_mask, (u64 *)p, ncap - 1, T, cfg.slot_u64);
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
     dfree(c, cfg.tab);
     cfg.tab = (u64 *)p;
     cfg.cap_mask = ncap - 1;
@@ -2885,7 +2479,7 @@ static int qual_encode_impl(fqsx_qual *q, const uint8_t *quals, const uint8_t *d
   if (err) { g_err = "device error " + std::to_string(err) + " in the quality kernel"; return FQSX_E_DEVICE; }
   for (u32 t = 0; t < T; ++t)
     if (q->h_lens[t] > cfg.out_cap) { g_err = "quality stream overflow"; return FQSX_E_DEVICE; }
-  return collect_streams(c, T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
+  return collect_streams(c, q->d_compact, q->compact_cap, T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
 }
 
 }  // extern "C"
@@ -2910,14 +2504,14 @@ FQ_KERNEL64 void k_id_init_fixed(IdCfg cfg) {
   }
 }
 
-struct fqsx_idg {
+struct fqsx_idg : DevCtx {
   IdCfg cfg;
   u32 T;
-  int device;
   u64 small_cap, big_cap, out_cap, ids_cap, off_cap;
   u8 *d_ids;
   u64 *d_off;
-  fqsx_dna mem;   // allocation bookkeeping / stream (reuses the helpers above)
+  u8 *d_compact;   // the T streams back to back (collect_streams)
+  u64 compact_cap;
   std::vector<u32> h_state;
   std::vector<u64> h_lens;
   std::vector<u8> h_out;
@@ -2927,66 +2521,34 @@ extern "C" {
 
 void fqsx_idg_destroy(fqsx_idg *q) {
   if (!q) return;
-  fqsx_dna *c = &q->mem;
-#ifndef FQSX_EMU
-  (void)hipSetDevice(q->device);
-  (void)hipStreamSynchronize(c->stream);
-#endif
-  std::vector<void *> a = c->allocs;
-  for (void *p : a) dfree(c, p);
-#ifndef FQSX_EMU
-  (void)hipEventDestroy(c->ev0);
-  (void)hipEventDestroy(c->ev1);
-  (void)hipStreamDestroy(c->stream);
-#endif
+  dev_close(q);
   delete q;
-}
-
-static int idg_fill_ff(fqsx_dna *c, void *p, u64 bytes) {
-#ifndef FQSX_EMU
-  HIPCHK(hipMemsetAsync(p, 0xff, bytes, c->stream));
-#else
-  (void)c;
-  memset(p, 0xff, bytes);
-#endif
-  return FQSX_OK;
 }
 
 int fqsx_idg_create(const uint8_t *h, int device, fqsx_idg **out) {
   if (!h || !out || memcmp(h, "KCSD", 4) || h[4] == 0 || h[7] > 1) { g_err = "malformed header or id_mode none"; return FQSX_E_ARG; }
-#ifndef FQSX_EMU
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (libfqsx has no CPU path)"; return FQSX_E_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_err = "bad device ordinal"; return FQSX_E_ARG; }
-  HIPCHK(hipSetDevice(device));
-#endif
   fqsx_idg *q = new fqsx_idg();
+  int rc = dev_open(q, device);
+  if (rc) {
+    delete q;
+    return rc;
+  }
   q->T = h[4];
-  q->device = device;
-  fqsx_dna *c = &q->mem;
-  c->T = q->T; c->device = device; c->profiling = false;
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamCreate(&c->stream));
-  HIPCHK(hipEventCreate(&c->ev0));
-  HIPCHK(hipEventCreate(&c->ev1));
-#endif
+  DevCtx *c = q;
   IdCfg &cfg = q->cfg;
   memset(&cfg, 0, sizeof(cfg));
   cfg.T = q->T;
   cfg.mode = h[7];   // 0 lossless, 1 instrument (params.h:18,92)
   q->small_cap = 1u << 10; q->big_cap = 1u << 9;
-  q->out_cap = q->ids_cap = q->off_cap = 0;
-  q->d_ids = nullptr; q->d_off = nullptr;
   const u64 T = q->T;
-  int rc;
   void *p = nullptr;
   auto fail = [&](int r) { fqsx_idg_destroy(q); return r; };
   if ((rc = dalloc(c, &p, q->small_cap * T * 2 * sizeof(u64), false))) return fail(rc);
   cfg.small = (u64 *)p; cfg.small_mask = q->small_cap - 1;
-  if ((rc = idg_fill_ff(c, cfg.small, q->small_cap * T * 2 * sizeof(u64)))) return fail(rc);
+  if ((rc = dfill_ff(c, cfg.small, q->small_cap * T * 2 * sizeof(u64)))) return fail(rc);
   if ((rc = dalloc(c, &p, q->big_cap * T * IDK_BIG_U64 * sizeof(u64), false))) return fail(rc);
   cfg.big = (u64 *)p; cfg.big_mask = q->big_cap - 1;
-  if ((rc = idg_fill_ff(c, cfg.big, q->big_cap * T * IDK_BIG_U64 * sizeof(u64)))) return fail(rc);
+  if ((rc = dfill_ff(c, cfg.big, q->big_cap * T * IDK_BIG_U64 * sizeof(u64)))) return fail(rc);
   if ((rc = dalloc(c, &p, T * IDK_FIXED * IDK_BIG_U64 * sizeof(u64), true))) return fail(rc);
   cfg.fixed = (u64 *)p;
   cfg.mtf_cap = 4096;
@@ -2997,9 +2559,7 @@ int fqsx_idg_create(const uint8_t *h, int device, fqsx_idg **out) {
   cfg.err = (u32 *)(cfg.lens + T);
   cfg.state = (u32 *)(cfg.lens + T + 2);
   LAUNCH(c, 2, k_id_init_fixed, q->T, 64, cfg);
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+  DEVCHK(dev_sync(c));
   q->h_state.assign(4 * T, 0);
   q->h_lens.assign(T + 2 + 2 * T, 0);
   *out = q;
@@ -3012,12 +2572,10 @@ int fqsx_idg_create(const uint8_t *h, int device, fqsx_idg **out) {
 int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, uint32_t n_reads, int paired,
                           const uint8_t **streams, uint64_t *lens) {
   if (!q || !ids || !off || !streams || !lens || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
-  fqsx_dna *c = &q->mem;
+  DevCtx *c = q;
   IdCfg &cfg = q->cfg;
   const u64 T = q->T;
-#ifndef FQSX_EMU
-  HIPCHK(hipSetDevice(q->device));
-#endif
+  DEVCHK(dev_enter(c));
   int rc;
   void *p = nullptr;
   // ---- table sizes: a worker creates at most one big model per byte it codes plus nine per numeric token, and three small
@@ -3042,11 +2600,9 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
     const u64 ncap = pow2_at_least(need * 2);
     int r = dalloc(c, &p, ncap * T * slot_u64 * sizeof(u64), false);
     if (r) return r;
-    if ((r = idg_fill_ff(c, p, ncap * T * slot_u64 * sizeof(u64)))) return r;
+    if ((r = dfill_ff(c, p, ncap * T * slot_u64 * sizeof(u64)))) return r;
     LAUNCH(c, 2, k_qual_rehash, REHASH_GRID, 256, (const u64 *)tab, mask, (u64 *)p, ncap - 1, (u32)T, slot_u64);
-#ifndef FQSX_EMU
-    HIPCHK(hipStreamSynchronize(c->stream));
-#endif
+    DEVCHK(dev_sync(c));
     dfree(c, tab);
     tab = (u64 *)p; cap = ncap; mask = ncap - 1;
     return FQSX_OK;
@@ -3077,7 +2633,7 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
   }
   for (u64 t = 0; t < T; ++t)
     if (q->h_lens[t] > cfg.out_cap) { g_err = "id stream overflow"; return FQSX_E_DEVICE; }
-  return collect_streams(c, (u32)T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
+  return collect_streams(c, q->d_compact, q->compact_cap, (u32)T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
 }
 
 }  // extern "C"
@@ -3106,7 +2662,7 @@ FQ_KERNEL64 void k_sort_scatter(SortCfg c) {
 FQ_KERNEL64 void k_sort_flags(SortCfg c) { sort_flags_body(c, FQ_BLOCK); }
 FQ_KERNEL64 void k_sort_rank(SortCfg c) { sort_rank_body(c); }
 
-static int sort_rank_impl(fqsx_dna *c, const u8 *bases, const u64 *off, u32 n, std::vector<u32> &rank, u32 *passes_out) {
+static int sort_rank_impl(DevCtx *c, const u8 *bases, const u64 *off, u32 n, std::vector<u32> &rank, u32 *passes_out) {
   int rc;
   void *p = nullptr;
   SortCfg s;
@@ -3182,12 +2738,10 @@ extern "C" int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *rea
   for (u32 b = 0; b <= 256; ++b) bin_start[b] = 0;
   if (n_batches_out) *n_batches_out = 0;
   if (n_reads == 0) return FQSX_OK;
-#ifndef FQSX_EMU
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device available (libfqsx has no CPU path)"; return FQSX_E_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_err = "bad device ordinal"; return FQSX_E_ARG; }
-  HIPCHK(hipSetDevice(device));
-#endif
+  DevCtx dev;   // (every batch hands its allocations back before the next one)
+  DevCtx *c = &dev;
+  int rc = dev_open(c, device);
+  if (rc) return rc;
   // bins in input order (preprocess_se, application.cpp:383-391: a position past the read counts as code 3 there
   // because it lands on the line feed)
   auto nt = [](u8 ch) -> u32 { return ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : 3u; };
@@ -3206,13 +2760,6 @@ extern "C" int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *rea
   std::vector<u32> cur(bin_start, bin_start + 256);
   std::vector<u32> member(n_reads);   // reads grouped by bin, input order inside a bin
   for (u32 r = 0; r < n_reads; ++r) member[cur[bin[r]]++] = r;
-  fqsx_dna mem{};
-  fqsx_dna *c = &mem;
-  c->T = 1; c->device = device; c->profiling = false;
-#ifndef FQSX_EMU
-  HIPCHK(hipStreamCreate(&c->stream));
-#endif
-  int rc = FQSX_OK;
   u32 n_batches = 0;
   std::vector<u8> gb;
   std::vector<u64> go;
@@ -3242,11 +2789,8 @@ extern "C" int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *rea
         pb = gb.data(); po = go.data();
       }
       rc = sort_rank_impl(c, pb, po, n, rank, nullptr);
-#ifndef FQSX_EMU
-      (void)hipStreamSynchronize(c->stream);
-#endif
-      std::vector<void *> a = c->allocs;
-      for (void *p : a) dfree(c, p);
+      dev_drain(c);
+      dfree_all(c);
       if (rc) break;
       // libstdc++'s std::sort per bin on the ranks (ranks of one batch are comparable; a bin never spans batches)
       v.resize(n);
@@ -3259,9 +2803,7 @@ extern "C" int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *rea
     }
     b0 = b1;
   }
-#ifndef FQSX_EMU
-  (void)hipStreamDestroy(c->stream);
-#endif
+  dev_close(c);
   if (n_batches_out) *n_batches_out = n_batches;
   return rc;
 }

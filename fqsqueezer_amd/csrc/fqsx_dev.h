@@ -296,12 +296,6 @@ FQ_DEV u32 dna_code(u8 c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u
 
 FQ_DEV void c4_zero(C4 &c) { c.c[0] = c.c[1] = c.c[2] = c.c[3] = 0; }
 FQ_DEV bool c4_any(const C4 &c) { return (c.c[0] | c.c[1] | c.c[2] | c.c[3]) != 0; }
-FQ_DEV void c4_add(C4 &c, u32 sym, u32 v) {
-  c.c[0] += sym == 0 ? v : 0;
-  c.c[1] += sym == 1 ? v : 0;
-  c.c[2] += sym == 2 ? v : 0;
-  c.c[3] += sym == 3 ? v : 0;
-}
 FQ_DEV u32 c4_get(const C4 &c, u32 i) { return i == 0 ? c.c[0] : i == 1 ? c.c[1] : i == 2 ? c.c[2] : c.c[3]; }
 FQ_DEV u64 sl_get(const u64 *s, u32 i) { return i == 0 ? s[0] : i == 1 ? s[1] : i == 2 ? s[2] : s[3]; }
 
@@ -738,24 +732,6 @@ FQ_DEV u32 tab_count(const KTab &t, u32 sub, u64 kmer_norm, u64 &nslots) {
   const TabLoc L = tab_locate(t, t.slots + (u64)sub * t.stride, kmer_norm >> (64 - 2 * t.k));
   nslots += L.ns;
   return (u32)(L.item & ((1ull << t.cbits) - 1ull));
-}
-// wave-uniform insert used for the worker-private local tables (insert(), ht_kmer.h:420-438)
-FQ_DEV void tab_insert_uniform(Wk &w, const KTab &t, u32 sub, u64 kmer_norm, u32 rng, const Cinc &ci) {
-  u64 *s = t.slots + (u64)sub * t.stride;
-  const u64 v = kmer_norm >> (64 - 2 * t.k);
-  const u64 cm = (1ull << t.cbits) - 1ull;
-  const TabLoc L = tab_locate(t, s, v);
-  const u64 p = L.pos, it = L.item;
-  if (p == ~0ull) { w.err = FQSX_ERR_LTAB_FULL; return; }
-  if (!it) {
-    const u32 f = t.filled[sub];
-    if ((u64)f * 10 >= t.nb * FQSX_BKT * 9) { w.err = FQSX_ERR_LTAB_FULL; return; }
-    s[p] = (v << t.cbits) | 1ull;  // Increment(0) == 1
-    t.filled[sub] = f + 1;
-    return;
-  }
-  const u32 cnt = (u32)(it & cm);
-  if (cnt < (u32)cm && cinc_inc1(w.sm, rng, ci, cnt) != cnt) s[p] = it + 1;
 }
 
 // probe the first n entries of the LDS batch (keys/orientations) lane-parallel
@@ -3277,7 +3253,7 @@ FQ_DEV void scout_release(Wk &w) {
 // i0 == pmer, from the head of that read (the resolving wave has finished the read before on its own)
 // The chunks of the new epoch take the ring slots in turn starting after the slot of the chunk the resolving wave holds
 // (w.sb), so with `hold` the request can go out while that chunk is still being read: the slot counts as an unreleased
-// chunk (sc_taken = -1) until scout_unhold.
+// chunk (sc_taken = -1) until the resolving wave next publishes its sc_taken.  (Every caller passes hold = false.)
 FQ_DEV void scout_restart(Wk &w, u32 read, u32 i0, const u64 s_let[4], u32 flags, bool hold) {
   WgShared *sm = w.sm;
   if (lds_load_acq(&sm->sc_dead)) return;
@@ -3300,10 +3276,6 @@ FQ_DEV void scout_restart(Wk &w, u32 read, u32 i0, const u64 s_let[4], u32 flags
   lds_store_rel(&sm->sc_taken, hold ? 0xffffffffu : 0u);
   w.sc_epoch += 1;
   lds_store_rel(&sm->sc_req_seq, w.sc_epoch);
-}
-FQ_DEV void scout_unhold(Wk &w) {   // the chunk held across an early restart is done with
-  FQ_SYNC();
-  lds_store_rel(&w.sm->sc_taken, w.sc_taken);
 }
 // The scouts' chunk that covers position `at` of the current read / request becomes w.sb; chunks that lie wholly before
 // it (inside a window the resolving wave has just covered itself) are released on the way.  False: go on without them.

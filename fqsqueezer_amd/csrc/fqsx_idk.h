@@ -64,14 +64,6 @@ struct IdK {
   u32 err;
 };
 
-FQ_DEV u32 idk_uniform32(u32 v) {   // (value computed alike in every lane: tell the compiler)
-#if FQ_WAVE > 1
-  return (u32)__builtin_amdgcn_readfirstlane((int)v);
-#else
-  return v;
-#endif
-}
-
 // ---- models -----------------------------------------------------------------------------------------------------------
 // 2- / 4-symbol model of `map` at context `ctx` (created all ones on first use, rc.h:69-74): encode symbol x
 FQ_DEV void idk_small(IdK &k, u32 map, u64 ctx, u32 N, u32 x) {

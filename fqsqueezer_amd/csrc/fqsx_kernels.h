@@ -14,4 +14,8 @@ int fqsx_launch_decode(hipStream_t s, const EncArgs &a);      // all modes
 static void fqsx_emu_encode_se(const EncArgs &a);
 static void fqsx_emu_encode_pe(const EncArgs &a);
 static void fqsx_emu_decode(const EncArgs &a);
+// (the launchers of the emulation: the kernel runs to its end on the calling thread; there is no stream)
+static int fqsx_launch_encode_se(void *, const EncArgs &a) { fqsx_emu_encode_se(a); return 0; }
+static int fqsx_launch_encode_pe(void *, const EncArgs &a) { fqsx_emu_encode_pe(a); return 0; }
+static int fqsx_launch_decode(void *, const EncArgs &a) { fqsx_emu_decode(a); return 0; }
 #endif

@@ -29,6 +29,7 @@ typedef int32_t i32;
 #define FQ_ROLE static __device__ __noinline__
 #define FQ_KERNEL extern "C" __global__
 #define FQ_KERNEL64 extern "C" __global__ __launch_bounds__(64)
+#define FQ_KERNEL128 extern "C" __global__ __launch_bounds__(128)
 #define FQ_KERNEL320 extern "C" __global__ __launch_bounds__(320)
 #define FQ_KERNEL192 extern "C" __global__ __launch_bounds__(192)
 #define FQ_KERNEL512 extern "C" __global__ __launch_bounds__(512)
@@ -36,6 +37,11 @@ typedef int32_t i32;
 #define FQ_LANE ((u32)(threadIdx.x & 63u))
 #define FQ_BLOCK ((u32)blockIdx.x)
 #define FQ_NBLOCKS ((u32)gridDim.x)
+// Grid-stride loops over n items, index type I: for (I i = FQ_GRID_FIRST(I); i < n; i += stride), stride = FQ_GRID_STRIDE(I).
+// FQ_GRID(g): the grid such a kernel is launched with (g here; 1 in the emulation, whose one block walks every item in order).
+#define FQ_GRID_FIRST(I) ((I)blockIdx.x * blockDim.x + threadIdx.x)
+#define FQ_GRID_STRIDE(I) ((I)gridDim.x * blockDim.x)
+#define FQ_GRID(g) (g)
 #define FQ_SHARED __shared__
 // Cross-lane hand-off through LDS inside the single wavefront of a workgroup: the LDS queue of one
 // wave is in order, so draining it (and stopping compiler reordering) is all that is needed.  This
@@ -103,7 +109,6 @@ FQ_DEV u32 wave_excl_scan32(u32 v) {
 FQ_DEV void lds_inc32(u32 *p) { atomicAdd(p, 1u); }
 FQ_DEV void lds_or64(u64 *p, u64 v) { atomicOr((unsigned long long *)p, (unsigned long long)v); }
 FQ_DEV bool wave_any(bool p) { return __ballot(p) != 0ull; }
-FQ_DEV bool wave_all(bool p) { return __ballot(p) == __ballot(true); }
 FQ_DEV u64 wave_ballot(bool p) { return __ballot(p); }
 FQ_DEV u32 wave_bcast32(u32 v, u32 lane) { return __shfl(v, (int)lane, 64); }
 FQ_DEV u64 wave_bcast64(u64 v, u32 lane) { return __shfl(v, (int)lane, 64); }
@@ -120,6 +125,13 @@ FQ_DEV u64 wave_min64(u64 v) {
   for (int o = 32; o > 0; o >>= 1) {
     const u64 y = __shfl_xor(v, o, 64);
     v = y < v ? y : v;
+  }
+  return v;
+}
+FQ_DEV u64 wave_max64(u64 v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const u64 y = __shfl_xor(v, o, 64);
+    v = y > v ? y : v;
   }
   return v;
 }
@@ -141,6 +153,7 @@ FQ_DEV double ema_update(double avg, double level) { return __dadd_rn(__dmul_rn(
 #define FQ_ROLE static
 #define FQ_KERNEL static
 #define FQ_KERNEL64 static
+#define FQ_KERNEL128 static
 #define FQ_KERNEL320 static
 #define FQ_KERNEL192 static
 #define FQ_KERNEL512 static
@@ -148,6 +161,9 @@ FQ_DEV double ema_update(double avg, double level) { return __dadd_rn(__dmul_rn(
 #define FQ_LANE 0u
 #define FQ_BLOCK (fq_emu_block)
 #define FQ_NBLOCKS (fq_emu_nblocks)
+#define FQ_GRID_FIRST(I) ((I)0)
+#define FQ_GRID_STRIDE(I) ((I)1)
+#define FQ_GRID(g) 1u
 #define FQ_SHARED static thread_local
 #define FQ_SYNC() ((void)0)
 #define FQ_SYNC_MEM() ((void)0)
@@ -168,7 +184,6 @@ FQ_DEV u32 wave_excl_scan32(u32) { return 0; }
 FQ_DEV void lds_inc32(u32 *p) { ++*p; }
 FQ_DEV void lds_or64(u64 *p, u64 v) { *p |= v; }
 FQ_DEV bool wave_any(bool p) { return p; }
-FQ_DEV bool wave_all(bool p) { return p; }
 FQ_DEV u64 wave_ballot(bool p) { return p ? 1ull : 0ull; }
 FQ_DEV u32 wave_bcast32(u32 v, u32) { return v; }
 FQ_DEV u64 wave_bcast64(u64 v, u32) { return v; }
@@ -176,6 +191,7 @@ FQ_DEV u32 uniform32(u32 v) { return v; }
 FQ_DEV u64 uniform64(u64 v) { return v; }
 FQ_DEV u64 touch_load(const u64 *p) { return *p; }
 FQ_DEV void keep_live(u64) {}
+FQ_DEV u64 wave_max64(u64 v) { return v; }
 FQ_DEV u32 popc64(u64 v) { return (u32)__builtin_popcountll(v); }
 FQ_DEV u32 ctz64(u64 v) { return (u32)__builtin_ctzll(v); }
 FQ_DEV u64 fq_clock() { return 0; }
