@@ -18,6 +18,12 @@ bases / wall time.  The file is configs[3]-shaped (150 bp SE sorted at the refer
 other multi-GPU mode instead (N independent files, one per GPU, no collective: weak scaling); its rate also rides along in
 the sharded line as `replicas`.
 
+A plain run does only what the headline figure needs: input set-up, the warm-up and timed steps, --dump-outputs, the line.
+`--full` adds everything else, each in runs of its own after the timed steps: the kernel-level pass behind `roofline` (one GPU
+and sharded), and on one GPU the PCIe-inclusive pass, T = 255, concurrent files, the other rows, the large file and the
+reference CPU baseline (each of these still switched off by its own option: --no-pcie, --concurrent 0, ...).  Without --full
+those fields of the line are null.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -93,13 +99,16 @@ def main() -> None:
     ap.add_argument("--genome", type=int, default=None, help="default: 7.5 Mbp (one GPU / replicas), 50 Mbp (sharded)")
     ap.add_argument("--gs", type=int, default=None, help="default: 8 (one GPU / replicas), 3100 = the reference's default geometry (sharded)")
     ap.add_argument("--threads", type=int, default=64, help="logical workers T (header byte, <=255)")
-    ap.add_argument("--cpu-sample-reads", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the extra host-buffer (PCIe-inclusive) pass")
-    ap.add_argument("--no-t255", action="store_true", help="skip the extra pass with 255 workers")
-    ap.add_argument("--concurrent", type=int, default=4, help="extra pass: this many codec instances at once (0/1 = skip)")
-    ap.add_argument("--no-rows", action="store_true", help="skip the extra passes over the other rows (decoder, quality, PE, original order)")
-    ap.add_argument("--no-large", action="store_true", help="skip the extra pass over the large file (10 M x 150 bp, G = 300 Mbp, -gs 300: tables of GBs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the extra passes: kernel-level (roofline), PCIe-inclusive, T = 255, concurrent files, "
+                         "other rows, large file, reference CPU baseline (the options below switch single ones off)")
+    ap.add_argument("--cpu-sample-reads", type=int, default=1_000_000, help="--full: reads in the CPU baseline's sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the reference CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the extra host-buffer (PCIe-inclusive) pass")
+    ap.add_argument("--no-t255", action="store_true", help="--full: skip the extra pass with 255 workers")
+    ap.add_argument("--concurrent", type=int, default=4, help="--full: extra pass with this many codec instances at once (0/1 = skip)")
+    ap.add_argument("--no-rows", action="store_true", help="--full: skip the extra passes over the other rows (decoder, quality, PE, original order)")
+    ap.add_argument("--no-large", action="store_true", help="--full: skip the extra pass over the large file (10 M x 150 bp, G = 300 Mbp, -gs 300: tables of GBs)")
     ap.add_argument("--chunked-tables", action="store_true",
                     help="the capacity mode (fqsx_dna_use_chunked_tables): k-mer tables in per-sub-table chunks, growth without old + new side by side")
     ap.add_argument("--partition", action="store_true",
@@ -162,7 +171,7 @@ def main() -> None:
     # ---- synthetic input, host preparation (not timed): binning + sort + block formation
     seed = 2 + rank
     reads = synth_reads(a.reads, a.len, a.genome, seed)
-    rec = hp.Records([read_id(i) for i in range(a.reads)], reads, reads if a.no_cpu_baseline else synth_quals(a.reads, a.len, seed))   # (qualities: only the reference CPU leg reads them)
+    rec = hp.Records([read_id(i) for i in range(a.reads)], reads, reads if a.no_cpu_baseline or not a.full else synth_quals(a.reads, a.len, seed))   # (qualities: only the reference CPU leg reads them)
     header = hp.make_header(a.threads, "se_sorted", a.gs)
     groups = None
     if a.reads > 2_000_000:   # large files: the sorted order from the GPU pre-pass (fqsx_sort_order) instead of numpy's lexsort
@@ -243,38 +252,53 @@ def main() -> None:
 
     cap_line = dict(capacity, note="k-mer tables at the end of the file: distinct s-/b-mers stored, slots allocated (8-byte slots, all owners), "
                                    "device bytes held / peak (old + new table alive during a growth), growth events")
-    # ---- kernel-level measurement pass (HIP events around every launch on the codec's stream; untimed)
-    _, st, kt = one_step(profile=True)
-    alg = algorithmic_bytes(st)
-    enc_s, ins_s = kt["encode_ms"] / 1e3, kt["insert_ms"] / 1e3
-    dominant = "k_encode_se_sorted" if enc_s >= ins_s else "k_insert_phase"
-    dom_s = max(enc_s, ins_s)
-    dom_launches = kt["encode_launches"] if enc_s >= ins_s else kt["insert_launches"]
-    # bytes attributable to the dominant kernel
-    ins_bytes = insert_bytes(st)
-    dom_bytes = alg - ins_bytes if dominant == "k_encode_se_sorted" else ins_bytes
-    r03_bytes = algorithmic_bytes(st, R03_SLOTS_PER_PROBE, R03_SLOTS_PER_INSERT) - insert_bytes(st, R03_SLOTS_PER_INSERT)   # (encode kernel, rounds 1-3's slot counts)
-    achieved = dom_bytes / dom_s / 1e9 if dom_s > 0 else 0.0
-    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
-                "frac": round(achieved / 8000.0, 6), "traffic": None, "kernel": dominant,
-                "launches": dom_launches, "avg_launch_ms": round(dom_s * 1e3 / max(1, dom_launches), 4),
-                "algorithmic_bytes_per_launch": round(dom_bytes / max(1, dom_launches), 1),
-                "encode_kernel_s": round(enc_s, 4), "insert_kernel_s": round(ins_s, 4),
-                "bytes_the_kernel_reads": {"achieved": round((dom_bytes - 8.0 * st.get("siv_saved", 0)) / dom_s / 1e9, 3), "unit": "GB/s",
-                                           "frac": round((dom_bytes - 8.0 * st.get("siv_saved", 0)) / dom_s / 1e9 / 8000.0, 6),
-                                           "per_launch": round((dom_bytes - 8.0 * st.get("siv_saved", 0)) / max(1, dom_launches), 1),
-                                           "note": "the same formula without the p-mer-vector words the count index spares the kernel (siv_saved): what the kernel asks the "
-                                                   "memory system for; `achieved` / `frac` above follow SURVEY 8d literally (the words the ALGORITHM sweeps)"},
-                "with_round_3_slot_counts": {"frac": round(r03_bytes / max(enc_s, 1e-9) / 1e9 / 8000.0, 6), "per_launch": round(r03_bytes / max(1, kt["encode_launches"]), 1),
-                                             "note": "encode kernel; 1.8 slots per probe as this library's linear tables scanned in round 3 (that round's line: 0.006872), for "
-                                                     "comparison across rounds; `achieved` / `frac` use the reference's 3.96 slots per probe (SURVEY 8d's 39.8 B per probe)"},
-                "probes_per_s": round((st["gprobe"] + st["lprobe"]) / max(enc_s, 1e-9), 1),
-                "siv_words_per_base": {"algorithm": round((st["siv_words"] + st.get("siv_saved", 0)) / max(1, st["bases"]), 2),
-                                       "read_by_the_kernels": round(st["siv_words"] / max(1, st["bases"]), 2)}}
+    # ---- --full: kernel-level measurement pass (HIP events around every launch on the codec's stream; untimed)
+    roofline = None
+    if a.full:
+        _, st, kt = one_step(profile=True)
+        alg = algorithmic_bytes(st)
+        enc_s, ins_s = kt["encode_ms"] / 1e3, kt["insert_ms"] / 1e3
+        dominant = "k_encode_se_sorted" if enc_s >= ins_s else "k_insert_phase"
+        dom_s = max(enc_s, ins_s)
+        dom_launches = kt["encode_launches"] if enc_s >= ins_s else kt["insert_launches"]
+        # bytes attributable to the dominant kernel
+        ins_bytes = insert_bytes(st)
+        dom_bytes = alg - ins_bytes if dominant == "k_encode_se_sorted" else ins_bytes
+        r03_bytes = algorithmic_bytes(st, R03_SLOTS_PER_PROBE, R03_SLOTS_PER_INSERT) - insert_bytes(st, R03_SLOTS_PER_INSERT)   # (encode kernel, rounds 1-3's slot counts)
+        achieved = dom_bytes / dom_s / 1e9 if dom_s > 0 else 0.0
+        roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
+                    "frac": round(achieved / 8000.0, 6), "traffic": None, "kernel": dominant,
+                    "launches": dom_launches, "avg_launch_ms": round(dom_s * 1e3 / max(1, dom_launches), 4),
+                    "algorithmic_bytes_per_launch": round(dom_bytes / max(1, dom_launches), 1),
+                    "encode_kernel_s": round(enc_s, 4), "insert_kernel_s": round(ins_s, 4),
+                    "bytes_the_kernel_reads": {"achieved": round((dom_bytes - 8.0 * st.get("siv_saved", 0)) / dom_s / 1e9, 3), "unit": "GB/s",
+                                               "frac": round((dom_bytes - 8.0 * st.get("siv_saved", 0)) / dom_s / 1e9 / 8000.0, 6),
+                                               "per_launch": round((dom_bytes - 8.0 * st.get("siv_saved", 0)) / max(1, dom_launches), 1),
+                                               "note": "the same formula without the p-mer-vector words the count index spares the kernel (siv_saved): what the kernel asks the "
+                                                       "memory system for; `achieved` / `frac` above follow SURVEY 8d literally (the words the ALGORITHM sweeps)"},
+                    "with_round_3_slot_counts": {"frac": round(r03_bytes / max(enc_s, 1e-9) / 1e9 / 8000.0, 6), "per_launch": round(r03_bytes / max(1, kt["encode_launches"]), 1),
+                                                 "note": "encode kernel; 1.8 slots per probe as this library's linear tables scanned in round 3 (that round's line: 0.006872), for "
+                                                         "comparison across rounds; `achieved` / `frac` use the reference's 3.96 slots per probe (SURVEY 8d's 39.8 B per probe)"},
+                    "probes_per_s": round((st["gprobe"] + st["lprobe"]) / max(enc_s, 1e-9), 1),
+                    "siv_words_per_base": {"algorithm": round((st["siv_words"] + st.get("siv_saved", 0)) / max(1, st["bases"]), 2),
+                                           "read_by_the_kernels": round(st["siv_words"] / max(1, st["bases"]), 2)}}
+        # HBM traffic of the dominant kernel from a separate rocprofv3 --pmc pass (profiles/traffic.json), if recorded
+        traffic = None
+        tf = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tf):
+            try:
+                tj = json.load(open(tf))
+                if tj.get("workers_T") == a.threads and tj.get("reads") == a.reads and tj.get("len") == a.len:
+                    traffic = tj.get("bytes_per_launch")
+                    roofline["traffic_source"] = ("profiles/traffic.json: separate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of this "
+                                                  "workload on the build named there (" + str(tj.get("build", "?"))[:60] + "); NOT measured by this run")
+            except Exception:
+                traffic = None
+        roofline["traffic"] = traffic
 
     # ---- PCIe-inclusive rate: the same pass through the host-buffer entry point (H2D copy per block; untimed run)
     pcie = None
-    if world == 1 and not a.no_pcie:
+    if a.full and world == 1 and not a.no_pcie:
         host_blocks = [hp.block_arrays(rec, idx) for idx in blocks]
         codec = DnaCodec(header, device=local_rank)
         t1 = time.perf_counter()
@@ -285,7 +309,7 @@ def main() -> None:
 
     # the same file at the bitstream's maximum worker count (T = 255; reference CLI caps -t at 64): extra, untimed-region info
     t255 = None
-    if world == 1 and not a.no_t255 and a.threads != 255:
+    if a.full and world == 1 and not a.no_t255 and a.threads != 255:
         h255 = hp.make_header(255, "se_sorted", a.gs)
         codec = DnaCodec(h255, device=local_rank)
         t1 = time.perf_counter()
@@ -300,7 +324,7 @@ def main() -> None:
     # K independent codec instances at once on this GPU (own tables, own stream, one host thread each): one file with
     # T = 64 occupies 64 of the 256 CUs, so a GPU has room for several files.  Extra information, not `value`.
     conc = None
-    if world == 1 and a.concurrent > 1:
+    if a.full and world == 1 and a.concurrent > 1:
         import threading
 
         def conc_pass(partitioned):
@@ -354,23 +378,9 @@ def main() -> None:
                         "its own partition of the compute units (fqsx_dna_create_on_partition: CU-masked stream; one file occupies T of the 256 CUs); "
                         "`unpartitioned` = the same with plain streams (the files' kernels queue behind each other for CUs); aggregate rates"}
 
-    # HBM traffic of the dominant kernel from a separate rocprofv3 --pmc pass (profiles/traffic.json), if recorded
-    traffic = None
-    tf = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tf):
-        try:
-            tj = json.load(open(tf))
-            if tj.get("workers_T") == a.threads and tj.get("reads") == a.reads and tj.get("len") == a.len:
-                traffic = tj.get("bytes_per_launch")
-                roofline["traffic_source"] = ("profiles/traffic.json: separate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of this "
-                                              "workload on the build named there (" + str(tj.get("build", "?"))[:60] + "); NOT measured by this run")
-        except Exception:
-            traffic = None
-    roofline["traffic"] = traffic
-
     # ---- the rows beside the headline path (other dna_modes): 300 k x 150 bp each, extras of the N=1 line
     rows = None
-    if world == 1 and not a.no_rows:
+    if a.full and world == 1 and not a.no_rows:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_rows
         rows = bench_rows.measure(300_000, a.len, a.threads, local_rank)
@@ -395,7 +405,7 @@ def main() -> None:
     # ---- a file whose tables do not fit any cache (the headline file's are 0.5 GB, twice the Infinity Cache): 10 M x 150 bp of a
     # 300 Mbp genome at -gs 300 (k = 12/17/21/26; the configs[3]-shaped c19 file of tests/test_gpu_fullsize.py), one pass, inputs in HBM
     large = None
-    if world == 1 and not a.no_large and a.reads == 1_000_000 and a.threads == 64:
+    if a.full and world == 1 and not a.no_large and a.reads == 1_000_000 and a.threads == 64:
         from fqsqueezer_amd.codec import sort_order
         lr = synth_reads(10_000_000, 150, 300_000_000, 19)
         lrec = hp.Records([b""] * 0, lr, lr)
@@ -426,7 +436,7 @@ def main() -> None:
 
     # ---- CPU baseline on a bounded sample of the same workload (rank 0, N=1 only)
     cpu = None
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(a, hp, reads, rec)
 
     line = {
@@ -522,9 +532,9 @@ def sharded_main(a, rank, local_rank, world, emu_lib=None, replicas=None, emit=T
                                   "ranks_seen": info.get("ranks_seen")})
     value = n_bases * a.steps / elapsed / 1e6
 
-    # ---- kernel-level pass (HIP events around every launch of this rank's stream; untimed): the dominant kernel's roofline on rank 0
+    # ---- --full: kernel-level pass (HIP events around every launch of this rank's stream; untimed): the dominant kernel's roofline on rank 0
     roofline = None
-    if gpu:
+    if gpu and a.full:
         _, st, kt = one_step(profile=True)
         sync()
         if rank == 0:

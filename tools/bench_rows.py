@@ -10,7 +10,7 @@ Every row carries
     stream in a second pass, against 8 TB/s,
   * `cpu`: the unmodified reference (oracle/_ref/fqs-1.1) timed on this box on a bounded sample of the same data in the
     row's own modes (whole process, -t 8: its fastest setting on a many-core host); absent when the binary is.
-Called by bench.py (extras of the N=1 line: `other_rows`) and by tools/gpu_rows.sh under rocprofv3 for the kernel
+Called by bench.py --full (extras of the N=1 line: `other_rows`) and by tools/gpu_rows.sh under rocprofv3 for the kernel
 statistics in profiles/.  Prints one JSON object."""
 from __future__ import annotations
 
