@@ -57,6 +57,11 @@ def _load(path: str):
     lib.fqsx_qual_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
     lib.fqsx_qual_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.fqsx_qual_destroy.argtypes = [C.c_void_p]
+    if hasattr(lib, "fqsx_qual_decode_block"):   # (as above: builds that predate the decoders)
+        lib.fqsx_qual_decode_block.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.fqsx_qual_decode_block_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        lib.fqsx_qual_contexts.argtypes = [C.c_void_p, C.c_void_p]
+        lib.fqsx_meta_decode_block.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
     lib.fqsx_meta_create.argtypes = [C.c_uint32, C.POINTER(C.c_void_p)]
     lib.fqsx_meta_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.fqsx_meta_destroy.argtypes = [C.c_void_p]
@@ -203,6 +208,17 @@ class MetaCodec:
             raise FqsxError("fqsx_meta_encode_block failed")
         return [C.string_at(self._streams[w], self._lens[w]) for w in range(self.T)]
 
+    def decode_block(self, streams, n_reads: int, paired: bool = False) -> np.ndarray:
+        """Inverse of encode_block: the T meta streams of a block -> its n_reads read lengths (an instance encodes or decodes a
+        file, never both)."""
+        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
+        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        out = np.zeros(max(1, n_reads), dtype=np.uint32)
+        rc = self._lib.fqsx_meta_decode_block(self._h, arr, lens.ctypes.data, n_reads, int(paired), out.ctypes.data)
+        if rc:
+            raise FqsxError(f"fqsx_meta_decode_block: {rc}: malformed or truncated meta stream")
+        return out[:n_reads]
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.fqsx_meta_destroy(self._h)
@@ -280,7 +296,7 @@ class IdCodec:
 
 
 class QualCodec:
-    """Quality-stream encoder on the GPU (fqsx_qual_*)."""
+    """Quality-stream coder on the GPU (fqsx_qual_*): one instance encodes or decodes a file, never both."""
 
     def __init__(self, header: bytes, device: int = 0, lib_path: Optional[str] = None):
         self._lib = load_library(lib_path)
@@ -310,6 +326,36 @@ class QualCodec:
             raise FqsxError(f"fqsx_qual_encode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
         return sum(self._lens[w] for w in range(self.T))
 
+    def decode_block(self, streams, read_off: np.ndarray) -> np.ndarray:
+        """Inverse of encode_block: the T quality streams of a block + read offsets -> concatenated quality bytes (ASCII)."""
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
+        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        out = np.zeros(max(1, int(read_off[-1])), dtype=np.uint8)
+        rc = self._lib.fqsx_qual_decode_block(self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1, out.ctypes.data)
+        if rc:
+            raise FqsxError(f"fqsx_qual_decode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return out[:int(read_off[-1])]
+
+    def decode_block_dev(self, streams, read_off: np.ndarray) -> int:
+        """The same, leaving the block in device memory: returns the device pointer (valid until the next call)."""
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
+        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        d_out = C.c_void_p()
+        rc = self._lib.fqsx_qual_decode_block_dev(self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1, C.byref(d_out))
+        if rc:
+            raise FqsxError(f"fqsx_qual_decode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return d_out.value or 0
+
+    def contexts(self) -> dict:
+        """Contexts stored per worker and the slots per worker of the context table (fqsx_qual_contexts)."""
+        a = np.zeros(self.T + 1, dtype=np.uint64)
+        rc = self._lib.fqsx_qual_contexts(self._h, a.ctypes.data)
+        if rc:
+            raise FqsxError(f"fqsx_qual_contexts: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return {"per_worker": [int(x) for x in a[:self.T]], "slots_per_worker": int(a[self.T])}
+
     def set_profiling(self, on: bool) -> None:
         self._lib.fqsx_qual_set_profiling.argtypes = [C.c_void_p, C.c_int]
         self._lib.fqsx_qual_set_profiling(self._h, int(on))
@@ -318,7 +364,7 @@ class QualCodec:
         a = (C.c_double * 2)()
         self._lib.fqsx_qual_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self._lib.fqsx_qual_kernel_times(self._h, a)
-        return {"encode_ms": a[0], "encode_launches": int(a[1])}
+        return {"encode_ms": a[0], "encode_launches": int(a[1])}   # (of a decoding instance: its decode launches)
 
     def close(self) -> None:
         if getattr(self, "_h", None):

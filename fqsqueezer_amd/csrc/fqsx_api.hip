@@ -15,6 +15,7 @@
 // so that both builds run this file's host orchestration alike.
 #include "fqsx_kernels.h"
 #include "fqsx_qual.h"
+#include "fqsx_qdec.h"
 #include "../../include/fqsx.h"
 #include "fqsx_vm.h"
 #include "fqsx_rt.h"
@@ -2315,6 +2316,7 @@ FQ_KERNEL64 void k_qual_encode(QualCfg cfg, u32 n_reads) {
   FQ_SHARED u8 lds_q[4096 + 96];
   qual_encode_body(cfg, lds_q, FQ_BLOCK, n_reads);
 }
+FQ_KERNEL64 void k_qual_decode(QualCfg cfg, QualDecArgs da, u32 n_reads) { qual_decode_body(cfg, da, FQ_BLOCK, n_reads); }
 FQ_KERNEL void k_qual_rehash(const u64 *o, u64 ocap_mask, u64 *n, u64 ncap_mask, u32 T, u32 slot_u64) {
   const u64 ocap = ocap_mask + 1, total = ocap * T;
   const u64 gstride = FQ_GRID_STRIDE(u64);
@@ -2347,11 +2349,18 @@ struct fqsx_qual : DevCtx {
   std::vector<u32> h_filled;
   std::vector<u64> h_lens;
   std::vector<u8> h_out;
+  // decoding (fqsx_qual_decode_block): the uploaded streams, the read offsets and the decoded block
+  QualDecArgs dec;
+  u8 *d_in;
+  u8 *d_dout;
+  u64 *d_roff;
+  u64 in_cap, dout_cap, roff_cap;
+  std::vector<u64> h_in;
 };
 
 extern "C" {
 
-// Kernel timing of the quality coder: HIP events around every k_qual_encode launch on the codec's stream (as
+// Kernel timing of the quality coder: HIP events around every k_qual_encode / k_qual_decode launch on the codec's stream (as
 // fqsx_dna_set_profiling / fqsx_dna_kernel_times); out[0] = accumulated milliseconds, out[1] = launches
 int fqsx_qual_set_profiling(fqsx_qual *q, int enable) {
   if (!q) return FQSX_E_ARG;
@@ -2389,6 +2398,10 @@ int fqsx_qual_create(const uint8_t *h, int device, fqsx_qual **out) {
   // Init + adjust_quality_map_*, quality.cpp:32-149
   auto band = [&](int a, int b, u8 v) { for (int i = a; i < b; ++i) cfg.fwd[i] = v; };
   const u32 thr = h[8];
+  // quality_code_map_rev, quality.cpp:74-149 (the decoder's table)
+  static const u8 rev8[8] = {0, 6, 15, 22, 27, 33, 37, 40}, rev4[4] = {0, 12, 23, 37};
+  memset(&q->dec, 0, sizeof(q->dec));
+  for (int i = 0; i < 96; ++i) q->dec.rev[i] = h[6] == 0 ? (u8)i : h[6] == 1 ? rev8[i & 7] : h[6] == 2 ? rev4[i & 3] : (u8)(i & 1 ? thr : 0);
   if (cfg.mode == 0) { cfg.n_sym = 96; cfg.bits = 6; cfg.nctx = 2; for (int i = 0; i < 96; ++i) cfg.fwd[i] = (u8)i; }
   else if (cfg.mode == 1) { cfg.n_sym = 8; cfg.bits = 4; cfg.nctx = 6; band(0, 2, 0); band(2, 10, 1); band(10, 20, 2); band(20, 25, 3); band(25, 30, 4); band(30, 35, 5); band(35, 40, 6); band(40, 96, 7); }
   else if (cfg.mode == 2) { cfg.n_sym = 4; cfg.bits = 3; cfg.nctx = 9; band(0, 2, 0); band(2, 15, 1); band(15, 31, 2); band(31, 96, 3); }
@@ -2480,6 +2493,88 @@ static int qual_encode_impl(fqsx_qual *q, const uint8_t *quals, const uint8_t *d
   for (u32 t = 0; t < T; ++t)
     if (q->h_lens[t] > cfg.out_cap) { g_err = "quality stream overflow"; return FQSX_E_DEVICE; }
   return collect_streams(c, q->d_compact, q->compact_cap, T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
+}
+
+// Inverse of qual_encode_impl: the T streams go up back to back in one transfer (behind their offsets and lengths, every
+// start 8-byte aligned), the table grows before the launch by the encoder's rule, the error word comes back with the block.
+static int qual_decode_impl(fqsx_qual *q, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *off, uint32_t n_reads,
+                            uint8_t *quals_out) {
+  DevCtx *c = q;
+  QualCfg &cfg = q->cfg;
+  const u32 T = q->T;
+  for (u32 i = 0; i < n_reads; ++i)
+    if (off[i + 1] < off[i] || off[i + 1] - off[i] >= (1ull << 24)) { g_err = "read offsets do not ascend or a read of 2^24 symbols or more"; return FQSX_E_ARG; }
+  if (off[0] != 0) { g_err = "read offsets must start at 0"; return FQSX_E_ARG; }
+  u64 max_w = 0, in_words = 2 * (u64)T;
+  q->h_in.assign(2 * (u64)T, 0);
+  for (u32 t = 0; t < T; ++t) {
+    u64 first = (u64)t * n_reads / T, last = ((u64)t + 1) * n_reads / T;
+    if (t) first &= ~1ull;
+    if (t + 1 < T) last &= ~1ull;
+    const u64 n_sym = off[last] - off[first];
+    max_w = std::max(max_w, n_sym);
+    if (n_sym && (lens[t] < 8 || !streams[t])) { g_err = "quality stream of a worker shorter than 8 bytes"; return FQSX_E_ARG; }   // sub_rc.h:114
+    q->h_in[t] = (in_words - 2 * (u64)T) * 8;
+    q->h_in[T + t] = streams[t] ? lens[t] : 0;
+    in_words += (q->h_in[T + t] + 7) / 8;
+  }
+  q->h_in.resize(in_words + 1, 0);
+  for (u32 t = 0; t < T; ++t)
+    if (q->h_in[T + t]) memcpy((u8 *)(q->h_in.data() + 2 * (u64)T) + q->h_in[t], streams[t], q->h_in[T + t]);
+  DEVCHK(dev_enter(c));
+  int rc;
+  void *p = nullptr;
+  // context table: every symbol can create one context
+  if ((rc = d2h_sync(c, q->h_filled.data(), cfg.filled, T * sizeof(u32)))) return rc;
+  u64 need = 0;
+  for (u32 t = 0; t < T; ++t) need = std::max<u64>(need, (u64)q->h_filled[t] + max_w + 64);
+  if (need * 2 > q->cap) {
+    const u64 ncap = pow2_at_least(need * 2);
+    if ((rc = dalloc(c, &p, ncap * T * cfg.slot_u64 * sizeof(u64), false))) return rc;
+    if ((rc = dfill_ff(c, p, ncap * T * cfg.slot_u64 * sizeof(u64)))) return rc;
+    LAUNCH(c, 2, k_qual_rehash, REHASH_GRID, 256, (const u64 *)cfg.tab, cfg.cap_mask, (u64 *)p, ncap - 1, T, cfg.slot_u64);
+    DEVCHK(dev_sync(c));
+    dfree(c, cfg.tab);
+    cfg.tab = (u64 *)p;
+    cfg.cap_mask = ncap - 1;
+    q->cap = ncap;
+  }
+  const u64 ni = (in_words + 1) * sizeof(u64), nout = (off[n_reads] + 64 + 7) & ~7ull, no = ((u64)n_reads + 1) * sizeof(u64);
+  if (ni > q->in_cap) { dfree(c, q->d_in); if ((rc = dalloc(c, &p, ni + ni / 4, false))) return rc; q->d_in = (u8 *)p; q->in_cap = ni + ni / 4; }
+  if (nout > q->dout_cap) { dfree(c, q->d_dout); if ((rc = dalloc(c, &p, nout + nout / 4, false))) return rc; q->d_dout = (u8 *)p; q->dout_cap = nout + nout / 4; }
+  if (no > q->roff_cap) { dfree(c, q->d_roff); if ((rc = dalloc(c, &p, no + no / 4, false))) return rc; q->d_roff = (u64 *)p; q->roff_cap = no + no / 4; }
+  if ((rc = h2d(c, q->d_in, q->h_in.data(), ni))) return rc;
+  if ((rc = h2d(c, q->d_roff, off, no))) return rc;
+  cfg.off = q->d_roff;
+  q->dec.in_off = (const u64 *)q->d_in;
+  q->dec.in = q->d_in + 2 * (u64)T * sizeof(u64);
+  q->dec.out = q->d_dout;
+  LAUNCH(c, 0, k_qual_decode, T, 64, cfg, q->dec, n_reads);
+  if (quals_out && off[n_reads] && (rc = d2h(c, quals_out, q->d_dout, off[n_reads]))) return rc;
+  if ((rc = d2h_sync(c, q->h_lens.data() + T, cfg.err, sizeof(u64)))) return rc;
+  const u32 err = (u32)q->h_lens[T];
+  if (err) { g_err = "device error " + std::to_string(err) + " in the quality decode kernel"; return FQSX_E_DEVICE; }
+  return FQSX_OK;
+}
+int fqsx_qual_decode_block(fqsx_qual *q, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off, uint32_t n_reads,
+                           uint8_t *quals_out) {
+  if (!q || !streams || !lens || !read_off || !quals_out) { g_err = "null argument"; return FQSX_E_ARG; }
+  return qual_decode_impl(q, streams, lens, read_off, n_reads, quals_out);
+}
+int fqsx_qual_decode_block_dev(fqsx_qual *q, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off, uint32_t n_reads,
+                               const uint8_t **d_quals_out) {
+  if (!q || !streams || !lens || !read_off || !d_quals_out) { g_err = "null argument"; return FQSX_E_ARG; }
+  const int rc = qual_decode_impl(q, streams, lens, read_off, n_reads, nullptr);
+  *d_quals_out = rc ? nullptr : q->d_dout;
+  return rc;
+}
+int fqsx_qual_contexts(fqsx_qual *q, uint64_t *out) {
+  if (!q || !out) { g_err = "null argument"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(q));
+  DEVCHK(d2h_sync(q, q->h_filled.data(), q->cfg.filled, q->T * sizeof(u32)));
+  for (u32 t = 0; t < q->T; ++t) out[t] = q->h_filled[t];
+  out[q->T] = q->cap;
+  return FQSX_OK;
 }
 
 }  // extern "C"

@@ -35,6 +35,28 @@ struct Enc {  // CRangeEncoder, sub_rc.h:32-87
   }
   void end() { for (int i = 0; i < 8; ++i) { out.push_back((u8)(low >> 56)); low <<= 8; } }
 };
+struct Dec {  // CRangeDecoder, sub_rc.h:93-158, on a buffer of n bytes; `over`: bytes asked for beyond its end (they read as 0)
+  u64 low, range, buf;
+  const u8 *p;
+  u64 n, pos, over;
+  u64 byte() { if (pos < n) return p[pos++]; ++over; return 0; }
+  void start(const u8 *p_, u64 n_) {
+    p = p_; n = n_; pos = 0; over = 0; buf = 0;
+    for (int i = 1; i <= 8; ++i) buf |= byte() << (64 - i * 8);
+    low = 0; range = 0xff00000000000000ULL;
+  }
+  u64 cum(u64 t) { range /= t; return buf / range; }
+  void update(u64 f, u64 c) {
+    const u64 Top = 0x00ffffffffffffULL, M = 0xff00000000000000ULL;
+    const u64 r = c * range;
+    buf -= r; low += r; range *= f;
+    while (range <= Top) {
+      if ((low ^ (low + range)) & M) range = (low | Top) - low;
+      buf = (buf << 8) + byte();
+      low <<= 8; range <<= 8;
+    }
+  }
+};
 struct Model256 {  // CRangeCoderModel(256 symbols, adder 1, max_total 1<<15), meta.cpp:33-38, rc.h:344-405
   u32 st[256], total;
   Model256() { for (auto &x : st) x = 1; total = 256; }
@@ -44,6 +66,16 @@ struct Model256 {  // CRangeCoderModel(256 symbols, adder 1, max_total 1<<15), m
     e.encode(st[x], cum, total);
     st[x] += 1; total += 1;
     while (total >= (1u << 15)) { total = 0; for (auto &v : st) { v = (v + 1) / 2; total += v; } }
+  }
+  int decode(Dec &d) {  // Decode, rc.h:403-417; -1: the cumulative frequency is not below the total (GetSym, rc.h:129-141)
+    const u64 lt = d.cum(total);
+    u32 x = 0, cum = 0;
+    while (x < 256 && cum + st[x] <= lt) cum += st[x++];
+    if (x == 256) return -1;
+    d.update(st[x], cum);
+    st[x] += 1; total += 1;
+    while (total >= (1u << 15)) { total = 0; for (auto &v : st) { v = (v + 1) / 2; total += v; } }
+    return (int)x;
   }
 };
 struct Worker { Model256 len[2], b0[2], b1[2], b2[2]; Enc enc; };
@@ -298,6 +330,36 @@ int fqsx_meta_encode_block_pe(fqsx_meta *m, const uint32_t *read_len, uint32_t n
     w.enc.end();
     streams[t] = w.enc.out.data();
     lens[t] = w.enc.out.size();
+  }
+  return FQSX_OK;
+}
+// decode_len(model), meta.cpp:76-97; false: malformed stream
+static bool decode_len(Worker &w, Dec &d, u32 mdl, u32 &L) {
+  const int flag = w.len[mdl].decode(d);
+  if (flag < 0) return false;
+  if (flag < 254) { L = (u32)flag; return true; }
+  int b0 = 0, b1, b2;
+  if (flag == 255 && (b0 = w.b0[mdl].decode(d)) < 0) return false;
+  if ((b1 = w.b1[mdl].decode(d)) < 0 || (b2 = w.b2[mdl].decode(d)) < 0) return false;
+  L = ((u32)b0 << 16) + ((u32)b1 << 8) + (u32)b2;
+  return true;
+}
+// inverse of fqsx_meta_encode_block_pe (DecompressReadLen / DecompressReadLenPE, meta.cpp:108-131)
+int fqsx_meta_decode_block(fqsx_meta *m, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                           uint32_t *read_len_out) {
+  if (!m || !streams || !lens || !read_len_out) return FQSX_E_ARG;
+  const u64 T = m->T;
+  for (u64 t = 0; t < T; ++t) {
+    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
+    if (t) first &= ~1ull;
+    if (t + 1 < T) last &= ~1ull;
+    if (first == last) continue;
+    if (!streams[t] || lens[t] < 8) return FQSX_E_ARG;   // sub_rc.h:114
+    Worker &w = m->w[t];
+    Dec d;
+    d.start(streams[t], lens[t]);
+    for (u64 i = first; i < last; ++i)
+      if (!decode_len(w, d, paired ? (u32)((i - first) & 1) : 0u, read_len_out[i]) || d.over) return FQSX_E_ARG;   // ran out of bytes
   }
   return FQSX_OK;
 }

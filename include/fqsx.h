@@ -212,7 +212,23 @@ int fqsx_qual_encode_block(fqsx_qual *, const uint8_t *quals, const uint64_t *re
 /* Same with the block already resident in device memory (d_quals / d_read_off device pointers, h_read_off the host copy). */
 int fqsx_qual_encode_block_dev(fqsx_qual *, const uint8_t *d_quals, const uint64_t *d_read_off, const uint64_t *h_read_off,
                                uint32_t n_reads, const uint8_t **streams, uint64_t *lens);
-int fqsx_qual_set_profiling(fqsx_qual *, int enable);         /* HIP events around every launch of the quality kernel ... */
+/* Decode one block's quality stream: inverse of fqsx_qual_encode_block (replaces CQualityCompressor::Decompress for all T
+ * workers, fqs/quality.cpp:175-200 with CRangeCoderModel::Decode, fqs/rc.h:403-421, and CRangeDecoder, fqs/sub_rc.h:93-158;
+ * called from the decoder workers, fqs/application.cpp:874-917).  streams[w] / lens[w] = worker w's quality stream of the
+ * block (host memory), read_off = n_reads+1 offsets of the reads inside quals_out, starting at 0 (the read lengths come from
+ * the meta stream).  quals_out receives the ASCII qualities (quality_code_map_rev + 33).  A worker that has symbols to
+ * decode and a stream shorter than 8 bytes: FQSX_E_ARG; a stream whose cumulative frequency leaves its model (malformed):
+ * FQSX_E_DEVICE, nothing outside read_off's range is written.  A codec instance is used either for encoding or for decoding
+ * a file, never both. */
+int fqsx_qual_decode_block(fqsx_qual *, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off,
+                           uint32_t n_reads, uint8_t *quals_out);
+/* The same, leaving the block in device memory: *d_quals_out is owned by the codec and valid until the next call. */
+int fqsx_qual_decode_block_dev(fqsx_qual *, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off,
+                               uint32_t n_reads, const uint8_t **d_quals_out);
+/* Contexts stored per worker (out[0..T)) and, in out[T], the slots per worker of the context table (the reference's
+ * m_ctx_rc, fqs/quality.h:30): what a decoder must agree on with the encoder of the same data. */
+int fqsx_qual_contexts(fqsx_qual *, uint64_t *out);
+int fqsx_qual_set_profiling(fqsx_qual *, int enable);         /* HIP events around every launch of the quality kernel (encode or decode) ... */
 int fqsx_qual_kernel_times(fqsx_qual *, double out[2]);       /* ... out[0] = accumulated milliseconds, out[1] = launches */
 void fqsx_qual_destroy(fqsx_qual *);
 
@@ -226,6 +242,11 @@ int fqsx_meta_encode_block(fqsx_meta *, const uint32_t *read_len, uint32_t n_rea
 /* paired != 0: reads alternate mate 1 / mate 2 (CompressReadLenPE, fqs/meta.cpp:100-107) */
 int fqsx_meta_encode_block_pe(fqsx_meta *, const uint32_t *read_len, uint32_t n_reads, int paired,
                               const uint8_t **streams, uint64_t *lens);
+/* Inverse of fqsx_meta_encode_block_pe (CMetaCompressor::DecompressReadLen / DecompressReadLenPE, fqs/meta.cpp:76-131):
+ * n_reads comes from the container block's header, paired as in the encoder.  A stream that runs out of bytes or is
+ * malformed: FQSX_E_ARG.  An instance is used either for encoding or for decoding a file, never both. */
+int fqsx_meta_decode_block(fqsx_meta *, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                           uint32_t *read_len_out);
 void fqsx_meta_destroy(fqsx_meta *);
 
 /* Read-id stream (host CPU by design: string tokeniser + delta coder).  Replaces

@@ -39,6 +39,8 @@ Fixtures (data only -- inputs are re-generated deterministically by fqsqueezer_a
                             -om s at the DEFAULT -gs 3100, T = 8: DNA digests per block (only with --only c21; ~50 GiB, about an hour)
   c22_pe1M_s_oo_t8.json     BASELINE configs[4]'s modes at 1 M pairs: 150bp mates, G=15Mbp, seed 22, varied ids, -p -om s -qm o -im o -gs 15, T=8:
                             all four streams of every block + the file's SHA-256 (only with --only c22; ~10 min)
+  c23_c4_q{8,4,2}_t4.fqs / c23_c5_pe_qo_t3.fqs + .json  files for the quality and meta decoders: lossy quality modes on the
+                            c4 reads, lossless qualities on 1400 of the c5 pairs; SHA-256 of the quality lines `fqs d` writes for each
 Usage: python tools/make_golden.py [--work /tmp/w] [--only c1|c2|c3]
 """
 import argparse, hashlib, json, os, subprocess, sys
@@ -241,6 +243,8 @@ def main():
         c21(a, 8)
     if a.only == "c22":
         c22(a)
+    if a.only in ("", "c23"):
+        c23(a)
     if a.only in ("", "c3"):
         fq = os.path.join(a.work, "c3.fq")
         if not os.path.exists(fq):
@@ -393,6 +397,42 @@ def c22(a):
     meta = {"pairs": npairs, "len": 150, "genome": G, "seed": seed, "gs": 15, "om": "s", "qm": "o", "im": "o", "threads": 8,
             "paired": True, "varied_ids": True}
     json.dump(fdigest(out, meta), open(os.path.join(GOLD, "c22_pe1M_s_oo_t8.json"), "w"))
+
+
+def c23(a):
+    """Files for the quality / meta decoders: the lossy quality modes on the c4 reads (ragged lengths: odd worker partitions) at
+    T = 4 and lossless qualities on the first 1400 c5 pairs (-p -om s, T = 3), all -im n; beside each the SHA-256 of the quality lines of
+    what `fqs d` writes for it (paired: one digest per mate file)."""
+    def qsha(path):
+        lines = open(path, "rb").read().split(b"\n")[3::4]
+        return len(lines), hashlib.sha256(b"".join(x + b"\n" for x in lines)).hexdigest()
+
+    ids, seqs, quals = ragged()
+    fq = os.path.join(a.work, "c4.fq")
+    with open(fq, "wb") as f:
+        for i, sq, q in zip(ids, seqs, quals):
+            f.write(i + b"\n" + sq + b"\n+\n" + q + b"\n")
+    for qm in ("8", "4", "2"):
+        out, dec = os.path.join(GOLD, f"c23_c4_q{qm}_t4.fqs"), os.path.join(a.work, f"c23_q{qm}.fq")
+        subprocess.check_call([REF, "e", "-s", "-om", "o", "-t", "4", "-gs", "1", "-qm", qm] + (["-qt", "25"] if qm == "2" else []) +
+                              ["-im", "n", "-v", "0", "-tmp", os.path.join(a.work, "tmpd_"), "-out", out, fq], stdout=subprocess.DEVNULL)
+        subprocess.check_call([REF, "d", "-out", dec, out], stdout=subprocess.DEVNULL)
+        n, sha = qsha(dec)
+        json.dump({"input": "c4 (3000 ragged reads, seed 4)", "om": "o", "qm": qm, "threads": 4, "decoded_reads": n, "decoded_quality_sha256": sha},
+                  open(os.path.join(GOLD, f"c23_c4_q{qm}_t4.json"), "w"), indent=1)
+    from fqsqueezer_amd.synth import synth_pairs, synth_quals
+    r1, r2 = synth_pairs(4000, 100, 60000, 5)
+    f1, f2 = os.path.join(a.work, "c23_1.fq"), os.path.join(a.work, "c23_2.fq")
+    np_ = 1400   # the first 1400 of the c5 pairs: the whole 4000 give a file larger than any other .fqs fixture
+    write_fastq(f1, r1[:np_], synth_quals(4000, 100, 5)[:np_], mate=1)
+    write_fastq(f2, r2[:np_], synth_quals(4000, 100, 6)[:np_], mate=2)
+    out, d1, d2 = os.path.join(GOLD, "c23_c5_pe_qo_t3.fqs"), os.path.join(a.work, "c23_pe_1.fq"), os.path.join(a.work, "c23_pe_2.fq")
+    subprocess.check_call([REF, "e", "-p", "-om", "s", "-t", "3", "-gs", "1", "-qm", "o", "-im", "n", "-v", "0",
+                           "-tmp", os.path.join(a.work, "tmpd_"), "-out", out, f1, f2], stdout=subprocess.DEVNULL)
+    subprocess.check_call([REF, "d", "-out", d1, "-out2", d2, out], stdout=subprocess.DEVNULL)
+    (n1, s1), (n2, s2) = qsha(d1), qsha(d2)
+    json.dump({"input": "c5, the first 1400 pairs (seeds 5 / 6)", "pairs": np_, "om": "s", "qm": "o", "threads": 3, "paired": True, "decoded_reads": n1 + n2,
+               "decoded_quality_sha256": s1, "decoded_quality_sha256_mate2": s2}, open(os.path.join(GOLD, "c23_c5_pe_qo_t3.json"), "w"), indent=1)
 
 
 def c4_ref_decode(a, fq):
