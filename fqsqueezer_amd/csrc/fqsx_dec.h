@@ -237,6 +237,9 @@ FQ_DEV void suffix_dec(Wk &w, u8 *codes, u8 *p_out, u32 size, bool original_orde
   // The cluster a b-mer look-up starts in is fixed by the k-mer's kernel (symbols 2 .. k-3), so the look-up of position
   // i + 1 -- sub-table, home slot, orientation -- is known before symbol i is decoded: its two buckets are requested
   // while the context search and the range decoder of position i run, and matched against the full k-mer afterwards.
+  // The request is made before position i's LV_BMER_UNC revert can replace the k-mer: it is only used if sub-table, bucket a
+  // AND bucket b are those of the k-mer actually looked up (with two-choice buckets a does not determine b; same a and b =
+  // same buckets and the same overflow chain, so the test is exact).
   TabG nf;
   nf.s = nullptr; nf.a = nf.b = 0;
   for (u32 x = 0; x < FQSX_BKT; ++x) { nf.ia[x] = 0; nf.ib[x] = 0; }
@@ -253,8 +256,12 @@ FQ_DEV void suffix_dec(Wk &w, u8 *codes, u8 *p_out, u32 size, bool original_orde
       const u64 *sl = cfg->g_b.slots + (u64)sub * cfg->g_b.stride;
       u64 ns = 0;
       c4_zero(counts);
-      if (nf.s == sl && nf.a == tab_home(cfg->g_b, key >> (64 - 2 * cfg->g_b.k)).a) tab_rest(cfg->g_b, nf, key, nd, counts, ns);
-      else tab_scan(cfg->g_b, sub, key, nd, counts, ns);   // (a correction changed the k-mer's kernel: ask again)
+      const TabHome h = tab_home(cfg->g_b, key >> (64 - 2 * cfg->g_b.k));
+      if (nf.s == sl && nf.a == h.a && nf.b == h.b) tab_rest(cfg->g_b, nf, key, nd, counts, ns);
+      else {   // (a revert changed the k-mer's kernel: ask again)
+        tab_scan(cfg->g_b, sub, key, nd, counts, ns);
+        if (nf.s) w.st[ST_DEC_REFETCH] += 1;
+      }
       w.st[ST_GPROBE] += 1;
       w.st[ST_GSLOT] += ns;
       if (c4_any(counts)) {

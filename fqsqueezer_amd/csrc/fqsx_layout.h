@@ -142,6 +142,8 @@ enum {
   ST_SIV_SAVED,    // siv words the reference's rank loop sweeps (dna.cpp:600-605: the whole range between the previous and the current
                    // p-mer) minus the words the kernel read for the same rank (end blocks + count index): ST_SIV_WORDS + this = the
                    // algorithmic figure of SURVEY 8d
+  ST_DEC_REFETCH,  // decoder: b-mer look-ups whose buckets, requested a position ahead, were dropped and looked up again (fqsx_dec.h: suffix_dec);
+                   // counted as ST_GPROBE is (the wave-uniform count one lane holds), so figures of different builds compare only in kind
   ST_N
 };
 // section timers (only maintained by -DFQSX_TIMING builds)
