@@ -254,7 +254,7 @@ def sort_order(bases: np.ndarray, read_off: np.ndarray, device: int = 0, lib_pat
 
 class IdCodec:
     """Read-id stream of the container (header byte 7 = id mode).  device = None: the host coder (fqsx_id_*, one host thread per
-    worker); device = ordinal: the GPU coder (fqsx_idg_*, one wavefront per worker) -- the same bytes."""
+    worker); device = ordinal: the GPU coder (fqsx_idg_*, one wavefront per worker) -- the same bytes.  Both flavours decode too."""
 
     def __init__(self, header: bytes, lib_path: Optional[str] = None, device: Optional[int] = None):
         self._lib = load_library(lib_path)
@@ -282,6 +282,57 @@ class IdCodec:
         if rc:
             raise FqsxError(f"fqsx_id{'g' if self._gpu else ''}_encode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
         return [C.string_at(self._streams[w], self._lens[w]) for w in range(self.T)]
+
+    def decode_block(self, streams, n_reads: int, paired: bool = False):
+        """Inverse of encode_block: the T id streams of a block -> (ids uint8[], id_off uint64[n_reads + 1]), the id lines the
+        reference's decoder writes, each with its line feed, in block order (an instance encodes or decodes a file, never both).
+        GPU flavour: FqsxError whose `staging` is True if a line is beyond what the kernel stages (the host flavour has no limits)."""
+        L = self._lib
+        name = "fqsx_idg_decode_block" if self._gpu else "fqsx_id_decode_block"
+        f = getattr(L, name)
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
+        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        ids, off = C.c_void_p(), C.c_void_p()
+        rc = f(self._h, arr, lens.ctypes.data, n_reads, int(paired), C.byref(ids), C.byref(off))
+        if rc:
+            msg = L.fqsx_last_error().decode() if self._gpu else ("a worker's stream is shorter than 8 bytes or a bad argument" if rc == -1 else "malformed or truncated id stream")
+            e = FqsxError(f"{name}: {rc}: {msg}")
+            e.staging = False
+            if self._gpu:   # what the kernel reported: 5 / 6 = beyond its staging sizes / its list of instrument names
+                L.fqsx_idg_error_kind.argtypes = [C.c_void_p]
+                e.staging = rc == -5 and L.fqsx_idg_error_kind(self._h) in (5, 6)
+            raise e
+        id_off = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(n_reads + 1,)).copy()
+        n = int(id_off[-1])
+        out = np.ctypeslib.as_array(C.cast(ids, C.POINTER(C.c_uint8)), shape=(max(n, 1),))[:n].copy()
+        return out, id_off
+
+    def stats(self) -> dict:
+        """GPU flavour: how often the decoder had to grow (fqsx_idg_stats) and its capacities."""
+        a = (C.c_uint64 * 8)()
+        self._lib.fqsx_idg_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        if not self._gpu or self._lib.fqsx_idg_stats(self._h, a):
+            raise FqsxError("fqsx_idg_stats failed")
+        return dict(zip(["retries", "grow_small", "grow_big", "grow_out", "small_slots", "big_slots", "out_bytes"], [int(x) for x in a]))
+
+    def state(self) -> np.ndarray:
+        """GPU flavour: (T, 3) models in the small table, in the big table and move-to-front names per worker after the last block."""
+        a = np.zeros(4 * self.T, dtype=np.uint32)
+        self._lib.fqsx_idg_state.argtypes = [C.c_void_p, C.c_void_p]
+        if not self._gpu or self._lib.fqsx_idg_state(self._h, a.ctypes.data):
+            raise FqsxError("fqsx_idg_state failed")
+        return a.reshape(self.T, 4)[:, :3].copy()
+
+    def set_profiling(self, on: bool) -> None:
+        self._lib.fqsx_idg_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        self._lib.fqsx_idg_set_profiling(self._h, int(on))
+
+    def kernel_times(self) -> dict:
+        a = (C.c_double * 2)()
+        self._lib.fqsx_idg_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._lib.fqsx_idg_kernel_times(self._h, a)
+        return {"ms": a[0], "launches": int(a[1])}
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -2583,10 +2583,15 @@ int fqsx_qual_contexts(fqsx_qual *q, uint64_t *out) {
 // Read-id stream on the GPU: one wavefront per worker, models in two per-worker tables in HBM
 // =======================================================================================================
 #include "fqsx_idk.h"
+#include "fqsx_iddec.h"
 
 FQ_KERNEL64 void k_id_encode(IdCfg cfg, u32 n_reads, u32 paired) {
   FQ_SHARED IdShared sm;
   id_encode_body(cfg, &sm, FQ_BLOCK, n_reads, paired);
+}
+FQ_KERNEL64 void k_id_decode(IdCfg cfg, IdDecArgs da, u32 n_reads, u32 paired) {
+  FQ_SHARED IdShared sm;
+  id_decode_body(cfg, da, &sm, FQ_BLOCK, n_reads, paired);
 }
 // the twelve fixed models of every worker: all ones (mtf_flag 11 symbols, mtf_code[k] 2 << k, mtf_byte 256; id.cpp:84-105)
 FQ_KERNEL64 void k_id_init_fixed(IdCfg cfg) {
@@ -2610,6 +2615,19 @@ struct fqsx_idg : DevCtx {
   std::vector<u32> h_state;
   std::vector<u64> h_lens;
   std::vector<u8> h_out;
+  // decoding (fqsx_idg_decode_block): the uploaded streams, the line lengths, the snapshot a block is run again from
+  u8 *d_in;
+  u32 *d_idlen;
+  u64 in_cap, idlen_cap;
+  u64 *snap_small, *snap_big, *snap_fixed;
+  u8 *snap_mtf;
+  u64 snap_small_cap, snap_big_cap;
+  std::vector<u64> h_in, h_idoff;
+  std::vector<u32> h_idlen;
+  std::vector<u8> h_ids;
+  u64 n_retry, n_grow_small, n_grow_big, n_grow_out;
+  u32 last_kind = 0;             // the kernel's error word of the last decode (fqsx_idg_error_kind)
+  u64 dec_out_init = 1u << 18;   // first per-worker capacity of the decoder's output
 };
 
 extern "C" {
@@ -2635,6 +2653,11 @@ int fqsx_idg_create(const uint8_t *h, int device, fqsx_idg **out) {
   cfg.T = q->T;
   cfg.mode = h[7];   // 0 lossless, 1 instrument (params.h:18,92)
   q->small_cap = 1u << 10; q->big_cap = 1u << 9;
+  if (const char *e = getenv("FQSX_IDG_INIT")) {   // (tests: growth from tiny tables and a tiny decoder output)
+    const u64 v = strtoull(e, nullptr, 10);
+    q->small_cap = q->big_cap = pow2_at_least(std::max<u64>(16, v));
+    q->dec_out_init = (std::max<u64>(64, v) + 7) & ~7ull;
+  }
   const u64 T = q->T;
   void *p = nullptr;
   auto fail = [&](int r) { fqsx_idg_destroy(q); return r; };
@@ -2729,6 +2752,189 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
   for (u64 t = 0; t < T; ++t)
     if (q->h_lens[t] > cfg.out_cap) { g_err = "id stream overflow"; return FQSX_E_DEVICE; }
   return collect_streams(c, q->d_compact, q->compact_cap, (u32)T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
+}
+
+// Inverse of fqsx_idg_encode_block.  The encoder sizes its tables and its output from the ids it is given; the decoder
+// cannot see them, so it runs a block from a snapshot: the small / big / fixed / move-to-front tables are copied device to
+// device before the launch, and when the kernel reports IDK_ERR_TABLE or IDK_ERR_OUT the snapshot is put back, the capacity
+// that ran out is doubled (k_qual_rehash) and the block runs again.  A valid stream never fails for want of pre-sizing.
+int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                          const uint8_t **ids_out, const uint64_t **id_off_out) {
+  if (!q || !streams || !lens || !ids_out || !id_off_out || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
+  DevCtx *c = q;
+  IdCfg &cfg = q->cfg;
+  const u64 T = q->T;
+  u64 in_words = 2 * T;
+  q->h_in.assign(2 * T, 0);
+  for (u64 t = 0; t < T; ++t) {
+    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
+    if (t) first &= ~1ull;
+    if (t + 1 < T) last &= ~1ull;
+    if (first < last && (lens[t] < 8 || !streams[t])) { g_err = "id stream of a worker shorter than 8 bytes"; return FQSX_E_ARG; }   // sub_rc.h:114
+    q->h_in[t] = (in_words - 2 * T) * 8;
+    q->h_in[T + t] = streams[t] ? lens[t] : 0;
+    in_words += (q->h_in[T + t] + 7) / 8;
+  }
+  q->h_in.resize(in_words + 1, 0);
+  for (u64 t = 0; t < T; ++t)
+    if (q->h_in[T + t]) memcpy((u8 *)(q->h_in.data() + 2 * T) + q->h_in[t], streams[t], q->h_in[T + t]);
+  DEVCHK(dev_enter(c));
+  int rc;
+  void *p = nullptr;
+  const u64 ni = (in_words + 1) * sizeof(u64), nl = ((u64)n_reads + 1) * sizeof(u32);
+  // (a buffer that is handed back is forgotten before its successor is asked for: a failed allocation leaves nothing dangling)
+  if (ni > q->in_cap) { dfree(c, q->d_in); q->d_in = nullptr; q->in_cap = 0; if ((rc = dalloc(c, &p, ni + ni / 4, false))) return rc; q->d_in = (u8 *)p; q->in_cap = ni + ni / 4; }
+  if (nl > q->idlen_cap) { dfree(c, q->d_idlen); q->d_idlen = nullptr; q->idlen_cap = 0; if ((rc = dalloc(c, &p, nl + nl / 4, false))) return rc; q->d_idlen = (u32 *)p; q->idlen_cap = nl + nl / 4; }
+  if ((rc = h2d(c, q->d_in, q->h_in.data(), ni))) return rc;
+  if (q->out_cap < q->dec_out_init) {
+    dfree(c, cfg.out);
+    cfg.out = nullptr; cfg.out_cap = q->out_cap = 0;
+    if ((rc = dalloc(c, &p, q->dec_out_init * T, false))) return rc;
+    cfg.out = (u8 *)p; cfg.out_cap = q->out_cap = q->dec_out_init;
+  }
+  const u64 fixed_bytes = T * IDK_FIXED * IDK_BIG_U64 * sizeof(u64), mtf_bytes = T * cfg.mtf_cap * IDK_NAME, state_bytes = 4 * T * sizeof(u32);
+  if (!q->snap_fixed) {
+    if ((rc = dalloc(c, &p, fixed_bytes, false))) return rc;
+    q->snap_fixed = (u64 *)p;
+    if (cfg.mode == 1) { if ((rc = dalloc(c, &p, mtf_bytes, false))) return rc; q->snap_mtf = (u8 *)p; }
+  }
+  auto grow = [&](u64 *&tab, u64 &cap, u64 &mask, u32 slot_u64) -> int {   // from the (restored) table into one of twice the slots
+    const u64 ncap = cap * 2;
+    void *nt = nullptr;
+    int r = dalloc(c, &nt, ncap * T * slot_u64 * sizeof(u64), false);
+    if (r) return r;
+    if (!(r = dfill_ff(c, nt, ncap * T * slot_u64 * sizeof(u64))))
+      r = dev_launch(c, 2, false, [&] { DEV_KERNEL(c, k_qual_rehash, REHASH_GRID, 256, (const u64 *)tab, mask, (u64 *)nt, ncap - 1, (u32)T, slot_u64); });
+    if (!r) r = dev_sync(c);
+    if (r) { dfree(c, nt); return r; }   // (the old table stays in place)
+    p = nt;
+    dfree(c, tab);
+    tab = (u64 *)p; cap = ncap; mask = ncap - 1;
+    return FQSX_OK;
+  };
+  // How far a valid stream can make the capacities grow: a new model is all ones, so the symbol that creates one costs at least
+  // 1 bit (small) or 7 bits (big) of the worker's stream, and a line has at most IDK_MAX_ID bytes.  A stream that asks for more
+  // is malformed.
+  u64 lim_small = 0, lim_big = 0, lim_out = 0;
+  for (u64 t = 0; t < T; ++t) {
+    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;
+    if (t) first &= ~1ull;
+    if (t + 1 < T) last &= ~1ull;
+    lim_small = std::max(lim_small, (u64)q->h_state[4 * t] + 8 * q->h_in[T + t] + 64);
+    lim_big = std::max(lim_big, (u64)q->h_state[4 * t + 1] + 2 * q->h_in[T + t] + 64);
+    lim_out = std::max(lim_out, (last - first) * IDK_MAX_ID + 64);
+  }
+  lim_small = pow2_at_least(lim_small * 2); lim_big = pow2_at_least(lim_big * 2); lim_out = pow2_at_least(lim_out) * 2;
+  IdDecArgs da;
+  da.in_off = (const u64 *)q->d_in;
+  da.in = q->d_in + 2 * T * sizeof(u64);
+  da.id_len = q->d_idlen;
+  for (u32 attempt = 0;; ++attempt) {
+    const u64 small_bytes = q->small_cap * T * 2 * sizeof(u64), big_bytes = q->big_cap * T * IDK_BIG_U64 * sizeof(u64);
+    if (q->snap_small_cap != q->small_cap) {
+      dfree(c, q->snap_small);
+      q->snap_small = nullptr; q->snap_small_cap = 0;
+      if ((rc = dalloc(c, &p, small_bytes, false))) return rc;
+      q->snap_small = (u64 *)p; q->snap_small_cap = q->small_cap;
+    }
+    if (q->snap_big_cap != q->big_cap) {
+      dfree(c, q->snap_big);
+      q->snap_big = nullptr; q->snap_big_cap = 0;
+      if ((rc = dalloc(c, &p, big_bytes, false))) return rc;
+      q->snap_big = (u64 *)p; q->snap_big_cap = q->big_cap;
+    }
+    if ((rc = d2d(c, q->snap_small, cfg.small, small_bytes)) || (rc = d2d(c, q->snap_big, cfg.big, big_bytes)) ||
+        (rc = d2d(c, q->snap_fixed, cfg.fixed, fixed_bytes)) || (cfg.mode == 1 && (rc = d2d(c, q->snap_mtf, cfg.mtf, mtf_bytes))))
+      return rc;
+    LAUNCH(c, 0, k_id_decode, q->T, 64, cfg, da, n_reads, (u32)(paired != 0));
+    if ((rc = d2h_sync(c, q->h_lens.data(), cfg.lens, (T + 2 + 2 * T) * sizeof(u64)))) return rc;
+    const u32 err = (u32)q->h_lens[T] & 0xff, which = ((u32)q->h_lens[T] >> 8) & 0xff;
+    q->last_kind = err;
+    if (!err) break;
+    // the models, the fixed models, the names and the state words as they were before the block
+    q->h_lens[T] = 0;
+    memcpy(q->h_lens.data() + T + 2, q->h_state.data(), state_bytes);
+    if ((rc = h2d(c, cfg.lens + T, q->h_lens.data() + T, 2 * sizeof(u64) + state_bytes)) || (rc = d2d(c, cfg.small, q->snap_small, small_bytes)) ||
+        (rc = d2d(c, cfg.big, q->snap_big, big_bytes)) || (rc = d2d(c, cfg.fixed, q->snap_fixed, fixed_bytes)) ||
+        (cfg.mode == 1 && (rc = d2d(c, cfg.mtf, q->snap_mtf, mtf_bytes))) || (rc = dev_sync(c)))
+      return rc;
+    const bool can_grow = err == IDK_ERR_OUT ? q->out_cap * 2 <= std::max(lim_out, q->dec_out_init) : err == IDK_ERR_TABLE && which == 1 ? q->small_cap * 2 <= lim_small
+                                                                                     : err == IDK_ERR_TABLE && q->big_cap * 2 <= lim_big;
+    if (can_grow && attempt < 64) {
+      q->n_retry += 1;
+      if (err == IDK_ERR_OUT) {
+        const u64 ncap = q->out_cap * 2;
+        dfree(c, cfg.out);
+        cfg.out = nullptr; cfg.out_cap = q->out_cap = 0;
+        if ((rc = dalloc(c, &p, ncap * T, false))) return rc;
+        cfg.out = (u8 *)p; cfg.out_cap = q->out_cap = ncap;
+        q->n_grow_out += 1;
+      } else if (which == 1) {
+        if ((rc = grow(cfg.small, q->small_cap, cfg.small_mask, 2))) return rc;
+        q->n_grow_small += 1;
+      } else {
+        if ((rc = grow(cfg.big, q->big_cap, cfg.big_mask, IDK_BIG_U64))) return rc;
+        q->n_grow_big += 1;
+      }
+      continue;
+    }
+    static const char *what[] = {"", "", "", "output overflow", "model table full", "id, token count or instrument name beyond the kernel's staging sizes",
+                                 "more than 4096 instrument names", "malformed or truncated id stream"};
+    g_err = std::string("id decode kernel: ") + (err < 8 ? what[err] : "error");
+    return FQSX_E_DEVICE;
+  }
+  memcpy(q->h_state.data(), q->h_lens.data() + T + 2, state_bytes);
+  // the workers' lines, in worker order, are the block's lines in block order
+  q->h_idlen.assign((u64)n_reads + 1, 0);
+  if (n_reads && (rc = d2h(c, q->h_idlen.data(), q->d_idlen, (u64)n_reads * sizeof(u32)))) return rc;
+  u64 total = 0;
+  for (u64 t = 0; t < T; ++t) {
+    if (q->h_lens[t] > cfg.out_cap) { g_err = "id decoder output overflow"; return FQSX_E_DEVICE; }
+    total += q->h_lens[t];
+  }
+  q->h_ids.resize(total + 8);
+  u64 at = 0;
+  for (u64 t = 0; t < T; ++t) {
+    if (q->h_lens[t] && (rc = d2h(c, q->h_ids.data() + at, cfg.out + t * cfg.out_cap, q->h_lens[t]))) return rc;
+    at += q->h_lens[t];
+  }
+  DEVCHK(dev_sync(c));
+  q->h_idoff.assign((u64)n_reads + 1, 0);
+  for (u64 i = 0; i < n_reads; ++i) q->h_idoff[i + 1] = q->h_idoff[i] + q->h_idlen[i];
+  if (q->h_idoff[n_reads] != total) { g_err = "id decoder: line lengths and output disagree"; return FQSX_E_DEVICE; }
+  *ids_out = q->h_ids.data();
+  *id_off_out = q->h_idoff.data();
+  return FQSX_OK;
+}
+
+// out[0] blocks the decoder ran again, out[1] / out[2] / out[3] growths of the small table, the big table and the decoder's output,
+// out[4] / out[5] slots per worker of the small and the big table, out[6] bytes per worker of the output, out[7] 0
+int fqsx_idg_stats(fqsx_idg *q, uint64_t out[8]) {
+  if (!q || !out) { g_err = "null argument"; return FQSX_E_ARG; }
+  out[0] = q->n_retry; out[1] = q->n_grow_small; out[2] = q->n_grow_big; out[3] = q->n_grow_out;
+  out[4] = q->small_cap; out[5] = q->big_cap; out[6] = q->out_cap; out[7] = 0;
+  return FQSX_OK;
+}
+// the per-worker state words after the last block: out[4 * w + 0 / 1 / 2] = small slots, big slots, move-to-front entries of worker w
+int fqsx_idg_state(fqsx_idg *q, uint32_t *out) {
+  if (!q || !out) { g_err = "null argument"; return FQSX_E_ARG; }
+  memcpy(out, q->h_state.data(), 4 * (u64)q->T * sizeof(u32));
+  return FQSX_OK;
+}
+// What the kernel reported in the last fqsx_idg_decode_block: 0 none, 3 output, 4 model table (both grown and run again unless the
+// stream cannot be valid), 5 a line, its tokens or an instrument name beyond the staging sizes, 6 more than 4096 instrument names
+// (5 and 6: decode the file with fqsx_id_decode_block), 7 malformed or truncated stream
+int fqsx_idg_error_kind(fqsx_idg *q) { return q ? (int)q->last_kind : FQSX_E_ARG; }
+int fqsx_idg_set_profiling(fqsx_idg *q, int enable) {
+  if (!q) return FQSX_E_ARG;
+  q->profiling = enable != 0;
+  return FQSX_OK;
+}
+int fqsx_idg_kernel_times(fqsx_idg *q, double out[2]) {
+  if (!q || !out) return FQSX_E_ARG;
+  out[0] = q->k_ms[0];
+  out[1] = (double)q->k_n[0];
+  return FQSX_OK;
 }
 
 }  // extern "C"

@@ -94,6 +94,17 @@ struct ModelN {
     st[x] += 1; total += 1;
     while (total >= (1u << 15)) { total = 0; for (auto &v : st) { v = (v + 1) / 2; total += v; } }
   }
+  int decode(Dec &d) {  // Decode, rc.h:403-417; -1: the cumulative frequency is not below the total, or the stream has run out
+    const u64 lt = d.cum(total);
+    u32 x = 0, cum = 0;
+    while (x < st.size() && cum + st[x] <= lt) cum += st[x++];
+    if (x == st.size()) return -1;
+    d.update(st[x], cum);
+    if (d.over) return -1;
+    st[x] += 1; total += 1;
+    while (total >= (1u << 15)) { total = 0; for (auto &v : st) { v = (v + 1) / 2; total += v; } }
+    return (int)x;
+  }
 };
 struct CtxMap {  // exact map context -> model, created from the all-ones template on first use (id.cpp:763-811)
   u32 n;
@@ -125,6 +136,8 @@ struct IdWorker {
   std::vector<Token> tok_prev, tok_cur;
   std::vector<int64_t> deltas;
   std::vector<u8> id_prev, id_cur;   // private copies: instrument mode terminates the name in place (id.cpp:427-428)
+  std::vector<u8> dec_ids;           // decoder: the worker's lines of the block ...
+  std::vector<u32> dec_len;          // ... and their lengths
   Mtf mtf;
   ModelN mtf_flag{11};
   std::vector<ModelN> mtf_code, mtf_byte;
@@ -265,10 +278,133 @@ bool typical_pe_ids(const u8 *a, u32 na, const u8 *b, u32 nb) {  // id.cpp:241-2
   if (!std::equal(a, a + na - 2, b)) return false;
   return a[na - 2] == '1' && b[nb - 2] == '2';
 }
+
+// ---- the decoder (id.cpp:182-228, 495-731).  No limits on a line beyond the format's; a malformed stream ends in w.err.
+const size_t ID_LINE_LIMIT = 1u << 24;   // (a line the reference's block buffer could not hold either)
+// store_int, id.h:117-149: one digit below 10 (also for negative values, whose "digit" is '0' + val % 10), none from 10^15
+void store_int(std::vector<u8> &p, int64_t val) {
+  int n_dig = 0;
+  if (val < 1000000000000000ll) {
+    n_dig = 1;
+    for (int64_t t = 10; n_dig < 15 && val >= t; t *= 10) ++n_dig;
+  }
+  const size_t begin = p.size();
+  p.resize(begin + n_dig);
+  for (int i = n_dig - 1; i >= 0; --i) { p[begin + i] = (u8)('0' + (int)(val % 10)); val /= 10; }
+}
+// decompress_lossless, id.cpp:495-666: the line is left in w.id_prev
+void id_dec_lossless(IdWorker &w, Dec &d) {
+  std::vector<u8> &p = w.id_cur;
+  p.clear();
+  auto sym = [&](ModelN &m) -> u32 { const int x = m.decode(d); if (x < 0) { w.err = 7; return 0; } return (u32)x; };
+  if (sym(w.flags.at(w.ctx_flags)) == 1 && !w.err) {   // tokens of the same type
+    w.ctx_flags = ((w.ctx_flags << 1) + 1) & 0xff;
+    const u32 n_tok = (u32)w.tok_prev.size();
+    if (w.deltas.size() < n_tok) w.deltas.resize(n_tok, 0);
+    const u8 *q = w.id_prev.data();
+    for (u32 i = 0; i < n_tok && !w.err; ++i) {
+      const Token &pv = w.tok_prev[i];
+      if (!pv.numeric) {
+        if (sym(w.literal_same.at(i)) == 1) p.insert(p.end(), q + pv.b, q + pv.e);
+        else if (w.err) break;
+        else if (sym(w.literal_same_length.at(i)) == 1) {
+          for (u32 j = 0; j < pv.e - pv.b && !w.err; ++j) {
+            // !!! Fix mixing literal contexts (id.cpp:525)
+            const u32 c = sym(w.literal.at(w.ctx_flags + (1ull << 32) + j));
+            p.push_back(c == 0 ? q[pv.b + j] : (u8)c);
+          }
+        } else {
+          for (u32 j = 0; !w.err; ++j) {
+            const u32 c = sym(w.literal.at(w.ctx_flags + j));
+            if (!c) break;
+            p.push_back((u8)c);
+            if (p.size() > ID_LINE_LIMIT) w.err = 5;
+          }
+        }
+      } else {
+        const int64_t v_prev = get_int(q, pv.b, pv.e), d0 = w.deltas[i];
+        u64 ctx = (u64)i << 40;
+        ctx += ilog2_(d0 < 0 ? 0ull - (u64)d0 : (u64)d0) << 31;
+        ctx += (u64)(d0 < 0) << 30;
+        ModelN &msz = w.numeric_size.at(ctx);
+        ModelN &msm = w.numeric_small.at(ctx);
+        int64_t delta;
+        u32 c = sym(msm);
+        if (w.err) break;
+        if (c < 3) delta = (int64_t)c - 1;
+        else {
+          int n_bytes = 0;
+          u64 ud = 0;
+          c = sym(msz);
+          if (w.err) break;
+          if (c <= 246) ud = (u64)((int64_t)c - 123);
+          else if (c == 247) { n_bytes = 2; ctx += 0x10; }
+          else if (c == 248) { n_bytes = 3; ctx += 0x20; }
+          else if (c == 249) { n_bytes = 4; ctx += 0x30; }
+          else if (c == 250) { n_bytes = 8; ctx += 0x40; }
+          else if (c == 251) { n_bytes = 2; ctx += 0x50; }
+          else if (c == 252) { n_bytes = 3; ctx += 0x60; }
+          else if (c == 253) { n_bytes = 4; ctx += 0x70; }
+          else if (c == 254) { n_bytes = 8; ctx += 0x80; }
+          for (int j = 0; j < n_bytes && !w.err; ++j) ud += (u64)sym(w.numeric_size.at(ctx + j)) << (8 * j);
+          if (c >= 251) ud = 0ull - ud;
+          delta = (int64_t)ud;
+        }
+        w.deltas[i] = delta;
+        store_int(p, (int64_t)((u64)delta + (u64)v_prev));
+      }
+      p.push_back(pv.sep);
+    }
+    if (w.err) return;
+    tokenize(p.data(), (u32)p.size(), w.tok_cur);
+  } else {
+    if (w.err) return;
+    w.ctx_flags = (w.ctx_flags << 1) & 0xff;
+    for (u32 i = 0;; ++i) {   // decode id plain
+      const u32 c = sym(w.plain.at(i));
+      if (w.err) return;
+      p.push_back((u8)c);
+      if (c == 0 || c == 0x0A) break;
+      if (p.size() > ID_LINE_LIMIT) { w.err = 5; return; }
+    }
+    tokenize(p.data(), (u32)p.size(), w.tok_cur);
+    w.deltas.assign(w.tok_cur.size(), 0);
+  }
+  w.tok_prev.swap(w.tok_cur);
+  w.id_prev.swap(w.id_cur);
+}
+// decompress_instrument, id.cpp:669-731: the instrument name and a line feed are appended to `out`
+void id_dec_instrument(IdWorker &w, Dec &d, std::vector<u8> &out) {
+  auto sym = [&](ModelN &m) -> u32 { const int x = m.decode(d); if (x < 0) { w.err = 7; return 0; } return (u32)x; };
+  const u32 flag = sym(w.mtf_flag);
+  if (w.err) return;
+  if (flag == 0) {   // new instrument name
+    id_dec_lossless(w, d);
+    if (w.err) return;
+    const std::vector<u8> &p = w.id_prev;
+    if (p.empty()) { w.err = 7; return; }
+    const std::string name(p.begin(), std::find(p.begin(), p.end(), (u8)0));
+    out.insert(out.end(), p.begin(), p.end());
+    out.back() = '\n';
+    w.mtf.insert(name);
+    return;
+  }
+  u32 code = 0;
+  if (flag < 3) code = flag - 1;
+  else if (flag < 10) code = sym(w.mtf_code[flag - 3]) + (2u << (flag - 3));
+  else
+    for (int i = 0; i < 4 && !w.err; ++i) code += sym(w.mtf_byte[i]) << (8 * i);
+  if (w.err) return;
+  if (code >= w.mtf.v.size()) { w.err = 7; return; }
+  if (code > 0) { std::string s = w.mtf.v[code]; w.mtf.v.erase(w.mtf.v.begin() + code); w.mtf.v.insert(w.mtf.v.begin(), s); }   // mtf.Insert(code)
+  const std::string &s = w.mtf.v[0];
+  out.insert(out.end(), s.begin(), s.end());
+  out.push_back('\n');
+}
 }  // namespace
 
 struct fqsx_meta { u32 T; std::vector<Worker> w; };
-struct fqsx_id { u32 T, mode; std::vector<IdWorker> w; };
+struct fqsx_id { u32 T, mode; std::vector<IdWorker> w; std::vector<u8> ids; std::vector<u64> off; };
 
 extern "C" {
 // Per-bin read order of `fqs e -om s`: std::sort with the comparator of CSortedFASTQFile::sort_reads
@@ -425,6 +561,77 @@ int fqsx_id_encode_block(fqsx_id *h, const uint8_t *ids, const uint64_t *id_off,
     streams[t] = h->w[t].enc.out.data();
     lens[t] = h->w[t].enc.out.size();
   }
+  return FQSX_OK;
+}
+
+// Inverse of fqsx_id_encode_block: CIdCompressor::Decompress / DecompressPE (id.cpp:182-228) for all T workers of one block.
+// The lines are what the reference's `fqs d` writes (numeric fields rebuilt by store_int, instrument mode: name + line feed).
+int fqsx_id_decode_block(fqsx_id *h, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                         const uint8_t **ids_out, const uint64_t **id_off_out) {
+  if (!h || !streams || !lens || !ids_out || !id_off_out || (paired && (n_reads & 1))) return FQSX_E_ARG;
+  const u64 T = h->T;
+  for (u64 t = 0; t < T; ++t) {
+    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
+    if (t) first &= ~1ull;
+    if (t + 1 < T) last &= ~1ull;
+    if (h->mode != 2 && first < last && (!streams[t] || lens[t] < 8)) return FQSX_E_ARG;   // sub_rc.h:114
+  }
+  auto run = [&](u64 t) {
+    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;
+    if (t) first &= ~1ull;
+    if (t + 1 < T) last &= ~1ull;
+    IdWorker &w = h->w[t];
+    w.reset_read_prev();
+    std::vector<u8> &out = w.dec_ids;
+    out.clear(); w.dec_len.clear();
+    if (first == last) return;
+    if (h->mode == 2) {   // decompress_none, id.cpp:486-492
+      for (u64 i = first; i < last; ++i) { out.push_back('@'); out.push_back('\n'); w.dec_len.push_back(2); }
+      return;
+    }
+    Dec d;
+    d.start(streams[t], lens[t]);
+    auto line = [&] {   // one id through the mode's decoder, appended to `out`
+      const size_t at = out.size();
+      if (h->mode == 0) { id_dec_lossless(w, d); if (!w.err) out.insert(out.end(), w.id_prev.begin(), w.id_prev.end()); }
+      else id_dec_instrument(w, d, out);
+      w.dec_len.push_back((u32)(out.size() - at));
+    };
+    for (u64 i = first; i < last && !w.err; i += paired ? 2 : 1) {
+      if (!paired || h->mode != 0) { line(); if (paired && !w.err) line(); continue; }
+      const int typical = w.pe_flags.at(w.ctx_pe_flags).decode(d);   // DecompressPE, id.cpp:195-228
+      if (typical < 0) { w.err = 7; break; }
+      w.ctx_pe_flags = ((w.ctx_pe_flags << 1) + (u64)typical) & 0xff;
+      line();
+      if (w.err) break;
+      if (typical) {   // typical PE ids: mate 2 is mate 1 with the byte before the line feed set to '2'
+        const size_t n = w.dec_len.back(), at = out.size();
+        const std::vector<u8> mate1(out.end() - n, out.end());
+        out.insert(out.end(), mate1.begin(), mate1.end());
+        if (n >= 2) out[at + n - 2] = '2';
+        w.dec_len.push_back((u32)n);
+      } else
+        line();
+    }
+  };
+  const u32 nthr = (u32)std::max<u64>(1, std::min<u64>(T, std::thread::hardware_concurrency()));
+  if (nthr <= 1 || n_reads < 4096) for (u64 t = 0; t < T; ++t) run(t);
+  else {
+    std::vector<std::thread> th;
+    for (u32 k = 0; k < nthr; ++k) th.emplace_back([&, k] { for (u64 t = k; t < T; t += nthr) run(t); });
+    for (auto &x : th) x.join();
+  }
+  h->ids.clear();
+  h->off.assign(1, 0);
+  for (u64 t = 0; t < T; ++t) {
+    if (h->w[t].err) return FQSX_E_DEVICE;   // malformed or truncated stream (the code the GPU decoder gives it)
+    h->ids.insert(h->ids.end(), h->w[t].dec_ids.begin(), h->w[t].dec_ids.end());
+    for (u32 n : h->w[t].dec_len) h->off.push_back(h->off.back() + n);
+  }
+  if (h->off.size() != (size_t)n_reads + 1) return FQSX_E_DEVICE;
+  h->ids.resize(h->ids.size() + 8);   // (never a null pointer for an empty block)
+  *ids_out = h->ids.data();
+  *id_off_out = h->off.data();
   return FQSX_OK;
 }
 }

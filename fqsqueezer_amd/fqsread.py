@@ -1,15 +1,18 @@
 """Read a `.fqs` file back: the bases and qualities of its reads, decoded on the GPU (codec.DnaCodec.decode_block,
 codec.QualCodec.decode_block) from the read lengths of the meta stream (codec.MetaCodec.decode_block, host).  Works on the
-files fqsfile writes and on those of the reference's `fqs e`.  The read-id stream is not decoded yet: a file that carries
-one is accepted and the stream is skipped; writing FASTQ text is left to the caller until ids can be restored."""
+files fqsfile writes and on those of the reference's `fqs e`.  decompress_reads gives lengths, bases and qualities (the id
+stream, if the file has one, is skipped); decompress_records also restores the read ids (codec.IdCodec.decode_block: the GPU id
+decoder on a stream of its own, the host decoder for files whose ids are beyond the kernel's staging limits) and
+decompress_fastq assembles the FASTQ text `fqs d` writes.  Command line: python -m fqsqueezer_amd.fqsread d in.fqs -out a.fq
+[-out2 b.fq]."""
 from __future__ import annotations
 
-from typing import Iterator, Optional, Tuple
+from typing import Iterator, List, Optional, Tuple, Union
 
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DnaCodec, MetaCodec, QualCodec
+from .codec import DnaCodec, FqsxError, IdCodec, MetaCodec, QualCodec
 
 
 def decompress_reads(data: bytes, device: int = 0, lib_path: Optional[str] = None) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
@@ -43,3 +46,159 @@ def decompress_reads(data: bytes, device: int = 0, lib_path: Optional[str] = Non
         meta.close()
         if qual is not None:
             qual.close()
+
+
+class _Ids:
+    """The id decoder of one file: the GPU kernel, or -- once the kernel reports a line beyond its staging limits -- the host
+    decoder, brought to the same point by replaying the id streams of the blocks read so far."""
+
+    def __init__(self, header: bytes, device: int, lib_path: Optional[str], gpu_ids: bool = True):
+        self.header, self.lib_path, self.paired = header, lib_path, header[5] >= 2
+        self.dec = IdCodec(header, lib_path=lib_path, device=device if gpu_ids else None)
+        self.on_gpu = gpu_ids
+        self.seen: List[tuple] = []   # (streams, n_reads) of the blocks decoded on the GPU so far
+        self.fell_back = False
+
+    def decode(self, streams, n_reads: int):
+        if self.on_gpu:
+            try:
+                out = self.dec.decode_block(streams, n_reads, self.paired)
+                self.seen.append((streams, n_reads))
+                return out
+            except FqsxError as e:
+                if not getattr(e, "staging", False):
+                    raise
+            self.dec.close()
+            self.dec = IdCodec(self.header, lib_path=self.lib_path)
+            self.on_gpu, self.fell_back = False, True
+            for st, n in self.seen:
+                self.dec.decode_block(st, n, self.paired)
+            self.seen = []
+        return self.dec.decode_block(streams, n_reads, self.paired)
+
+    def close(self):
+        self.dec.close()
+
+
+def decompress_records(data: bytes, device: int = 0, lib_path: Optional[str] = None, stats: Optional[dict] = None,
+                       gpu_ids: bool = True) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+    """decompress_reads with the read ids: per container block (read_len, bases, quals, ids uint8[], id_off uint64[n + 1]), the
+    id lines each with its line feed, as the reference's decoder writes them (numeric fields without leading zeros, instrument
+    mode: the instrument name only).  The id decoder runs on its own HIP stream beside the DNA and the quality decoder.
+    id_mode none: every id is '@' (id.cpp:486-492).  stats: receives 'id_host_fallback' and the id decoder's growth counters."""
+    from concurrent.futures import ThreadPoolExecutor
+    header, blocks = hp.parse_fqs(data)
+    threads, paired = header[4], header[5] >= 2
+    stored = hp.stored_streams(header)
+    dna = DnaCodec(header, device=device, lib_path=lib_path)
+    meta = MetaCodec(threads, lib_path=lib_path)
+    qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
+    idd = _Ids(header, device, lib_path, gpu_ids) if hp.STREAM_ID in stored else None
+    pool = ThreadPoolExecutor(max_workers=3)
+    try:
+        for g, blk in enumerate(blocks):
+            st = lambda sid: [blk.streams[w][sid] for w in range(threads)]   # noqa: E731
+            ji = pool.submit(idd.decode, st(hp.STREAM_ID), blk.n_reads) if idd is not None else None
+            read_len = meta.decode_block(st(hp.STREAM_META), blk.n_reads, paired)
+            off = np.zeros(blk.n_reads + 1, dtype=np.uint64)
+            off[1:] = np.cumsum(read_len, dtype=np.uint64)
+            jd = pool.submit(dna.decode_block, st(hp.STREAM_DNA), off, g)
+            jq = pool.submit(qual.decode_block, st(hp.STREAM_QUALITY), off) if qual is not None else None
+            quals = jq.result() if jq is not None else np.full(int(off[-1]), 33 + header[8], dtype=np.uint8)
+            if ji is not None:
+                ids, id_off = ji.result()
+            else:
+                ids = np.tile(np.frombuffer(b"@\n", dtype=np.uint8), blk.n_reads)
+                id_off = np.arange(blk.n_reads + 1, dtype=np.uint64) * np.uint64(2)
+            yield read_len, jd.result(), quals, ids, id_off
+    finally:
+        pool.shutdown(wait=True)
+        if stats is not None and idd is not None:   # (here, so that a caller that stops after the last block has them too)
+            stats["id_host_fallback"] = idd.fell_back
+            if idd.on_gpu:
+                stats["id_decoder"] = idd.dec.stats()
+        dna.close()
+        meta.close()
+        if qual is not None:
+            qual.close()
+        if idd is not None:
+            idd.close()
+
+
+def _scatter(dst: np.ndarray, at: np.ndarray, src: np.ndarray, off: np.ndarray) -> None:
+    """dst[at[i] : at[i] + len_i] = src[off[i] : off[i + 1]] for every i, without a loop over i"""
+    off = off.astype(np.int64)
+    n = int(off[-1] - off[0])
+    if n:
+        dst[np.repeat(at - off[:-1], np.diff(off)) + np.arange(off[0], off[0] + n, dtype=np.int64)] = src[off[0]:off[0] + n]
+
+
+def _take(src: np.ndarray, off: np.ndarray, idx: np.ndarray) -> np.ndarray:
+    """the segments src[off[i] : off[i + 1]], i in idx, back to back"""
+    ln = off[idx + 1] - off[idx]
+    at = np.zeros(len(idx) + 1, dtype=np.int64)
+    at[1:] = np.cumsum(ln)
+    return src[np.repeat(off[idx] - at[:-1], ln) + np.arange(int(at[-1]), dtype=np.int64)]
+
+
+def fastq_text(read_len: np.ndarray, bases: np.ndarray, quals: np.ndarray, ids: np.ndarray, id_off: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The FASTQ text of the reads of a block, in their order: per read id line + bases + "\n+\n" + qualities + "\n"
+    (application.cpp:871-889).  Returns (text uint8[], rec_off int64[n + 1])."""
+    L = read_len.astype(np.int64)
+    il = np.diff(id_off.astype(np.int64))
+    rec_off = np.zeros(len(L) + 1, dtype=np.int64)
+    rec_off[1:] = np.cumsum(il + 2 * L + 4)
+    out = np.empty(int(rec_off[-1]), dtype=np.uint8)
+    roff = np.zeros(len(L) + 1, dtype=np.int64)
+    roff[1:] = np.cumsum(L)
+    start = rec_off[:-1]
+    _scatter(out, start, ids, id_off)
+    _scatter(out, start + il, bases, roff)
+    sep = start + il + L
+    out[sep], out[sep + 1], out[sep + 2] = 10, ord("+"), 10
+    _scatter(out, sep + 3, quals, roff)
+    out[rec_off[1:] - 1] = 10
+    return out, rec_off
+
+
+def decompress_fastq(data: bytes, device: int = 0, lib_path: Optional[str] = None, stats: Optional[dict] = None,
+                     gpu_ids: bool = True) -> Union[bytes, Tuple[bytes, bytes]]:
+    """The FASTQ text `fqs d` writes for the file: bytes for a single-end file, (mate 1 file, mate 2 file) for a paired one
+    (workers in order, blocks in file order, mates alternately to the two outputs: application.cpp:871-889, 980-982)."""
+    if len(data) < 18 or data[0] != 17:
+        raise ValueError("not a .fqs file (header length byte)")
+    paired = data[6] >= 2   # header byte 5: the DNA mode
+    parts: Tuple[list, list] = ([], [])
+    for read_len, bases, quals, ids, id_off in decompress_records(data, device=device, lib_path=lib_path, stats=stats, gpu_ids=gpu_ids):
+        text, rec_off = fastq_text(read_len, bases, quals, ids, id_off)
+        if not paired:
+            parts[0].append(text.tobytes())
+            continue
+        for m in (0, 1):   # record i of the block goes to file i & 1
+            parts[m].append(_take(text, rec_off, np.arange(m, len(read_len), 2, dtype=np.int64)).tobytes())
+    return (b"".join(parts[0]), b"".join(parts[1])) if paired else b"".join(parts[0])
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m fqsqueezer_amd.fqsread", description="decompress a .fqs file to FASTQ on the GPU")
+    ap.add_argument("cmd", choices=["d"])
+    ap.add_argument("input")
+    ap.add_argument("-out", required=True)
+    ap.add_argument("-out2")
+    ap.add_argument("-device", type=int, default=0)
+    ap.add_argument("-lib", default=None, help="path of the library to load (default: the package's libfqsx.so)")
+    a = ap.parse_args(argv)
+    text = decompress_fastq(open(a.input, "rb").read(), device=a.device, lib_path=a.lib)
+    if isinstance(text, tuple):
+        if not a.out2:
+            ap.error("a paired file needs -out2")
+        open(a.out, "wb").write(text[0])
+        open(a.out2, "wb").write(text[1])
+    else:
+        open(a.out, "wb").write(text)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

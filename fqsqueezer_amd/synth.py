@@ -121,6 +121,27 @@ def synth_ids_varied(n: int, seed: int, mate: int = 0) -> list:
     return out
 
 
+def synth_ids_zeros(n: int, seed: int) -> list:
+    """Ids for the id *decoder*, which rebuilds a numeric field as decimal(previous value + delta) and so loses leading zeros:
+    zero-padded numeric fields, fields whose digit count changes (9 -> 10, 100 -> 99), an 11-digit run (literal by rule, kept
+    as it is) and empty tokens ('::')."""
+    rng = np.random.Generator(np.random.PCG64(seed ^ 0x2E05))
+    out = []
+    a, b = 7, 100
+    for i in range(n):
+        a += 1                                   # 8, 9, 10, ...: the digit count grows
+        b -= 1 if i % 3 == 0 else 0              # 100, 99, ...: and shrinks
+        if b < 1:
+            b = 120
+        run = 10_000_000_000 + int(rng.integers(0, 89_999_999_999))   # 11 digits
+        pad = int(rng.integers(0, 1000))
+        if i % 41 == 17:
+            out.append(b"@z%03d::%d::" % (pad, a))              # another shape: empty tokens next to the separators
+        else:
+            out.append(b"@zr.%03d:%d:%d::%011d:%05d/%02d" % (pad, a, b, run, i % 100000, 1 + i % 9))
+    return out
+
+
 def write_fastq(path: str, reads: np.ndarray, quals: np.ndarray | None = None,
                 seed: int = 0, mate: int = 1) -> None:
     n, L = reads.shape

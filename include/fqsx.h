@@ -274,6 +274,40 @@ int fqsx_idg_encode_block(fqsx_idg *, const uint8_t *ids, const uint64_t *id_off
                           const uint8_t **streams, uint64_t *lens);
 void fqsx_idg_destroy(fqsx_idg *);
 
+/* Decode one block's id streams: the inverse of fqsx_idg_encode_block / fqsx_id_encode_block, and what the reference's
+ * `fqs d` writes (CIdCompressor::Decompress / DecompressPE, fqs/id.cpp:182-228, 495-731) -- not necessarily what the encoder
+ * was given: a numeric field comes back as store_int(previous value + delta) (fqs/id.h:117-149: leading zeros are lost), in
+ * instrument mode only the instrument name and a line feed come back, id_mode none (host decoder only) gives "@\n".
+ * streams[w] / lens[w] = worker w's id stream of the block (host memory); n_reads from the container block; paired as in the
+ * encoder.  *ids_out = the block's id lines back to back, each including its line feed, in block order; *id_off_out =
+ * n_reads + 1 offsets into it.  Both are callee-owned until the next call.  A codec instance encodes or decodes a file, never both.
+ * Errors: a worker with reads to decode and a stream shorter than 8 bytes: FQSX_E_ARG; a malformed or truncated stream (a
+ * cumulative frequency at or above its model's total, a move-to-front code beyond the list, bytes wanted beyond the stream's
+ * end): FQSX_E_DEVICE -- nothing outside a worker's own output is ever written and the call always returns.  GPU decoder only:
+ * a line that would pass 1024 bytes, 128 tokens, an instrument name beyond 63 bytes or more than 4096 names per worker:
+ * FQSX_E_DEVICE ("staging sizes" in fqsx_last_error(); decode the file with fqsx_id_decode_block, which has no such limits).
+ * The GPU decoder cannot size its model tables and its output from its input: it snapshots them before a block and, when one
+ * runs out, restores the snapshot, doubles that capacity and runs the block again ("Reading a file back").
+ * FQSX_IDG_INIT=<n> in the environment at fqsx_idg_create: the first table capacities (slots, at least 16) and the first
+ * per-worker output capacity of the decoder (bytes, at least 64). */
+int fqsx_idg_decode_block(fqsx_idg *, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                          const uint8_t **ids_out, const uint64_t **id_off_out);
+int fqsx_id_decode_block(fqsx_id *, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                         const uint8_t **ids_out, const uint64_t **id_off_out);
+/* out[0] = blocks the decoder ran again, out[1] / out[2] / out[3] = growths of the small table, the big table and the decoder's
+ * output, out[4] / out[5] = slots per worker of the small and the big table, out[6] = output bytes per worker, out[7] = 0 */
+int fqsx_idg_stats(fqsx_idg *, uint64_t out[8]);
+/* out[4 * w + 0 / 1 / 2] = models in worker w's small table, in its big table, names in its move-to-front list after the last
+ * block (an encoder and a decoder that have seen the same blocks agree on them) */
+int fqsx_idg_state(fqsx_idg *, uint32_t *out);
+/* What the kernel reported in the last fqsx_idg_decode_block: 0 nothing, 5 = a line over 1024 bytes, over 128 tokens or an
+ * instrument name over 63 bytes, 6 = more than 4096 instrument names in a worker (5 and 6: the file is for fqsx_id_decode_block),
+ * 7 = malformed or truncated stream, 3 / 4 = an output / model table that a valid stream could not have filled */
+int fqsx_idg_error_kind(fqsx_idg *);
+/* Kernel timing of the id coder, as fqsx_qual_set_profiling / fqsx_qual_kernel_times: out[0] = milliseconds, out[1] = launches */
+int fqsx_idg_set_profiling(fqsx_idg *, int enable);
+int fqsx_idg_kernel_times(fqsx_idg *, double out[2]);
+
 /* Read order of `fqs e -om s` with the string work on the GPU.  Replaces preprocess_se
  * (fqs/application.cpp:349-412: 256 bins by the first four bases, N->T) plus CSortedFASTQFile::sort_reads on every
  * bin (fqs/io.h:499-528).  The GPU radix-sorts the reads by the comparator's keys and gives every read a dense

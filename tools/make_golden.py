@@ -41,6 +41,13 @@ Fixtures (data only -- inputs are re-generated deterministically by fqsqueezer_a
                             all four streams of every block + the file's SHA-256 (only with --only c22; ~10 min)
   c23_c4_q{8,4,2}_t4.fqs / c23_c5_pe_qo_t3.fqs + .json  files for the quality and meta decoders: lossy quality modes on the
                             c4 reads, lossless qualities on 1400 of the c5 pairs; SHA-256 of the quality lines `fqs d` writes for each
+  c24_*.fqs + .json         files for the id decoder and the FASTQ writer (--only c24), all -qm n: c24_c10_s_i_t4 (c10, -s -om s -im i,
+                            T=4), c24_c11_pe_o_o_t3 (c11 pairs, -p -om o -im o, T=3: typical and atypical mate ids), c24_c11_pe_s_i_t2
+                            (-p -om s -im i, T=2), c24_zeros_o_t2 (300 reads with synth_ids_zeros ids: leading zeros, digit counts that
+                            change, an 11-digit run, empty tokens; -s -om o -im o, T=2; its .json also holds the decoded id lines).
+                            Each .json: SHA-256 and read count of the FASTQ text `fqs d` writes (per mate file when paired) and,
+                            separately, the SHA-256 of its id lines.  JSON only for two committed files: c24_c10_full_o_t3.json
+                            (c10_full_o_t3.fqs) and c24_c4_ragged_o_t3.json (c4_ragged_o_t3.fqs: -im n -qm n)
 Usage: python tools/make_golden.py [--work /tmp/w] [--only c1|c2|c3]
 """
 import argparse, hashlib, json, os, subprocess, sys
@@ -245,6 +252,8 @@ def main():
         c22(a)
     if a.only in ("", "c23"):
         c23(a)
+    if a.only in ("", "c24"):
+        c24(a)
     if a.only in ("", "c3"):
         fq = os.path.join(a.work, "c3.fq")
         if not os.path.exists(fq):
@@ -433,6 +442,65 @@ def c23(a):
     (n1, s1), (n2, s2) = qsha(d1), qsha(d2)
     json.dump({"input": "c5, the first 1400 pairs (seeds 5 / 6)", "pairs": np_, "om": "s", "qm": "o", "threads": 3, "paired": True, "decoded_reads": n1 + n2,
                "decoded_quality_sha256": s1, "decoded_quality_sha256_mate2": s2}, open(os.path.join(GOLD, "c23_c5_pe_qo_t3.json"), "w"), indent=1)
+
+
+def c24(a):
+    """Files for the id decoder and the FASTQ writer: what `fqs d` writes for each (the whole text and its id lines)."""
+    from fqsqueezer_amd.synth import synth_ids_varied, synth_ids_zeros, synth_pairs, synth_quals
+
+    def fq_digest(path):
+        text = open(path, "rb").read()
+        lines = text.split(b"\n")[0::4]
+        lines = lines[:-1] if lines and lines[-1] == b"" else lines
+        return {"reads": len(lines), "fastq_sha256": hashlib.sha256(text).hexdigest(), "fastq_bytes": len(text),
+                "id_lines_sha256": hashlib.sha256(b"".join(x + b"\n" for x in lines)).hexdigest()}, lines
+
+    def decode(fqs, tag, paired, meta, keep_lines=False):
+        d1, d2 = os.path.join(a.work, tag + "_d1.fq"), os.path.join(a.work, tag + "_d2.fq")
+        subprocess.check_call([REF, "d", "-out", d1] + (["-out2", d2] if paired else []) + [fqs], stdout=subprocess.DEVNULL)
+        m1, lines = fq_digest(d1)
+        d = dict(meta, fqs=os.path.basename(fqs), paired=paired, mate1=m1)
+        if paired:
+            d["mate2"] = fq_digest(d2)[0]
+        if keep_lines:
+            d["id_lines"] = [x.decode("latin-1") for x in lines]
+        json.dump(d, open(os.path.join(GOLD, tag + ".json"), "w"), indent=1)
+        return lines
+
+    def encode(out, inputs, paired, om, im, t):
+        subprocess.check_call([REF, "e", "-p" if paired else "-s", "-om", om, "-t", str(t), "-gs", "1", "-qm", "n", "-im", im, "-v", "0",
+                               "-tmp", os.path.join(a.work, "tmpi_"), "-out", out] + inputs, stdout=subprocess.DEVNULL)
+
+    n = 3000
+    fq = os.path.join(a.work, "c24_c10.fq")
+    write_fq_ids(fq, synth_ids_varied(n, 10), synth_reads(n, 100, 80000, 10), synth_quals(n, 100, 10))
+    out = os.path.join(GOLD, "c24_c10_s_i_t4.fqs")
+    encode(out, [fq], False, "s", "i", 4)
+    decode(out, "c24_c10_s_i_t4", False, {"input": "c10 (3000 x 100bp, G=80kbp, seed 10, synth_ids_varied)", "om": "s", "qm": "n", "im": "i", "threads": 4})
+    np_ = 2000
+    r1, r2 = synth_pairs(np_, 100, 60000, 11)
+    f1, f2 = os.path.join(a.work, "c24_c11_1.fq"), os.path.join(a.work, "c24_c11_2.fq")
+    write_fq_ids(f1, synth_ids_varied(np_, 11, 1), r1, synth_quals(np_, 100, 11))
+    write_fq_ids(f2, synth_ids_varied(np_, 11, 2), r2, synth_quals(np_, 100, 12))
+    for tag, om, im, t in (("c24_c11_pe_o_o_t3", "o", "o", 3), ("c24_c11_pe_s_i_t2", "s", "i", 2)):
+        out = os.path.join(GOLD, tag + ".fqs")
+        encode(out, [f1, f2], True, om, im, t)
+        decode(out, tag, True, {"input": "c11 (2000 pairs x 100bp, G=60kbp, seed 11, synth_ids_varied mates 1/2)", "om": om, "qm": "n", "im": im, "threads": t})
+    nz = 300
+    ids = synth_ids_zeros(nz, 24)
+    fq = os.path.join(a.work, "c24_zeros.fq")
+    write_fq_ids(fq, ids, synth_reads(nz, 100, 20000, 24), synth_quals(nz, 100, 24))
+    out = os.path.join(GOLD, "c24_zeros_o_t2.fqs")
+    encode(out, [fq], False, "o", "o", 2)
+    lines = decode(out, "c24_zeros_o_t2", False, {"input": "300 x 100bp, G=20kbp, seed 24, synth_ids_zeros(300, 24)", "om": "o", "qm": "n", "im": "o", "threads": 2},
+                   keep_lines=True)
+    assert len(lines) == nz and any(x != y for x, y in zip(lines, ids)), "c24_zeros: the fixture has to exercise the decoder's lossy rule"
+    # digests only, for two files already committed
+    decode(os.path.join(GOLD, "c10_full_o_t3.fqs"), "c24_c10_full_o_t3", False, {"input": "c10_full_o_t3.fqs (-qm o -im o, T=3)"})
+    decode(os.path.join(GOLD, "c4_ragged_o_t3.fqs"), "c24_c4_ragged_o_t3", False, {"input": "c4_ragged_o_t3.fqs (-im n -qm n, T=3)"})
+    for f in os.listdir(GOLD):
+        if f.startswith("c24_"):
+            assert os.path.getsize(os.path.join(GOLD, f)) < 245705, f
 
 
 def c4_ref_decode(a, fq):
