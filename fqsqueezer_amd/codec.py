@@ -267,8 +267,9 @@ class IdCodec:
             L.fqsx_idg_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
             L.fqsx_idg_destroy.argtypes = [C.c_void_p]
             L.fqsx_idg_destroy.restype = None
-            if L.fqsx_idg_create(bytes(header), device, C.byref(self._h)):
-                raise FqsxError(f"fqsx_idg_create: {L.fqsx_last_error().decode()}")
+            rc = L.fqsx_idg_create(bytes(header), device, C.byref(self._h))
+            if rc:
+                raise FqsxError(f"fqsx_idg_create: {rc}: {L.fqsx_last_error().decode()}")
         elif L.fqsx_id_create(bytes(header), C.byref(self._h)):
             raise FqsxError("fqsx_id_create failed")
         self._streams = (C.c_void_p * self.T)()

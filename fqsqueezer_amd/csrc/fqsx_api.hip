@@ -79,16 +79,7 @@ FQ_KERNEL128 void k_insert_phase(DevCfg cfg, u64 nb_slots, u64 ns_slots) {
   // before the kernel ends (the phase's collective then orders the end of this kernel before anybody's next look-up)
   if (cfg.sys_scope) fq_release_system();
 }
-// gathers the T streams of the block into one contiguous buffer (one D2H transfer per block)
-FQ_KERNEL64 void k_compact_streams(DevCfg cfg, const u64 *lens, u8 *dst) {
-  const u32 tid = FQ_BLOCK;
-  u64 off = 0;
-  for (u32 t = 0; t < tid; ++t) off += lens[t];
-  const u64 n = lens[tid] <= cfg.out_cap ? lens[tid] : 0;
-  const u8 *src = cfg.out + (u64)tid * cfg.out_cap;
-  for (u64 i = FQ_LANE; i < n; i += FQ_WAVE) dst[off + i] = src[i];
-}
-// the same for the quality and id coders ([T][out_cap] streams, one workgroup per worker)
+// gathers the T streams of a block ([T][out_cap], one workgroup per worker) into one contiguous buffer: one D2H transfer per block
 FQ_KERNEL64 void k_compact_generic(const u8 *out, u64 out_cap, const u64 *lens, u8 *dst) {
   const u32 tid = FQ_BLOCK;
   u64 off = 0;
@@ -591,8 +582,8 @@ struct fqsx_dna : DevCtx {   // (a new fqsx_dna() starts with every field zero u
   DevCfg cfg;
   u32 T;
   // capacities (host mirror)
-  u64 gs_cap, gb_cap, ls_cap, lb_cap, ctx_cap, out_cap, gpe_cap, lpe_cap;
-  u32 pe_cap;
+  u64 gs_cap, gb_cap, ls_cap, lb_cap, ctx_cap, gpe_cap, lpe_cap;   // (output streams and triple lists: cfg.out_cap, cfg.pe_cap)
+  u32 pe_bkt_cap;     // triples per source cfg.pe_bkt holds (it follows cfg.pe_cap)
   bool paired;
   u32 mail_cap[3];
   u64 dev_bases_cap, dev_off_cap;
@@ -666,22 +657,14 @@ int d2h_small_end(fqsx_dna *c, void *h, u64 bytes) {
 
 #define REHASH_GRID FQ_GRID(2048)
 
-// The T streams a quality / id kernel left in [T][out_cap] (lengths lens_host, already read back and checked against out_cap)
-// -> one contiguous host buffer: a compaction launch and ONE transfer instead of a transfer and a synchronisation per worker
-// (d_compact / compact_cap: the caller's compaction buffer, grown here)
-int collect_streams(DevCtx *c, u8 *&d_compact, u64 &compact_cap, u32 T, const u8 *d_out, u64 out_cap, const u64 *d_lens,
+// The T streams a kernel left in [T][out_cap] (lengths lens_host, already read back and checked against out_cap) -> one
+// contiguous host buffer: a compaction launch and ONE transfer instead of a transfer and a synchronisation per worker
+// (d_compact: the caller's compaction buffer, which holds the streams' total)
+int collect_streams(DevCtx *c, u8 *d_compact, u32 T, const u8 *d_out, u64 out_cap, const u64 *d_lens,
                     const std::vector<u64> &lens_host, std::vector<u8> &h_out, const u8 **streams, u64 *lens) {
   int rc;
-  void *p = nullptr;
   u64 total = 0;
   for (u32 t = 0; t < T; ++t) total += lens_host[t];
-  if (total > compact_cap) {
-    dfree(c, d_compact);
-    d_compact = nullptr; compact_cap = 0;
-    if ((rc = dalloc(c, &p, total + total / 2 + 4096, false))) return rc;
-    d_compact = (u8 *)p;
-    compact_cap = total + total / 2 + 4096;
-  }
   h_out.resize(total ? total : 1);
   if (total) {
     LAUNCH(c, 2, k_compact_generic, T, 64, d_out, out_cap, d_lens, d_compact);
@@ -726,7 +709,7 @@ void mt_seed(u32 *s, u32 seed) {
   for (int i = 1; i < 624; ++i) s[i] = 1812433253u * (s[i - 1] ^ (s[i - 1] >> 30)) + (u32)i;
 }
 
-// (re)allocate a k-mer table of n_sub sub-tables with `cap` slots each, empty
+// a k-mer table of n_sub sub-tables with `cap` slots each, empty
 int ktab_alloc(fqsx_dna *c, KTab &t, u32 n_sub, u64 cap, u32 k, u32 cbits, bool with_filled) {
   void *p = nullptr;
   int rc = dalloc(c, &p, cap * n_sub * sizeof(u64), true);
@@ -869,6 +852,27 @@ int vtab_alloc(fqsx_dna *c, KTab &t, fqsx_dna::VmTab &v, u64 cap, u32 k, u32 cbi
   return rc ? rc : vtab_exchange(c, v);
 }
 
+// A worker-local table of a block (l_b, l_s, l_pe: cleared after every phase, so nothing is carried over) that has to hold
+// `need` slots per worker -- the dfit rule for a table of several arrays: handed back and forgotten before its successor is asked for
+int ltab_fit(fqsx_dna *c, KTab &t, u64 &cap, u64 need, u32 k, u32 cbits) {
+  if (need <= cap) return FQSX_OK;
+  dfree(c, t.slots);
+  t.slots = nullptr; cap = 0;
+  const int rc = ktab_alloc(c, t, c->T, need, k, cbits, false);
+  if (!rc) cap = need;
+  return rc;
+}
+int ptab_alloc(fqsx_dna *c, PTab &t, u32 n_sub, u64 cap, bool with_filled);
+int lpe_fit(fqsx_dna *c, PTab &t, u64 &cap, u64 need) {
+  if (need <= cap) return FQSX_OK;
+  dfree(c, t.key);
+  dfree(c, t.val);
+  t.key = t.val = nullptr; cap = 0;
+  const int rc = ptab_alloc(c, t, c->T, need, false);
+  if (!rc) cap = need;
+  return rc;
+}
+
 int grow_global(fqsx_dna *c, KTab &t, u64 &cap_field, u64 new_cap) {
   KTab n = t;
   int rc;
@@ -927,7 +931,7 @@ int ptab_alloc(fqsx_dna *c, PTab &t, u32 n_sub, u64 cap, bool with_filled) {
   int rc;
   if ((rc = dalloc(c, &p, cap * n_sub * sizeof(u64), true))) return rc;
   t.key = (u64 *)p;
-  if ((rc = dalloc(c, &p, cap * n_sub * sizeof(u64), true))) return rc;
+  if ((rc = dalloc(c, &p, cap * n_sub * sizeof(u64), true))) { dfree(c, t.key); t.key = nullptr; return rc; }
   t.val = (u64 *)p;
   t.cap_mask = cap - 1;
   t.stride = cap;
@@ -1010,7 +1014,9 @@ int grow_ctx(fqsx_dna *c, u64 new_cap) {
 int mail_alloc(fqsx_dna *c, u32 kind, u32 cap) {
   Mail &m = c->cfg.mail[kind];
   const u32 T = c->T;
-  if (m.list) { dfree(c, m.list); dfree(c, m.sorted); dfree(c, m.tile_hist); }
+  dfree(c, m.list); dfree(c, m.sorted); dfree(c, m.tile_hist);   // (three arrays: forgotten before their successors are asked for, as dfit)
+  m.list = m.sorted = nullptr; m.tile_hist = nullptr;
+  m.cap = m.n_tiles = 0; c->mail_cap[kind] = 0;
   cap = (cap + FQSX_TILE - 1) / FQSX_TILE * FQSX_TILE;
   void *p = nullptr;
   int rc;
@@ -1050,9 +1056,8 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
   u64 max_wbases = 0, max_seg_bases = 0, max_seg_reads = 0, max_wreads = 0;
   std::vector<u64> wbases(T);
   for (u32 t = 0; t < T; ++t) {
-    u64 first = (u64)t * n_reads / T, last = ((u64)t + 1) * n_reads / T;
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     wbases[t] = h_off[last] - h_off[first];
     max_wbases = std::max(max_wbases, wbases[t]);
     max_wreads = std::max(max_wreads, last - first);
@@ -1060,7 +1065,7 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
     for (u64 seg = 0; seg <= S; ++seg) {
       u64 stop = last;
       if (seg < S) {
-        const u64 ns = (seg + 1) * (last - first) / (S + 1) + first;
+        const u64 ns = segment_synchro(seg, S, first, last);
         if (!c->paired) stop = ns + 1;
         else { u64 i = cur; if (i < ns) i += (ns - i + 1) & ~1ull; stop = i + 2; }
       }
@@ -1077,62 +1082,30 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
   if (c->paired && (n_reads & 1)) { g_err = "paired-end blocks need an even number of reads"; return FQSX_E_ARG; }
   // ---- per-block buffers
   u64 need_out = max_wbases + 16 * max_wreads + 1024;
-  if (need_out > c->out_cap) {
-    if (cfg.out) dfree(c, cfg.out);
-    c->out_cap = pow2_at_least(need_out);
-    if ((rc = dalloc(c, &p, c->out_cap * T, false))) return rc;
-    cfg.out = (u8 *)p;
-    cfg.out_cap = c->out_cap;
-  }
+  if ((rc = dfit(c, cfg.out, cfg.out_cap, need_out, pow2_at_least(need_out), T))) return rc;
   const u64 mail_entries[3] = {2 * max_seg_bases + 2 * max_seg_reads, max_seg_bases, 2 * max_seg_bases};
   for (u32 k = 0; k < 3; ++k) {
     u64 need = mail_entries[k] + 64;
     if (need > c->mail_cap[k] && (rc = mail_alloc(c, k, (u32)(need + need / 4)))) return rc;
   }
   u64 need_lb = pow2_at_least(4 * max_seg_bases + 64), need_ls = pow2_at_least(2 * max_seg_bases + 64);
-  if (need_lb > c->lb_cap) {
-    dfree(c, cfg.l_b.slots);
-    if ((rc = ktab_alloc(c, cfg.l_b, T, need_lb, cfg.bmer, 6, false))) return rc;
-    c->lb_cap = need_lb;
-  }
-  if (need_ls > c->ls_cap) {
-    dfree(c, cfg.l_s.slots);
-    if ((rc = ktab_alloc(c, cfg.l_s, T, need_ls, cfg.smer, 12, false))) return rc;
-    c->ls_cap = need_ls;
-  }
+  if ((rc = ltab_fit(c, cfg.l_b, c->lb_cap, need_lb, cfg.bmer, 6))) return rc;
+  if ((rc = ltab_fit(c, cfg.l_s, c->ls_cap, need_ls, cfg.smer, 12))) return rc;
   u64 need_lpe = 0;
   if (c->paired) {
     const u64 seg_pairs = max_seg_reads / 2 + 1;
     const u64 need_list = 14 * seg_pairs + 16;
-    if (need_list > c->pe_cap) {
-      if (cfg.pe_list) dfree(c, cfg.pe_list);
-      c->pe_cap = (u32)(need_list + need_list / 4);
-      if ((rc = dalloc(c, &p, (u64)T * c->pe_cap * 3 * sizeof(u64), false))) return rc;
-      cfg.pe_list = (u64 *)p;
-      cfg.pe_cap = c->pe_cap;
-      if (cfg.pe_bkt) dfree(c, cfg.pe_bkt);
-      if ((rc = dalloc(c, &p, (u64)T * c->pe_cap * 3 * sizeof(u64), false))) return rc;
-      cfg.pe_bkt = (u64 *)p;
-    }
+    const u32 list_cap = (u32)(need_list + need_list / 4);
+    if ((rc = dfit(c, cfg.pe_bkt, c->pe_bkt_cap, need_list, list_cap, (u64)T * 3 * sizeof(u64)))) return rc;
+    if ((rc = dfit(c, cfg.pe_list, cfg.pe_cap, need_list, list_cap, (u64)T * 3 * sizeof(u64)))) return rc;
     need_lpe = pow2_at_least(2 * 14 * seg_pairs + 64);
-    if (need_lpe > c->lpe_cap) {
-      dfree(c, cfg.l_pe.key);
-      dfree(c, cfg.l_pe.val);
-      if ((rc = ptab_alloc(c, cfg.l_pe, T, need_lpe, false))) return rc;
-      c->lpe_cap = need_lpe;
-    }
+    if ((rc = lpe_fit(c, cfg.l_pe, c->lpe_cap, need_lpe))) return rc;
     cfg.l_pe.cap_mask = need_lpe - 1;
     cfg.l_pe.stride = need_lpe;
     // mates longer than the LDS staging size: three scratch lines per worker (codes of either mate, reverse-complement line)
     u64 max_len = 0;
     for (u32 i = 0; i < n_reads; ++i) max_len = std::max(max_len, h_off[i + 1] - h_off[i]);
-    if (!decode && max_len > FQSX_RD_LDS && max_len + 128 > cfg.pe_scr_cap) {
-      if (cfg.pe_scr) dfree(c, cfg.pe_scr);
-      const u64 cap = (max_len + max_len / 4 + 128 + 63) & ~63ull;
-      if ((rc = dalloc(c, &p, (u64)T * 3 * cap, true))) return rc;
-      cfg.pe_scr = (u8 *)p;
-      cfg.pe_scr_cap = cap;
-    }
+    if (!decode && max_len > FQSX_RD_LDS && (rc = dfit(c, cfg.pe_scr, cfg.pe_scr_cap, max_len + 128, (max_len + max_len / 4 + 128 + 63) & ~63ull, (u64)T * 3, true))) return rc;
   }
   // active geometry of the local tables for this block (cleared after every phase)
   cfg.l_b.nb = need_lb / FQSX_BKT; cfg.l_b.stride = need_lb;
@@ -1156,21 +1129,9 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
     u64 max_len = 0;
     for (u32 i = 0; i < n_reads; ++i) max_len = std::max(max_len, h_off[i + 1] - h_off[i]);
     const u64 need_in = doff[T] + 64, need_out = h_off[n_reads] + 64, need_sc = max_len + 64;
-    if (need_in > c->din_cap) {
-      dfree(c, (void *)cfg.din);
-      if ((rc = dalloc(c, &p, need_in + need_in / 4, false))) return rc;
-      cfg.din = (const u8 *)p; c->din_cap = need_in + need_in / 4;
-    }
-    if (need_out > c->dout_cap) {
-      dfree(c, cfg.dout);
-      if ((rc = dalloc(c, &p, need_out + need_out / 4, false))) return rc;
-      cfg.dout = (u8 *)p; c->dout_cap = need_out + need_out / 4;
-    }
-    if (need_sc > cfg.dcap) {
-      dfree(c, cfg.dscratch);
-      if ((rc = dalloc(c, &p, (u64)T * 2 * (need_sc + need_sc / 4), false))) return rc;
-      cfg.dscratch = (u8 *)p; cfg.dcap = need_sc + need_sc / 4;
-    }
+    if ((rc = dfit(c, cfg.din, c->din_cap, need_in, need_in + need_in / 4, 1))) return rc;
+    if ((rc = dfit(c, cfg.dout, c->dout_cap, need_out, need_out + need_out / 4, 1))) return rc;
+    if ((rc = dfit(c, cfg.dscratch, cfg.dcap, need_sc, need_sc + need_sc / 4, (u64)T * 2))) return rc;
     if (!cfg.din_off && (rc = dalloc(c, &p, ((u64)T + 1) * sizeof(u64), false))) return rc;
     if (!cfg.din_off) cfg.din_off = (const u64 *)p;
     std::vector<u8> flat(doff[T] ? doff[T] : 1);
@@ -1311,7 +1272,6 @@ int block_finish(fqsx_dna *c, const u64 *h_off, const u8 **streams, u64 *lens, u
   const bool decode = c->cur_decode;
   DevCfg &cfg = c->cfg;
   int rc;
-  void *p = nullptr;
   if (decode) {
     u32 derr = 0;
     if ((rc = d2h_sync(c, &derr, cfg.err, sizeof(u32)))) return rc;
@@ -1341,25 +1301,11 @@ int block_finish(fqsx_dna *c, const u64 *h_off, const u8 **streams, u64 *lens, u
   }
   u64 total = 0;
   for (u32 t = 0; t < T; ++t) {
-    if (c->h_lens[t] > c->out_cap) { g_err = "stream overflow"; return FQSX_E_DEVICE; }
+    if (c->h_lens[t] > cfg.out_cap) { g_err = "stream overflow"; return FQSX_E_DEVICE; }
     total += c->h_lens[t];
   }
-  if (total > c->compact_cap) {
-    dfree(c, c->d_compact);
-    if ((rc = dalloc(c, &p, total + total / 2 + 4096, false))) return rc;
-    c->d_compact = (u8 *)p;
-    c->compact_cap = total + total / 2 + 4096;
-  }
-  LAUNCH(c, 2, k_compact_streams, T, 64, cfg, (const u64 *)c->d_lens, c->d_compact);
-  c->h_out.resize(total ? total : 1);
-  if (total && (rc = d2h_sync(c, c->h_out.data(), c->d_compact, total))) return rc;
-  u64 pos = 0;
-  for (u32 t = 0; t < T; ++t) {
-    streams[t] = c->h_out.data() + pos;
-    lens[t] = c->h_lens[t];
-    pos += c->h_lens[t];
-  }
-  return FQSX_OK;
+  if ((rc = dfit(c, c->d_compact, c->compact_cap, total, total + total / 2 + 4096, 1))) return rc;
+  return collect_streams(c, c->d_compact, T, cfg.out, cfg.out_cap, c->d_lens, c->h_lens, c->h_out, streams, lens);
 }
 
 // decode: dec_streams/dec_lens (host) are the T input streams, bases_out (host) receives the block
@@ -1479,7 +1425,6 @@ int create_impl(fqsx_dna *c, const u8 *h) {
   }
   c->paired = cfg.mode >= 2;
   c->gpe_cap = c->lpe_cap = 0;
-  c->pe_cap = 0;
   if (c->paired) {  // ht_pe_mers (application.cpp:89) and ht_pe_mers_local (dna.cpp:105-107)
     c->gpe_cap = pow2_at_least(std::max<u64>(1024, (1ull << 20) / T));
     if (const char *e = getenv("FQSX_PTAB_INIT")) c->gpe_cap = pow2_at_least(std::max<u64>(64, strtoull(e, nullptr, 10)));   // (tests: growth from a tiny pair table)
@@ -1583,20 +1528,9 @@ int fqsx_dna_encode_block(fqsx_dna *c, const uint8_t *bases, const uint64_t *off
   if (!c || !bases || !off || !streams || !lens) { g_err = "null argument"; return FQSX_E_ARG; }
   DEVCHK(dev_enter(c));
   int rc;
-  void *p = nullptr;
   u64 nb = off[n_reads] + 64, no = ((u64)n_reads + 1) * sizeof(u64);
-  if (nb > c->dev_bases_cap) {
-    dfree(c, c->d_bases);
-    if ((rc = dalloc(c, &p, nb + nb / 4, false))) return rc;
-    c->d_bases = (u8 *)p;
-    c->dev_bases_cap = nb + nb / 4;
-  }
-  if (no > c->dev_off_cap) {
-    dfree(c, c->d_off);
-    if ((rc = dalloc(c, &p, no + no / 4, false))) return rc;
-    c->d_off = (u64 *)p;
-    c->dev_off_cap = no + no / 4;
-  }
+  if ((rc = dfit(c, c->d_bases, c->dev_bases_cap, nb, nb + nb / 4, 1))) return rc;
+  if ((rc = dfit(c, c->d_off, c->dev_off_cap, no, no + no / 4, 1))) return rc;
   if ((rc = h2d(c, c->d_bases, bases, off[n_reads]))) return rc;
   if ((rc = h2d(c, c->d_off, off, no))) return rc;
   return encode_block_impl(c, c->d_bases, c->d_off, off, n_reads, generation, streams, lens);
@@ -1607,14 +1541,8 @@ int fqsx_dna_decode_block(fqsx_dna *c, const uint8_t *const *streams, const uint
   if (!c || !streams || !lens || !off || !bases_out) { g_err = "null argument"; return FQSX_E_ARG; }
   DEVCHK(dev_enter(c));
   int rc;
-  void *p = nullptr;
   u64 no = ((u64)n_reads + 1) * sizeof(u64);
-  if (no > c->dev_off_cap) {
-    dfree(c, c->d_off);
-    if ((rc = dalloc(c, &p, no + no / 4, false))) return rc;
-    c->d_off = (u64 *)p;
-    c->dev_off_cap = no + no / 4;
-  }
+  if ((rc = dfit(c, c->d_off, c->dev_off_cap, no, no + no / 4, 1))) return rc;
   if ((rc = h2d(c, c->d_off, off, no))) return rc;
   return encode_block_impl(c, nullptr, c->d_off, off, n_reads, generation, nullptr, nullptr, streams, lens, bases_out);
 }
@@ -1776,17 +1704,7 @@ int fqsx_shard_finish_block(fqsx_dna *c, const uint64_t *h_off, const uint8_t **
 
 // ---- the phase loop inside the library ------------------------------------------------------------------------------
 namespace {
-int xbuf_fit(fqsx_dna *c, u64 *&buf, u64 &cap, u64 words) {
-  if (words <= cap) return FQSX_OK;
-  void *p = nullptr;
-  if (buf) dfree(c, buf);
-  const u64 ncap = words + words / 4 + 1024;
-  int rc = dalloc(c, &p, ncap * sizeof(u64), false);
-  if (rc) { buf = nullptr; cap = 0; return rc; }
-  buf = (u64 *)p;
-  cap = ncap;
-  return FQSX_OK;
-}
+int xbuf_fit(fqsx_dna *c, u64 *&buf, u64 &cap, u64 words) { return dfit(c, buf, cap, words, words + words / 4 + 1024, sizeof(u64)); }
 // A collective that fails is not something the ranks can agree on any more: the transport is told to give up (RCCL:
 // ncclCommAbort, so that this rank's part of a pending collective does not keep the others' kernels spinning) and the call fails.
 #define COMMCHK(x, what) do { if ((x) != 0) { if (g_err.empty() || g_err.find(what) == std::string::npos) g_err = std::string(what) + " failed"; if (c->comm.abort) c->comm.abort(c->comm.ctx); return FQSX_E_HIP; } } while (0)
@@ -2338,10 +2256,44 @@ FQ_KERNEL void k_qual_rehash(const u64 *o, u64 ocap_mask, u64 *n, u64 ncap_mask,
   }
 }
 
+// ---- host glue the side-stream codecs (quality, ids) share
+namespace {
+// A per-worker hash table ([T][cap] slots of slot_u64 words, key ~0 = empty: quality contexts, id models) into one of ncap slots
+// per worker.  The old table stays in place until the new one is filled: a step that fails changes nothing.
+int hash_tab_regrow(DevCtx *c, u64 *&tab, u64 &cap, u64 &mask, u64 ncap, u32 T, u32 slot_u64) {
+  const u64 bytes = ncap * T * slot_u64 * sizeof(u64);
+  void *nt = nullptr;
+  int rc = dalloc(c, &nt, bytes, false);
+  if (rc) return rc;
+  if (!(rc = dfill_ff(c, nt, bytes)))
+    rc = dev_launch(c, 2, false, [&] { DEV_KERNEL(c, k_qual_rehash, REHASH_GRID, 256, (const u64 *)tab, mask, (u64 *)nt, ncap - 1, T, slot_u64); });
+  if (!rc) rc = dev_sync(c);
+  if (rc) { dfree(c, nt); return rc; }
+  dfree(c, tab);
+  tab = (u64 *)nt; cap = ncap; mask = ncap - 1;
+  return FQSX_OK;
+}
+// The T input streams of a decoder -> h_in: [T] byte offsets, [T] lengths (a null stream counts as empty), then the streams back
+// to back, every start 8-byte aligned: what goes up in one transfer.  Returns the words in use (h_in holds one more).
+u64 pack_streams(u64 T, const u8 *const *streams, const u64 *lens, std::vector<u64> &h_in) {
+  u64 in_words = 2 * T;
+  h_in.assign(2 * T, 0);
+  for (u64 t = 0; t < T; ++t) {
+    h_in[t] = (in_words - 2 * T) * 8;
+    h_in[T + t] = streams[t] ? lens[t] : 0;
+    in_words += (h_in[T + t] + 7) / 8;
+  }
+  h_in.resize(in_words + 1, 0);
+  for (u64 t = 0; t < T; ++t)
+    if (h_in[T + t]) memcpy((u8 *)(h_in.data() + 2 * T) + h_in[t], streams[t], h_in[T + t]);
+  return in_words;
+}
+}  // namespace
+
 struct fqsx_qual : DevCtx {
   QualCfg cfg;
   u32 T;
-  u64 cap, out_cap, q_cap, off_cap;
+  u64 cap, q_cap, off_cap;   // (the output streams: cfg.out_cap)
   u8 *d_q;
   u64 *d_off;
   u8 *d_compact;   // the T streams back to back (collect_streams)
@@ -2428,6 +2380,15 @@ int fqsx_qual_create(const uint8_t *h, int device, fqsx_qual **out) {
 
 static int qual_encode_impl(fqsx_qual *q, const uint8_t *quals, const uint8_t *d_quals, const uint64_t *d_off_in, const uint64_t *off,
                             uint32_t n_reads, const uint8_t **streams, uint64_t *lens);
+// the context table before a launch in which a worker codes up to max_w symbols: every symbol can create one context
+static int qual_fit_table(fqsx_qual *q, u64 max_w) {
+  QualCfg &cfg = q->cfg;
+  DEVCHK(d2h_sync(q, q->h_filled.data(), cfg.filled, q->T * sizeof(u32)));
+  u64 need = 0;
+  for (u32 t = 0; t < q->T; ++t) need = std::max<u64>(need, (u64)q->h_filled[t] + max_w + 64);
+  if (need * 2 <= q->cap) return FQSX_OK;
+  return hash_tab_regrow(q, cfg.tab, q->cap, cfg.cap_mask, pow2_at_least(need * 2), q->T, cfg.slot_u64);
+}
 int fqsx_qual_encode_block(fqsx_qual *q, const uint8_t *quals, const uint64_t *off, uint32_t n_reads, const uint8_t **streams,
                            uint64_t *lens) {
   if (!q || !quals || !off || !streams || !lens) { g_err = "null argument"; return FQSX_E_ARG; }
@@ -2446,41 +2407,23 @@ static int qual_encode_impl(fqsx_qual *q, const uint8_t *quals, const uint8_t *d
   const u32 T = q->T;
   DEVCHK(dev_enter(c));
   int rc;
-  void *p = nullptr;
   u64 max_w = 0;
   for (u32 t = 0; t < T; ++t) {
-    u64 first = (u64)t * n_reads / T, last = ((u64)t + 1) * n_reads / T;
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     max_w = std::max(max_w, off[last] - off[first]);
   }
-  // context table: every symbol can create one context
-  if ((rc = d2h_sync(c, q->h_filled.data(), cfg.filled, T * sizeof(u32)))) return rc;
-  u64 need = 0;
-  for (u32 t = 0; t < T; ++t) need = std::max<u64>(need, (u64)q->h_filled[t] + max_w + 64);
-  if (need * 2 > q->cap) {
-    const u64 ncap = pow2_at_least(need * 2);
-    if ((rc = dalloc(c, &p, ncap * T * cfg.slot_u64 * sizeof(u64), false))) return rc;
-    if ((rc = dfill_ff(c, p, ncap * T * cfg.slot_u64 * sizeof(u64)))) return rc;
-    LAUNCH(c, 2, k_qual_rehash, REHASH_GRID, 256, (const u64 *)cfg.tab, cfg.cap_mask, (u64 *)p, ncap - 1, T, cfg.slot_u64);
-    DEVCHK(dev_sync(c));
-    dfree(c, cfg.tab);
-    cfg.tab = (u64 *)p;
-    cfg.cap_mask = ncap - 1;
-    q->cap = ncap;
-  }
+  if ((rc = qual_fit_table(q, max_w))) return rc;
   const u64 need_out = (max_w * 2 + 4096 + 7) & ~7ull, nq = off[n_reads] + 64, no = ((u64)n_reads + 1) * sizeof(u64);
-  if (need_out > q->out_cap) {
-    dfree(c, cfg.out);
-    if ((rc = dalloc(c, &p, need_out * T, false))) return rc;
-    cfg.out = (u8 *)p; cfg.out_cap = q->out_cap = need_out;
-  }
+  if ((rc = dfit(c, cfg.out, cfg.out_cap, need_out, need_out, T))) return rc;
+  // (every allocation of the block before the launch: a call that fails for memory has not moved the models and can be repeated)
+  if ((rc = dfit(c, q->d_compact, q->compact_cap, cfg.out_cap * T, cfg.out_cap * T, 1))) return rc;
   if (d_quals) {
     cfg.quals = d_quals;
     cfg.off = d_off_in;
   } else {
-    if (nq > q->q_cap) { dfree(c, q->d_q); if ((rc = dalloc(c, &p, nq + nq / 4, false))) return rc; q->d_q = (u8 *)p; q->q_cap = nq + nq / 4; }
-    if (no > q->off_cap) { dfree(c, q->d_off); if ((rc = dalloc(c, &p, no + no / 4, false))) return rc; q->d_off = (u64 *)p; q->off_cap = no + no / 4; }
+    if ((rc = dfit(c, q->d_q, q->q_cap, nq, nq + nq / 4, 1))) return rc;
+    if ((rc = dfit(c, q->d_off, q->off_cap, no, no + no / 4, 1))) return rc;
     if ((rc = h2d(c, q->d_q, quals, off[n_reads]))) return rc;
     if ((rc = h2d(c, q->d_off, off, no))) return rc;
     cfg.quals = q->d_q;
@@ -2492,7 +2435,7 @@ static int qual_encode_impl(fqsx_qual *q, const uint8_t *quals, const uint8_t *d
   if (err) { g_err = "device error " + std::to_string(err) + " in the quality kernel"; return FQSX_E_DEVICE; }
   for (u32 t = 0; t < T; ++t)
     if (q->h_lens[t] > cfg.out_cap) { g_err = "quality stream overflow"; return FQSX_E_DEVICE; }
-  return collect_streams(c, q->d_compact, q->compact_cap, T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
+  return collect_streams(c, q->d_compact, T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
 }
 
 // Inverse of qual_encode_impl: the T streams go up back to back in one transfer (behind their offsets and lengths, every
@@ -2505,44 +2448,22 @@ static int qual_decode_impl(fqsx_qual *q, const uint8_t *const *streams, const u
   for (u32 i = 0; i < n_reads; ++i)
     if (off[i + 1] < off[i] || off[i + 1] - off[i] >= (1ull << 24)) { g_err = "read offsets do not ascend or a read of 2^24 symbols or more"; return FQSX_E_ARG; }
   if (off[0] != 0) { g_err = "read offsets must start at 0"; return FQSX_E_ARG; }
-  u64 max_w = 0, in_words = 2 * (u64)T;
-  q->h_in.assign(2 * (u64)T, 0);
+  u64 max_w = 0;
   for (u32 t = 0; t < T; ++t) {
-    u64 first = (u64)t * n_reads / T, last = ((u64)t + 1) * n_reads / T;
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     const u64 n_sym = off[last] - off[first];
     max_w = std::max(max_w, n_sym);
     if (n_sym && (lens[t] < 8 || !streams[t])) { g_err = "quality stream of a worker shorter than 8 bytes"; return FQSX_E_ARG; }   // sub_rc.h:114
-    q->h_in[t] = (in_words - 2 * (u64)T) * 8;
-    q->h_in[T + t] = streams[t] ? lens[t] : 0;
-    in_words += (q->h_in[T + t] + 7) / 8;
   }
-  q->h_in.resize(in_words + 1, 0);
-  for (u32 t = 0; t < T; ++t)
-    if (q->h_in[T + t]) memcpy((u8 *)(q->h_in.data() + 2 * (u64)T) + q->h_in[t], streams[t], q->h_in[T + t]);
+  const u64 in_words = pack_streams(T, streams, lens, q->h_in);
   DEVCHK(dev_enter(c));
   int rc;
-  void *p = nullptr;
-  // context table: every symbol can create one context
-  if ((rc = d2h_sync(c, q->h_filled.data(), cfg.filled, T * sizeof(u32)))) return rc;
-  u64 need = 0;
-  for (u32 t = 0; t < T; ++t) need = std::max<u64>(need, (u64)q->h_filled[t] + max_w + 64);
-  if (need * 2 > q->cap) {
-    const u64 ncap = pow2_at_least(need * 2);
-    if ((rc = dalloc(c, &p, ncap * T * cfg.slot_u64 * sizeof(u64), false))) return rc;
-    if ((rc = dfill_ff(c, p, ncap * T * cfg.slot_u64 * sizeof(u64)))) return rc;
-    LAUNCH(c, 2, k_qual_rehash, REHASH_GRID, 256, (const u64 *)cfg.tab, cfg.cap_mask, (u64 *)p, ncap - 1, T, cfg.slot_u64);
-    DEVCHK(dev_sync(c));
-    dfree(c, cfg.tab);
-    cfg.tab = (u64 *)p;
-    cfg.cap_mask = ncap - 1;
-    q->cap = ncap;
-  }
+  if ((rc = qual_fit_table(q, max_w))) return rc;
   const u64 ni = (in_words + 1) * sizeof(u64), nout = (off[n_reads] + 64 + 7) & ~7ull, no = ((u64)n_reads + 1) * sizeof(u64);
-  if (ni > q->in_cap) { dfree(c, q->d_in); if ((rc = dalloc(c, &p, ni + ni / 4, false))) return rc; q->d_in = (u8 *)p; q->in_cap = ni + ni / 4; }
-  if (nout > q->dout_cap) { dfree(c, q->d_dout); if ((rc = dalloc(c, &p, nout + nout / 4, false))) return rc; q->d_dout = (u8 *)p; q->dout_cap = nout + nout / 4; }
-  if (no > q->roff_cap) { dfree(c, q->d_roff); if ((rc = dalloc(c, &p, no + no / 4, false))) return rc; q->d_roff = (u64 *)p; q->roff_cap = no + no / 4; }
+  if ((rc = dfit(c, q->d_in, q->in_cap, ni, ni + ni / 4, 1))) return rc;
+  if ((rc = dfit(c, q->d_dout, q->dout_cap, nout, nout + nout / 4, 1))) return rc;
+  if ((rc = dfit(c, q->d_roff, q->roff_cap, no, no + no / 4, 1))) return rc;
   if ((rc = h2d(c, q->d_in, q->h_in.data(), ni))) return rc;
   if ((rc = h2d(c, q->d_roff, off, no))) return rc;
   cfg.off = q->d_roff;
@@ -2607,7 +2528,7 @@ FQ_KERNEL64 void k_id_init_fixed(IdCfg cfg) {
 struct fqsx_idg : DevCtx {
   IdCfg cfg;
   u32 T;
-  u64 small_cap, big_cap, out_cap, ids_cap, off_cap;
+  u64 small_cap, big_cap, ids_cap, off_cap;   // (the output streams / the decoder's output: cfg.out_cap)
   u8 *d_ids;
   u64 *d_off;
   u8 *d_compact;   // the T streams back to back (collect_streams)
@@ -2695,14 +2616,12 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
   const u64 T = q->T;
   DEVCHK(dev_enter(c));
   int rc;
-  void *p = nullptr;
   // ---- table sizes: a worker creates at most one big model per byte it codes plus nine per numeric token, and three small
   // ones per token plus two per read; tokens end at separators, which are counted here
   u64 max_bytes = 0, max_big = 0, max_small = 0;
   for (u64 t = 0; t < T; ++t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     const u64 nb = off[last] - off[first];
     u64 sep = 0;
     for (u64 i = off[first]; i < off[last]; ++i) {
@@ -2713,28 +2632,14 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
     max_big = std::max(max_big, (u64)q->h_state[4 * t + 1] + nb + 9 * sep + 2 * (last - first) + 16);
     max_small = std::max(max_small, (u64)q->h_state[4 * t] + 3 * sep + 4 * (last - first) + 16);
   }
-  auto regrow = [&](u64 *&tab, u64 &cap, u64 &mask, u64 need, u32 slot_u64) -> int {
-    if (need * 10 < cap * 8) return FQSX_OK;
-    const u64 ncap = pow2_at_least(need * 2);
-    int r = dalloc(c, &p, ncap * T * slot_u64 * sizeof(u64), false);
-    if (r) return r;
-    if ((r = dfill_ff(c, p, ncap * T * slot_u64 * sizeof(u64)))) return r;
-    LAUNCH(c, 2, k_qual_rehash, REHASH_GRID, 256, (const u64 *)tab, mask, (u64 *)p, ncap - 1, (u32)T, slot_u64);
-    DEVCHK(dev_sync(c));
-    dfree(c, tab);
-    tab = (u64 *)p; cap = ncap; mask = ncap - 1;
-    return FQSX_OK;
-  };
-  if ((rc = regrow(cfg.small, q->small_cap, cfg.small_mask, max_small, 2))) return rc;
-  if ((rc = regrow(cfg.big, q->big_cap, cfg.big_mask, max_big, IDK_BIG_U64))) return rc;
+  if (max_small * 10 >= q->small_cap * 8 && (rc = hash_tab_regrow(c, cfg.small, q->small_cap, cfg.small_mask, pow2_at_least(max_small * 2), q->T, 2))) return rc;
+  if (max_big * 10 >= q->big_cap * 8 && (rc = hash_tab_regrow(c, cfg.big, q->big_cap, cfg.big_mask, pow2_at_least(max_big * 2), q->T, IDK_BIG_U64))) return rc;
   const u64 need_out = (max_bytes * 2 + 4096 + 7) & ~7ull, ni = off[n_reads] + 64, no = ((u64)n_reads + 1) * sizeof(u64);
-  if (need_out > q->out_cap) {
-    dfree(c, cfg.out);
-    if ((rc = dalloc(c, &p, need_out * T, false))) return rc;
-    cfg.out = (u8 *)p; cfg.out_cap = q->out_cap = need_out;
-  }
-  if (ni > q->ids_cap) { dfree(c, q->d_ids); if ((rc = dalloc(c, &p, ni + ni / 4, false))) return rc; q->d_ids = (u8 *)p; q->ids_cap = ni + ni / 4; }
-  if (no > q->off_cap) { dfree(c, q->d_off); if ((rc = dalloc(c, &p, no + no / 4, false))) return rc; q->d_off = (u64 *)p; q->off_cap = no + no / 4; }
+  if ((rc = dfit(c, cfg.out, cfg.out_cap, need_out, need_out, T))) return rc;
+  // (every allocation of the block before the launch: a call that fails for memory has not moved the models and can be repeated)
+  if ((rc = dfit(c, q->d_compact, q->compact_cap, cfg.out_cap * T, cfg.out_cap * T, 1))) return rc;
+  if ((rc = dfit(c, q->d_ids, q->ids_cap, ni, ni + ni / 4, 1))) return rc;
+  if ((rc = dfit(c, q->d_off, q->off_cap, no, no + no / 4, 1))) return rc;
   if ((rc = h2d(c, q->d_ids, ids, off[n_reads]))) return rc;
   if ((rc = h2d(c, q->d_off, off, no))) return rc;
   cfg.ids = q->d_ids;
@@ -2751,7 +2656,7 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
   }
   for (u64 t = 0; t < T; ++t)
     if (q->h_lens[t] > cfg.out_cap) { g_err = "id stream overflow"; return FQSX_E_DEVICE; }
-  return collect_streams(c, q->d_compact, q->compact_cap, (u32)T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
+  return collect_streams(c, q->d_compact, (u32)T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
 }
 
 // Inverse of fqsx_idg_encode_block.  The encoder sizes its tables and its output from the ids it is given; the decoder
@@ -2764,62 +2669,36 @@ int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint
   DevCtx *c = q;
   IdCfg &cfg = q->cfg;
   const u64 T = q->T;
-  u64 in_words = 2 * T;
-  q->h_in.assign(2 * T, 0);
   for (u64 t = 0; t < T; ++t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     if (first < last && (lens[t] < 8 || !streams[t])) { g_err = "id stream of a worker shorter than 8 bytes"; return FQSX_E_ARG; }   // sub_rc.h:114
-    q->h_in[t] = (in_words - 2 * T) * 8;
-    q->h_in[T + t] = streams[t] ? lens[t] : 0;
-    in_words += (q->h_in[T + t] + 7) / 8;
   }
-  q->h_in.resize(in_words + 1, 0);
-  for (u64 t = 0; t < T; ++t)
-    if (q->h_in[T + t]) memcpy((u8 *)(q->h_in.data() + 2 * T) + q->h_in[t], streams[t], q->h_in[T + t]);
+  const u64 in_words = pack_streams(T, streams, lens, q->h_in);
   DEVCHK(dev_enter(c));
   int rc;
   void *p = nullptr;
   const u64 ni = (in_words + 1) * sizeof(u64), nl = ((u64)n_reads + 1) * sizeof(u32);
-  // (a buffer that is handed back is forgotten before its successor is asked for: a failed allocation leaves nothing dangling)
-  if (ni > q->in_cap) { dfree(c, q->d_in); q->d_in = nullptr; q->in_cap = 0; if ((rc = dalloc(c, &p, ni + ni / 4, false))) return rc; q->d_in = (u8 *)p; q->in_cap = ni + ni / 4; }
-  if (nl > q->idlen_cap) { dfree(c, q->d_idlen); q->d_idlen = nullptr; q->idlen_cap = 0; if ((rc = dalloc(c, &p, nl + nl / 4, false))) return rc; q->d_idlen = (u32 *)p; q->idlen_cap = nl + nl / 4; }
+  if ((rc = dfit(c, q->d_in, q->in_cap, ni, ni + ni / 4, 1))) return rc;
+  if ((rc = dfit(c, q->d_idlen, q->idlen_cap, nl, nl + nl / 4, 1))) return rc;
   if ((rc = h2d(c, q->d_in, q->h_in.data(), ni))) return rc;
-  if (q->out_cap < q->dec_out_init) {
-    dfree(c, cfg.out);
-    cfg.out = nullptr; cfg.out_cap = q->out_cap = 0;
-    if ((rc = dalloc(c, &p, q->dec_out_init * T, false))) return rc;
-    cfg.out = (u8 *)p; cfg.out_cap = q->out_cap = q->dec_out_init;
-  }
+  if ((rc = dfit(c, cfg.out, cfg.out_cap, q->dec_out_init, q->dec_out_init, T))) return rc;
   const u64 fixed_bytes = T * IDK_FIXED * IDK_BIG_U64 * sizeof(u64), mtf_bytes = T * cfg.mtf_cap * IDK_NAME, state_bytes = 4 * T * sizeof(u32);
   if (!q->snap_fixed) {
     if ((rc = dalloc(c, &p, fixed_bytes, false))) return rc;
     q->snap_fixed = (u64 *)p;
-    if (cfg.mode == 1) { if ((rc = dalloc(c, &p, mtf_bytes, false))) return rc; q->snap_mtf = (u8 *)p; }
   }
-  auto grow = [&](u64 *&tab, u64 &cap, u64 &mask, u32 slot_u64) -> int {   // from the (restored) table into one of twice the slots
-    const u64 ncap = cap * 2;
-    void *nt = nullptr;
-    int r = dalloc(c, &nt, ncap * T * slot_u64 * sizeof(u64), false);
-    if (r) return r;
-    if (!(r = dfill_ff(c, nt, ncap * T * slot_u64 * sizeof(u64))))
-      r = dev_launch(c, 2, false, [&] { DEV_KERNEL(c, k_qual_rehash, REHASH_GRID, 256, (const u64 *)tab, mask, (u64 *)nt, ncap - 1, (u32)T, slot_u64); });
-    if (!r) r = dev_sync(c);
-    if (r) { dfree(c, nt); return r; }   // (the old table stays in place)
-    p = nt;
-    dfree(c, tab);
-    tab = (u64 *)p; cap = ncap; mask = ncap - 1;
-    return FQSX_OK;
-  };
+  if (cfg.mode == 1 && !q->snap_mtf) {
+    if ((rc = dalloc(c, &p, mtf_bytes, false))) return rc;
+    q->snap_mtf = (u8 *)p;
+  }
   // How far a valid stream can make the capacities grow: a new model is all ones, so the symbol that creates one costs at least
   // 1 bit (small) or 7 bits (big) of the worker's stream, and a line has at most IDK_MAX_ID bytes.  A stream that asks for more
   // is malformed.
   u64 lim_small = 0, lim_big = 0, lim_out = 0;
   for (u64 t = 0; t < T; ++t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     lim_small = std::max(lim_small, (u64)q->h_state[4 * t] + 8 * q->h_in[T + t] + 64);
     lim_big = std::max(lim_big, (u64)q->h_state[4 * t + 1] + 2 * q->h_in[T + t] + 64);
     lim_out = std::max(lim_out, (last - first) * IDK_MAX_ID + 64);
@@ -2831,18 +2710,9 @@ int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint
   da.id_len = q->d_idlen;
   for (u32 attempt = 0;; ++attempt) {
     const u64 small_bytes = q->small_cap * T * 2 * sizeof(u64), big_bytes = q->big_cap * T * IDK_BIG_U64 * sizeof(u64);
-    if (q->snap_small_cap != q->small_cap) {
-      dfree(c, q->snap_small);
-      q->snap_small = nullptr; q->snap_small_cap = 0;
-      if ((rc = dalloc(c, &p, small_bytes, false))) return rc;
-      q->snap_small = (u64 *)p; q->snap_small_cap = q->small_cap;
-    }
-    if (q->snap_big_cap != q->big_cap) {
-      dfree(c, q->snap_big);
-      q->snap_big = nullptr; q->snap_big_cap = 0;
-      if ((rc = dalloc(c, &p, big_bytes, false))) return rc;
-      q->snap_big = (u64 *)p; q->snap_big_cap = q->big_cap;
-    }
+    // (the tables only grow, so a snapshot buffer that does not fit is one that is too small)
+    if ((rc = dfit(c, q->snap_small, q->snap_small_cap, q->small_cap, q->small_cap, T * 2 * sizeof(u64)))) return rc;
+    if ((rc = dfit(c, q->snap_big, q->snap_big_cap, q->big_cap, q->big_cap, T * IDK_BIG_U64 * sizeof(u64)))) return rc;
     if ((rc = d2d(c, q->snap_small, cfg.small, small_bytes)) || (rc = d2d(c, q->snap_big, cfg.big, big_bytes)) ||
         (rc = d2d(c, q->snap_fixed, cfg.fixed, fixed_bytes)) || (cfg.mode == 1 && (rc = d2d(c, q->snap_mtf, cfg.mtf, mtf_bytes))))
       return rc;
@@ -2858,22 +2728,19 @@ int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint
         (rc = d2d(c, cfg.big, q->snap_big, big_bytes)) || (rc = d2d(c, cfg.fixed, q->snap_fixed, fixed_bytes)) ||
         (cfg.mode == 1 && (rc = d2d(c, cfg.mtf, q->snap_mtf, mtf_bytes))) || (rc = dev_sync(c)))
       return rc;
-    const bool can_grow = err == IDK_ERR_OUT ? q->out_cap * 2 <= std::max(lim_out, q->dec_out_init) : err == IDK_ERR_TABLE && which == 1 ? q->small_cap * 2 <= lim_small
+    const bool can_grow = err == IDK_ERR_OUT ? cfg.out_cap * 2 <= std::max(lim_out, q->dec_out_init) : err == IDK_ERR_TABLE && which == 1 ? q->small_cap * 2 <= lim_small
                                                                                      : err == IDK_ERR_TABLE && q->big_cap * 2 <= lim_big;
     if (can_grow && attempt < 64) {
       q->n_retry += 1;
       if (err == IDK_ERR_OUT) {
-        const u64 ncap = q->out_cap * 2;
-        dfree(c, cfg.out);
-        cfg.out = nullptr; cfg.out_cap = q->out_cap = 0;
-        if ((rc = dalloc(c, &p, ncap * T, false))) return rc;
-        cfg.out = (u8 *)p; cfg.out_cap = q->out_cap = ncap;
+        const u64 ncap = cfg.out_cap * 2;
+        if ((rc = dfit(c, cfg.out, cfg.out_cap, ncap, ncap, T))) return rc;
         q->n_grow_out += 1;
-      } else if (which == 1) {
-        if ((rc = grow(cfg.small, q->small_cap, cfg.small_mask, 2))) return rc;
+      } else if (which == 1) {   // (from the restored table into one of twice the slots)
+        if ((rc = hash_tab_regrow(c, cfg.small, q->small_cap, cfg.small_mask, q->small_cap * 2, q->T, 2))) return rc;
         q->n_grow_small += 1;
       } else {
-        if ((rc = grow(cfg.big, q->big_cap, cfg.big_mask, IDK_BIG_U64))) return rc;
+        if ((rc = hash_tab_regrow(c, cfg.big, q->big_cap, cfg.big_mask, q->big_cap * 2, q->T, IDK_BIG_U64))) return rc;
         q->n_grow_big += 1;
       }
       continue;
@@ -2912,7 +2779,7 @@ int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint
 int fqsx_idg_stats(fqsx_idg *q, uint64_t out[8]) {
   if (!q || !out) { g_err = "null argument"; return FQSX_E_ARG; }
   out[0] = q->n_retry; out[1] = q->n_grow_small; out[2] = q->n_grow_big; out[3] = q->n_grow_out;
-  out[4] = q->small_cap; out[5] = q->big_cap; out[6] = q->out_cap; out[7] = 0;
+  out[4] = q->small_cap; out[5] = q->big_cap; out[6] = q->cfg.out_cap; out[7] = 0;
   return FQSX_OK;
 }
 // the per-worker state words after the last block: out[4 * w + 0 / 1 / 2] = small slots, big slots, move-to-front entries of worker w

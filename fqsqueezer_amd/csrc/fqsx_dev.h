@@ -4079,12 +4079,11 @@ FQ_DEV void head_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_re
   for (u32 i = 0; i < ST_N; ++i) w.st[i] = 0;
   for (u32 i = 0; i < FQSX_TM_SLOTS; ++i) w.tm[i] = 0;
   const u64 T = cfg.T;
-  u64 first = (u64)tid * n_reads / T, last = ((u64)tid + 1) * n_reads / T;   // PartitionForWorkers, reads_block.h:197-214
-  if (tid) first &= ~1ull;
-  if (tid + 1 < T) last &= ~1ull;
+  u64 first, last;
+  worker_reads(tid, T, n_reads, first, last);
   const u64 cur = seg == 0 ? first : ws->cursor;
   u64 stop = last;
-  if (seg < S) stop = ((u64)seg + 1) * (last - first) / ((u64)S + 1) + first + 1;   // application.cpp:643
+  if (seg < S) stop = segment_synchro(seg, S, first, last) + 1;
   if (stop > last) stop = last;
   WHATIF(cfg, 7, 1);   // (once per launch, ahead of everything: the calibration of the what-if profile)
   for (u64 i = cur; i < stop && !w.err; ++i) {
@@ -4169,12 +4168,11 @@ FQ_DEV void scout_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_r
   for (u32 i = 0; i < FQSX_TM_SLOTS; ++i) w.tm[i] = 0;
   for (u32 i = 0; i < 4; ++i) w.s_let[i] = ws->s_letters[i];
   const u64 T = cfg.T;
-  u64 first = (u64)tid * n_reads / T, last = ((u64)tid + 1) * n_reads / T;   // PartitionForWorkers, reads_block.h:197-214
-  if (tid) first &= ~1ull;
-  if (tid + 1 < T) last &= ~1ull;
+  u64 first, last;
+  worker_reads(tid, T, n_reads, first, last);
   const u64 cur = seg == 0 ? first : ws->cursor;
   u64 stop = last;
-  if (seg < S) stop = ((u64)seg + 1) * (last - first) / ((u64)S + 1) + first + 1;   // application.cpp:643
+  if (seg < S) stop = segment_synchro(seg, S, first, last) + 1;
   if (stop > last) stop = last;
   bool quit = false;
   w.sc_epoch = 0;
@@ -4465,10 +4463,8 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
   TM_BEGIN(t_total);
   TM_STAMP(cfg, tid, launch, 0);
   const u64 T = cfg.T;
-  // PartitionForWorkers, reads_block.h:197-214
-  u64 first = (u64)tid * n_reads / T, last = ((u64)tid + 1) * n_reads / T;
-  if (tid) first &= ~1ull;
-  if (tid + 1 < T) last &= ~1ull;
+  u64 first, last;
+  worker_reads(tid, T, n_reads, first, last);
   if (seg == 0) {  // application.cpp:624-628
     ws->cursor = (u32)first;
     if (!piped) {   // (the coder wave initialises its own coder)
@@ -4481,7 +4477,7 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
   constexpr bool paired = MODE >= 2;
   u64 stop;
   if (seg < S) {
-    const u64 ns = ((u64)seg + 1) * (last - first) / ((u64)S + 1) + first;
+    const u64 ns = segment_synchro(seg, S, first, last);
     if (!paired) stop = ns + 1;            // SE: synchronise after read i == next_synchro (application.cpp:643)
     else {                                 // PE: after the first pair with i >= next_synchro (application.cpp:1170)
       u64 i = ws->cursor;

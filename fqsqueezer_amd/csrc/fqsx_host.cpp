@@ -5,6 +5,7 @@
 // per-bin read order of sorted mode.  None of it is on the hot path; it exists so that a complete container
 // can be written around the GPU DNA / quality streams and handed to the reference decoder.
 #include "../../include/fqsx.h"
+#include "fqsx_split.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -456,9 +457,8 @@ int fqsx_meta_encode_block_pe(fqsx_meta *m, const uint32_t *read_len, uint32_t n
   if (!m || !read_len || !streams || !lens) return FQSX_E_ARG;
   const u64 T = m->T;
   for (u64 t = 0; t < T; ++t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     Worker &w = m->w[t];
     w.enc.start();
     for (u64 i = first; i < last; ++i)
@@ -486,9 +486,8 @@ int fqsx_meta_decode_block(fqsx_meta *m, const uint8_t *const *streams, const ui
   if (!m || !streams || !lens || !read_len_out) return FQSX_E_ARG;
   const u64 T = m->T;
   for (u64 t = 0; t < T; ++t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     if (first == last) continue;
     if (!streams[t] || lens[t] < 8) return FQSX_E_ARG;   // sub_rc.h:114
     Worker &w = m->w[t];
@@ -519,9 +518,8 @@ int fqsx_id_encode_block(fqsx_id *h, const uint8_t *ids, const uint64_t *id_off,
   if (!h || !ids || !id_off || !streams || !lens || (paired && (n_reads & 1))) return FQSX_E_ARG;
   const u64 T = h->T;
   auto run = [&](u64 t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     IdWorker &w = h->w[t];
     w.reset_read_prev();
     w.enc.start();
@@ -571,15 +569,13 @@ int fqsx_id_decode_block(fqsx_id *h, const uint8_t *const *streams, const uint64
   if (!h || !streams || !lens || !ids_out || !id_off_out || (paired && (n_reads & 1))) return FQSX_E_ARG;
   const u64 T = h->T;
   for (u64 t = 0; t < T; ++t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;  // reads_block.h:197-214
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     if (h->mode != 2 && first < last && (!streams[t] || lens[t] < 8)) return FQSX_E_ARG;   // sub_rc.h:114
   }
   auto run = [&](u64 t) {
-    u64 first = t * n_reads / T, last = (t + 1) * n_reads / T;
-    if (t) first &= ~1ull;
-    if (t + 1 < T) last &= ~1ull;
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
     IdWorker &w = h->w[t];
     w.reset_read_prev();
     std::vector<u8> &out = w.dec_ids;

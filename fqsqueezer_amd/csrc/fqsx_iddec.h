@@ -387,9 +387,8 @@ FQ_DEV u32 idd_instrument(IdD &k) {
 // worker `tid` decodes the ids of its reads of the block (CIdCompressor::Decompress / DecompressPE, application.cpp:874-917)
 FQ_DEV void id_decode_body(const IdCfg &cfg, const IdDecArgs &da, IdShared *sm, u32 tid, u32 n_reads, u32 paired) {
   const u64 T = cfg.T;
-  u64 first = (u64)tid * n_reads / T, last = ((u64)tid + 1) * n_reads / T;  // reads_block.h:197-214
-  if (tid) first &= ~1ull;
-  if (tid + 1 < T) last &= ~1ull;
+  u64 first, last;
+  worker_reads(tid, T, n_reads, first, last);
   IdD k;
   k.cfg = &cfg; k.sm = sm;
   k.d.in = da.in + uniform64(da.in_off[tid]);

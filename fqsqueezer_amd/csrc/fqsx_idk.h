@@ -370,9 +370,8 @@ FQ_DEV bool idk_typical_pe(const u8 *a, u32 na, const u8 *b, u32 nb) {   // id.c
 // worker `tid` codes the ids of its reads of the block (CIdCompressor::Compress / CompressPE, application.cpp:634-640)
 FQ_DEV void id_encode_body(const IdCfg &cfg, IdShared *sm, u32 tid, u32 n_reads, u32 paired) {
   const u64 T = cfg.T;
-  u64 first = (u64)tid * n_reads / T, last = ((u64)tid + 1) * n_reads / T;  // reads_block.h:197-214
-  if (tid) first &= ~1ull;
-  if (tid + 1 < T) last &= ~1ull;
+  u64 first, last;
+  worker_reads(tid, T, n_reads, first, last);
   IdK k;
   k.cfg = &cfg; k.sm = sm;
   k.e.low = 0; k.e.range = 0xff00000000000000ULL; k.e.len = 0; k.e.acc = 0; k.e.cap = cfg.out_cap; k.e.out = cfg.out + (u64)tid * cfg.out_cap; k.e.err = 0;

@@ -11,6 +11,7 @@
 // (tests/emu); it is never part of the product library, which has no CPU path.
 #pragma once
 #include <stdint.h>
+#include "fqsx_split.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;

@@ -280,9 +280,8 @@ FQ_DEV void qd_flush(u8 *out, u64 base, u64 lo, u64 hi, u32 byte) {
 // worker `tid` decodes the qualities of its reads of the block (application.cpp:874-917, quality.cpp:175-200)
 FQ_DEV void qual_decode_body(const QualCfg &cfg, const QualDecArgs &da, u32 tid, u32 n_reads) {
   const u64 T = cfg.T;
-  u64 first = (u64)tid * n_reads / T, last = ((u64)tid + 1) * n_reads / T;  // reads_block.h:197-214
-  if (tid) first &= ~1ull;
-  if (tid + 1 < T) last &= ~1ull;
+  u64 first, last;
+  worker_reads(tid, T, n_reads, first, last);
   const u32 N = cfg.n_sym;
   QDec d;
   d.in = da.in + uniform64(da.in_off[tid]);

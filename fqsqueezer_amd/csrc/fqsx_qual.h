@@ -183,9 +183,8 @@ FQ_DEV void qual_chunk(const QualCfg &cfg, QEnc &e, u64 *tab, u32 &filled, const
 // worker `tid` codes the qualities of its reads of the block (application.cpp:641, quality.cpp:152-175)
 FQ_DEV void qual_encode_body(const QualCfg &cfg, u8 *lds_q /*[4096 + 96]*/, u32 tid, u32 n_reads) {
   const u64 T = cfg.T;
-  u64 first = (u64)tid * n_reads / T, last = ((u64)tid + 1) * n_reads / T;  // reads_block.h:197-214
-  if (tid) first &= ~1ull;
-  if (tid + 1 < T) last &= ~1ull;
+  u64 first, last;
+  worker_reads(tid, T, n_reads, first, last);
   QEnc e;
   e.low = 0; e.range = 0xff00000000000000ULL; e.len = 0; e.acc = 0; e.cap = cfg.out_cap; e.out = cfg.out + (u64)tid * cfg.out_cap; e.err = 0;
   u64 *tab = cfg.tab + (u64)tid * (cfg.cap_mask + 1) * cfg.slot_u64;

@@ -33,6 +33,7 @@ struct DevCtx {
   std::vector<void *> allocs;
   std::vector<u64> alloc_bytes;   // size of allocs[i]
   u64 dev_bytes = 0, dev_bytes_peak = 0;   // device memory held now / at most so far (fqsx_dna_capacity)
+  u64 n_dalloc = 0;   // dalloc calls so far (FQSX_TEST_ALLOC_FAIL)
 };
 
 #ifndef FQSX_EMU
@@ -206,11 +207,17 @@ template <class F> static int emu_grid(u32 grid, F &&block) {
 // ---- allocations: every one is in the context's ledger, so that dev_close can hand back whatever is left
 static int dzero(DevCtx *c, void *p, u64 bytes) { return dfill(c, p, 0, bytes); }
 static int dfill_ff(DevCtx *c, void *p, u64 bytes) { return dfill(c, p, 0xff, bytes); }
+// (tests: FQSX_TEST_ALLOC_FAIL=k makes the context's k-th dalloc, counted from 0, fail before it touches the runtime)
 static int dalloc(DevCtx *c, void **p, u64 bytes, bool zero) {
   if (bytes == 0) bytes = 8;
+  const char *fail_at = getenv("FQSX_TEST_ALLOC_FAIL");
+  if (c->n_dalloc++ == (fail_at ? strtoull(fail_at, nullptr, 10) : ~0ull)) {
+    g_err = "allocation " + std::string(fail_at) + " of the context refused (FQSX_TEST_ALLOC_FAIL)";
+    return FQSX_E_NOMEM;
+  }
   int rc = dev_malloc(p, bytes);
   if (rc) return rc;
-  if (zero && (rc = dzero(c, *p, bytes))) return rc;
+  if (zero && (rc = dzero(c, *p, bytes))) { dev_free_raw(*p); return rc; }
   c->allocs.push_back(*p);
   c->alloc_bytes.push_back(bytes);
   c->dev_bytes += bytes;
@@ -231,6 +238,21 @@ static void dfree(DevCtx *c, void *p) {
 static void dfree_all(DevCtx *c) {
   const std::vector<void *> a = c->allocs;
   for (void *p : a) dfree(c, p);
+}
+// The one way a buffer that is reused from call to call grows: nothing if `need` units fit into `cap`; else the old buffer is
+// handed back and FORGOTTEN (ptr null, cap 0) before its successor of `new_cap` units of `unit_bytes` bytes is asked for, so
+// that a failed allocation leaves nothing dangling and the next call starts from an empty buffer.  new_cap: the site's own rule.
+template <class P, class C> static int dfit(DevCtx *c, P *&ptr, C &cap, u64 need, u64 new_cap, u64 unit_bytes, bool zero = false) {
+  if (need <= cap) return FQSX_OK;
+  dfree(c, (void *)ptr);
+  ptr = nullptr;
+  cap = 0;
+  void *p = nullptr;
+  const int rc = dalloc(c, &p, new_cap * unit_bytes, zero);
+  if (rc) return rc;
+  ptr = (P *)p;
+  cap = (C)new_cap;
+  return FQSX_OK;
 }
 static int d2h_sync(DevCtx *c, void *h, const void *d, u64 bytes) {
   int rc = d2h(c, h, d, bytes);
