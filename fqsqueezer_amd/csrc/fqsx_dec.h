@@ -88,36 +88,19 @@ FQ_DEV u32 find_leveled_dec(Wk &w, u32 tag, const u64 *lev, u64 rs, int n_levels
 // ASCII to the output block; a second line holds the reverse-complement part of an anchored second mate
 FQ_DEV u8 dec_alpha(u32 sym) { return sym == 0 ? 'A' : sym == 1 ? 'C' : sym == 2 ? 'G' : sym == 3 ? 'T' : 'N'; }
 
-// ---- CRangeDecoder
-FQ_DEV u64 rcd_byte(Wk &w) {
-  u64 b = w.din_pos < w.din_len ? w.din[w.din_pos] : 0;
+// ---- CRangeDecoder (fqsx_rc.h) over the worker's stream, read byte by byte
+FQ_DEV u64 rc_src_byte(Wk &w) {
+  const u64 b = w.din_pos < w.din_len ? w.din[w.din_pos] : 0;
   ++w.din_pos;
   return b;
 }
-FQ_DEV void rcd_start(Wk &w) {  // sub_rc.h:112-125
+FQ_DEV void rcd_start(Wk &w) {
   w.din_pos = 0;
-  w.din_buffer = 0;
-  if (w.din_len >= 8)
-    for (u32 i = 1; i <= 8; ++i) w.din_buffer |= rcd_byte(w) << (64 - i * 8);
-  w.enc.low = 0;
-  w.enc.range = 0xff00000000000000ULL;
+  rcd_start(w.dec, w, w.din_len);
 }
-FQ_DEV u32 rcd_cum(Wk &w, u32 tot) {  // GetCumulativeFreq, sub_rc.h:127-131
-  w.enc.range = div_u64_small(w.enc.range, tot);
-  return (u32)(w.din_buffer / w.enc.range);
-}
-FQ_DEV void rcd_update(Wk &w, u32 freq, u32 cum) {  // UpdateFrequency, sub_rc.h:133-151
-  const u64 Top = 0x00ffffffffffffULL, M = 0xff00000000000000ULL;
-  u64 r = (u64)cum * w.enc.range, low = w.enc.low + r, range = w.enc.range * freq;
-  w.din_buffer -= r;
-  while (range <= Top) {
-    if ((low ^ (low + range)) & M) range = (low | Top) - low;
-    w.din_buffer = (w.din_buffer << 8) + rcd_byte(w);
-    low <<= 8;
-    range <<= 8;
-  }
-  w.enc.low = low;
-  w.enc.range = range;
+FQ_DEV u32 rcd_cum(Wk &w, u32 tot) { return rcd_cum(w.dec, tot); }
+FQ_DEV void rcd_update(Wk &w, u32 freq, u32 cum) {
+  rcd_update(w.dec, w, freq, cum);
   w.st[ST_CODED] += 1;
 }
 

@@ -5,6 +5,7 @@
 // the data structures and the execution model are this repo's own (fqsx_layout.h).
 #pragma once
 #include "fqsx_layout.h"
+#include "fqsx_rc.h"
 
 // ---------------------------------------------------------------------------------------
 // workgroup-shared (LDS) state of one worker
@@ -191,7 +192,6 @@ enum { PV_B = 1, PV_S = 2, PV_P = 4, PV_PHID = 8, PV_PCAND = 16 };
 struct C4 { u32 c[4]; };
 struct Kmer { u64 dir, rc; u32 cur; };
 struct Cinc { u32 thr, mult, maxv; };
-struct Enc { u64 low, range, len, cap, acc; u8 *out; };   // acc: bytes of the 8-byte output word being filled
 
 struct Wk {
   const DevCfg *cfg;
@@ -199,7 +199,7 @@ struct Wk {
   WState *ws;
   u32 tid;
   u32 mode;                             // dna_mode, a compile-time constant of the kernel (template argument of the bodies)
-  Enc enc;
+  RcEnc enc;                            // the worker's coder (fqsx_rc.h)
   Kmer pm, sm_, bm, pm_u, sm_u, bm_u;   // corrected and uncorrected rolling k-mers (dna.h:160-168)
   u64 ctx_letters;
   u32 cor_pos, N_run;
@@ -210,7 +210,8 @@ struct Wk {
   u32 mn[3];                            // entries appended to this worker's p/s/b mailbox lists
   u32 pe_n;                             // paired-end triples pushed in this launch
   const u8 *din;                        // decoder input stream of this worker
-  u64 din_len, din_pos, din_buffer;
+  u64 din_len, din_pos;
+  RcDec dec;                            // ... and its coder
   u32 la[3];                            // list entries already applied to the local tables (b, s)
   u32 pq_lo[2];                         // list entries (b, s) below this index were in the local tables when stage P last probed them
   bool lqh;                             // a third wave of the workgroup applies the local inserts (else: inline, on demand)
@@ -1091,10 +1092,9 @@ FQ_DEV u64 siv_count_equal(Wk &w, u64 lo, u64 hi, u64 flag) {
 }
 
 // ---------------------------------------------------------------------------------------
-// range coder (CRangeEncoder, sub_rc.h:32-87) writing into the worker's HBM stream
+// range coder (fqsx_rc.h) writing into the worker's HBM stream
 // The coder state is wave-uniform and kept in scalar registers (readfirstlane at enc_open), so the dependent chain of
-// a coding step -- multiply-high, compare, add, shift -- runs on the scalar unit.  Output bytes are gathered into the
-// aligned 8-byte word they belong to and leave with one store per word.
+// a coding step -- multiply-high, compare, add, shift -- runs on the scalar unit.
 // What-if profiling (-DFQSX_WHATIF, tools/gpu_whatif.py): `ev` events of role `role` cost an extra ev * units * ~0.2 us when the
 // run asks for that role (DevCfg.whatif) -- the file's slowdown per microsecond added says how much of the role is critical path.
 #ifdef FQSX_WHATIF
@@ -1114,50 +1114,10 @@ FQ_DEV void enc_open(Wk &w, u64 low, u64 range, u64 len, const DevCfg &cfg) {
   const u32 part = (u32)(w.enc.len & 7);
   if (part && w.enc.len < w.enc.cap) w.enc.acc = uniform64(((const u64 *)w.enc.out)[w.enc.len >> 3]) & ((1ull << (8 * part)) - 1ull);
 }
-FQ_DEV void enc_close(Wk &w) {   // the partly filled word (its tail is rewritten when the stream goes on)
-  if (w.enc.len > w.enc.cap) { w.err = FQSX_ERR_OUT_OVERFLOW; return; }   // (ended inside the word beyond the buffer: rc_put has not seen it)
-  if ((w.enc.len & 7) && w.enc.len < w.enc.cap) ((u64 *)w.enc.out)[w.enc.len >> 3] = w.enc.acc;
+FQ_DEV void enc_close(Wk &w) {
+  if (rc_overflowed(w.enc)) { w.err = FQSX_ERR_OUT_OVERFLOW; return; }
+  rc_close(w.enc);
 }
-FQ_DEV void rc_put(Wk &w, u8 b) {
-  w.enc.acc |= (u64)b << (8 * (u32)(w.enc.len & 7));
-  ++w.enc.len;
-  if ((w.enc.len & 7) == 0) {
-    if (w.enc.len <= w.enc.cap) ((u64 *)w.enc.out)[(w.enc.len >> 3) - 1] = w.enc.acc; else w.err = FQSX_ERR_OUT_OVERFLOW;
-    w.enc.acc = 0;
-  }
-}
-// exact range / tot for tot < 2^16 without the 64-bit software divide or an IEEE fp64 division: hardware
-// reciprocal (~26 bits) + one Newton step (~52 bits), high word and the remaining < 2^48 dividend each by one fp64
-// multiply with a +-1 fix-up (sub_rc.h:63).  tools/ubench checks it against u64 division on 1.3e9 operands.
-FQ_DEV double recip_u16(u32 d) {
-  const double dd = (double)d;
-#ifndef FQSX_EMU
-  const double r0 = __builtin_amdgcn_rcp(dd);
-  return __builtin_fma(r0, __builtin_fma(-dd, r0, 1.0), r0);
-#else
-  return 1.0 / dd;
-#endif
-}
-FQ_DEV u64 div_u64_rd(u64 x, u32 d, double rd) {
-  const u32 hi = (u32)(x >> 32), lo = (u32)x;
-  u32 qh = (u32)((double)hi * rd);
-  u32 ph = qh * d;
-  if (ph > hi) { --qh; ph -= d; } else if (hi - ph >= d) { ++qh; ph += d; }
-  const u32 r1 = hi - ph;                                                        // < d
-  const double remd = __builtin_fma((double)r1, 4294967296.0, (double)lo);      // exact: < 2^48
-  u32 q = (u32)(remd * rd);                                                      // rem / d < 2^32
-  const u64 rem = ((u64)r1 << 32) | lo;
-  const u64 prod = (u64)q * d;
-  if (prod > rem) --q;
-  else if (rem - prod >= d) ++q;
-  return ((u64)qh << 32) + q;
-}
-FQ_DEV u64 div_u64_small(u64 x, u32 d) { return div_u64_rd(x, d, recip_u16(d)); }
-// One coding step (Encode, sub_rc.h:60-77) with the division as an integer multiply-high by
-// m = floor((2^64-1) / tot), 2 <= tot < 2^16: for any range < 2^64, mulhi(range, m) is the quotient or one less.
-// Integer only and wave-uniform: the whole dependent chain of a symbol runs on the scalar unit (low / range live in
-// scalar registers, see enc_open).  m is computed off the chain where the caller can (one lane per position in code_run).
-FQ_DEV u64 recip64_u16(u32 d) { return div_u64_rd(~0ull, d, recip_u16(d)); }
 // model wave -> range-coder wave: room for `need` more entries
 FQ_DEV bool rq_wait_space(Wk &w, u32 need) {
   if (w.rq_tail - lds_load_acq(&w.sm->rq_head) + need <= FQSX_RQ) return true;
@@ -1182,27 +1142,8 @@ FQ_DEV void rc_encode_m(Wk &w, u32 freq, u32 cum, u32 tot, u64 m) {
     lds_store_rel(&sm->rq_tail, w.rq_tail);
     return;
   }
-  const u64 Top = 0x00ffffffffffffULL, M = 0xff00000000000000ULL;
-  freq = uniform32(freq); cum = uniform32(cum); tot = uniform32(tot); m = uniform64(m);
-  u64 low = w.enc.low;
-#ifndef FQSX_EMU
-  u64 range = __umul64hi(w.enc.range, m);
-#else
-  u64 range = (u64)(((unsigned __int128)w.enc.range * m) >> 64);
-#endif
-  // mulhi gives the quotient or one less, so the remainder is below 2 * tot < 2^17: its low 32 bits decide (one
-  // multiply, one subtract, one compare on the scalar unit instead of a 64-bit multiply-subtract-compare)
-  if ((u32)w.enc.range - (u32)range * tot >= tot) ++range;
-  low += range * cum;
-  range *= freq;
-  while (range <= Top) {
-    if ((low ^ (low + range)) & M) range = (low | Top) - low;
-    rc_put(w, (u8)(low >> 56));
-    low <<= 8;
-    range <<= 8;
-  }
-  w.enc.low = low;
-  w.enc.range = range;
+  rc_step(w.enc, uniform32(freq), uniform32(cum), uniform32(tot), uniform64(m));
+  if (rc_overflowed(w.enc)) w.err = FQSX_ERR_OUT_OVERFLOW;   // (stops the worker before the close)
   w.st[ST_CODED] += 1;
 }
 FQ_DEV void rc_encode_rd(Wk &w, u32 freq, u32 cum, u32 tot, double rd) {
@@ -4514,7 +4455,7 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
     w.din = cfg.din + cfg.din_off[tid];
     w.din_len = cfg.din_off[tid + 1] - cfg.din_off[tid];
     if (ws->dec_pos == ~0ull) rcd_start(w);
-    else { w.din_pos = ws->dec_pos; w.din_buffer = ws->dec_buffer; }
+    else { w.din_pos = ws->dec_pos; w.dec.low = ws->rc_low; w.dec.range = ws->rc_range; w.dec.buf = ws->dec_buffer; }
     u8 *codes = cfg.dscratch + (u64)tid * 2 * cfg.dcap, *rcodes = codes + cfg.dcap;
     for (u64 i = cur; i < stop && !w.err; i += paired ? 2 : 1) {
       const u64 o0 = cfg.read_off[i], o1 = cfg.read_off[i + 1];
@@ -4524,7 +4465,7 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
       else if (i + 1 < stop) pair_dec(w, codes, rcodes, cfg.dout + o0, (u32)(o1 - o0), cfg.dout + o1, (u32)(cfg.read_off[i + 2] - o1), prev_out);
     }
     ws->dec_pos = w.din_pos;
-    ws->dec_buffer = w.din_buffer;
+    ws->dec_buffer = w.dec.buf;
   } else if (heads)
     for (u64 i = cur; i < stop && !w.err; ++i) {
       u64 o0 = cfg.read_off[i], o1 = cfg.read_off[i + 1];
@@ -4570,8 +4511,11 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
   }
   ws->cursor = (u32)cur;
   if (!piped) {
-    enc_close(w);
-    ws->rc_low = w.enc.low; ws->rc_range = w.enc.range; ws->out_len = w.enc.len;
+    if (decode) { ws->rc_low = w.dec.low; ws->rc_range = w.dec.range; }
+    else {
+      enc_close(w);
+      ws->rc_low = w.enc.low; ws->rc_range = w.enc.range; ws->out_len = w.enc.len;
+    }
     ws->avg_code = w.avg_code; ws->avg_letters = w.avg_letters;
   }
   for (u32 i = 0; i < 4; ++i) ws->s_letters[i] = w.s_let[i];

@@ -41,64 +41,24 @@ struct IdD {
 FQ_DEV u32 idd_n_tok(const IdD &k, u32 set) { return set ? k.n_tok1 : k.n_tok0; }
 
 // ---- models -----------------------------------------------------------------------------------------------------------
-// 2- / 4-symbol model of `map` at context `ctx` (created all ones on first use): decode one symbol
+// small model of `map` at context `ctx`: decode one symbol
 FQ_DEV u32 idd_small(IdD &k, u32 map, u64 ctx, u32 N) {
-  const u64 key = ((u64)map << 56) | ctx, mask = k.cfg->small_mask;
-  u64 h = q_hash(key) & mask;
-  u64 *slot = nullptr;
-  u64 st = 0;
-  for (u64 it = 0; it <= mask; ++it) {
-    u64 *p = k.small + 2 * h;
-    const u64 kk = uniform64(p[0]);
-    if (kk == key) { slot = p; st = uniform64(p[1]); break; }
-    if (kk == ~0ull) {
-      if ((u64)(k.n_small + 1) * 10 >= (mask + 1) * 9) break;
-      slot = p;
-      st = N == 2 ? 0x0000000000010001ULL : 0x0001000100010001ULL;
-      if (FQ_LANE == 0) p[0] = key;
-      k.n_small += 1;
-      break;
-    }
-    h = (h + 1) & mask;
-  }
-  if (!slot) { k.err = IDK_ERR_TABLE; k.which = 1; return 0; }
+  bool fresh;
+  u64 *slot = idw_small_slot(k, map, ctx, fresh);
+  if (!slot) { k.which = 1; return 0; }
+  const u64 st = idm_small_load(slot, N, fresh);
   u32 tot = 0;
-  for (u32 i = 0; i < N; ++i) tot += (u32)((st >> (16 * i)) & 0xffff);
+  for (u32 i = 0; i < N; ++i) tot += idm_field(st, i);
   const u32 cumv = qd_cum(k.d, tot);
   if (cumv >= tot) { k.err = IDK_ERR_STREAM; return 0; }
   u32 x = 0, cum = 0;
   for (; x + 1 < N; ++x) {
-    const u32 f = (u32)((st >> (16 * x)) & 0xffff);
-    if (cum + f > cumv) break;
-    cum += f;
+    if (cum + idm_field(st, x) > cumv) break;
+    cum += idm_field(st, x);
   }
-  qd_update(k.d, (u32)((st >> (16 * x)) & 0xffff), cum);
-  st += 1ull << (16 * x);
-  tot += 1;
-  while (tot >= (1u << 15)) {
-    u64 nv = 0;
-    tot = 0;
-    for (u32 i = 0; i < N; ++i) {
-      const u32 s = ((u32)((st >> (16 * i)) & 0xffff) + 1) / 2;
-      tot += s;
-      nv |= (u64)s << (16 * i);
-    }
-    st = nv;
-  }
-  if (FQ_LANE == 0) slot[1] = st;
-  FQ_SYNC_MEM();
+  qd_update(k.d, idm_field(st, x), cum);
+  idm_small_update_store(slot, st, N, x, tot);
   return x;
-}
-// one word of a big slot halved (rc.h:41-55): the statistics below N only
-FQ_DEV u64 idd_halve_word(u64 v, u32 first, u32 N, u32 &part) {
-  u64 nv = 0;
-#pragma unroll
-  for (u32 f = 0; f < 4; ++f) {
-    u32 s = (u32)((v >> (16 * f)) & 0xffff);
-    if (first + f < N) { s = (s + 1) / 2; part += s; }
-    nv |= (u64)s << (16 * f);
-  }
-  return nv;
 }
 // N-symbol model (N <= 256) in a big slot: decode one symbol.  Four statistics per lane.
 FQ_DEV u32 idd_big_decode(IdD &k, u64 *slot, u32 N, bool fresh) {
@@ -128,7 +88,7 @@ FQ_DEV u32 idd_big_decode(IdD &k, u64 *slot, u32 N, bool fresh) {
   bool all = fresh;
   while (tot >= (1u << 15)) {
     u32 part = 0;
-    v = idd_halve_word(v, 4 * l, N, part);
+    v = idm_halve_word(v, 4 * l, N, part);
     tot = uniform32(wave_sum32(part));
     all = true;
   }
@@ -155,29 +115,17 @@ FQ_DEV u32 idd_big_decode(IdD &k, u64 *slot, u32 N, bool fresh) {
   tot += 1;
   while (tot >= (1u << 15)) {
     tot = 0;
-    for (u32 i = 0; 4 * i < N; ++i) w[i] = idd_halve_word(w[i], 4 * i, N, tot);
+    for (u32 i = 0; 4 * i < N; ++i) w[i] = idm_halve_word(w[i], 4 * i, N, tot);
   }
   w[64] = tot;
   return x;
 #endif
 }
 FQ_DEV u32 idd_big(IdD &k, u32 map, u64 ctx, u32 N) {
-  const u64 key = ((u64)map << 56) | ctx, mask = k.cfg->big_mask;
-  u64 h = q_hash(key) & mask;
-  for (u64 it = 0; it <= mask; ++it) {
-    u64 *p = k.big + IDK_BIG_U64 * h;
-    const u64 kk = uniform64(p[0]);
-    if (kk == key) return idd_big_decode(k, p, N, false);
-    if (kk == ~0ull) {
-      if ((u64)(k.n_big + 1) * 10 >= (mask + 1) * 9) break;
-      if (FQ_LANE == 0) p[0] = key;
-      k.n_big += 1;
-      return idd_big_decode(k, p, N, true);
-    }
-    h = (h + 1) & mask;
-  }
-  k.err = IDK_ERR_TABLE; k.which = 2;
-  return 0;
+  bool fresh;
+  u64 *slot = idw_big_slot(k, map, ctx, fresh);
+  if (!slot) { k.which = 2; return 0; }
+  return idd_big_decode(k, slot, N, fresh);
 }
 FQ_DEV u32 idd_fixed(IdD &k, u32 which, u32 N) { return idd_big_decode(k, k.fixed + IDK_BIG_U64 * which, N, false); }
 
@@ -390,19 +338,12 @@ FQ_DEV void id_decode_body(const IdCfg &cfg, const IdDecArgs &da, IdShared *sm, 
   u64 first, last;
   worker_reads(tid, T, n_reads, first, last);
   IdD k;
-  k.cfg = &cfg; k.sm = sm;
+  idw_open(k, cfg, sm, tid);
   k.d.in = da.in + uniform64(da.in_off[tid]);
   k.d.len = uniform64(da.in_off[T + tid]);
   qd_start(k.d);
-  k.small = cfg.small + (u64)tid * (cfg.small_mask + 1) * 2;
-  k.big = cfg.big + (u64)tid * (cfg.big_mask + 1) * IDK_BIG_U64;
-  k.fixed = cfg.fixed + (u64)tid * IDK_FIXED * IDK_BIG_U64;
-  k.mtf = cfg.mtf + (u64)tid * cfg.mtf_cap * IDK_NAME;
-  k.n_small = cfg.state[4 * tid]; k.n_big = cfg.state[4 * tid + 1]; k.n_mtf = cfg.state[4 * tid + 2];
-  // ResetReadPrev, id.cpp:124-135
-  k.cur_set = 0; k.n_tok0 = k.n_tok1 = 0;
-  k.ctx_flags = 0; k.ctx_pe_flags = 0;
-  k.err = 0; k.which = 0;
+  k.n_tok0 = k.n_tok1 = 0;
+  k.which = 0;
   k.out = cfg.out + (u64)tid * cfg.out_cap;
   k.out_pos = 0;
   for (u64 i = first; i < last && !k.err; i += paired ? 2 : 1) {
@@ -436,7 +377,7 @@ FQ_DEV void id_decode_body(const IdCfg &cfg, const IdDecArgs &da, IdShared *sm, 
   if (!k.err && k.d.pos > k.d.len) k.err = IDK_ERR_STREAM;   // (a decoder consumes exactly the bytes the encoder wrote: this stream was cut short)
   if (FQ_LANE == 0) {
     cfg.lens[tid] = k.out_pos;
-    cfg.state[4 * tid] = k.n_small; cfg.state[4 * tid + 1] = k.n_big; cfg.state[4 * tid + 2] = k.n_mtf;
+    idw_store_counts(k, tid);
     if (k.err) *cfg.err = k.err | (k.which << 8);
   }
 }

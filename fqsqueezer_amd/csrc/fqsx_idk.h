@@ -8,9 +8,9 @@
 //   small  [key | 4 x u16]            the 2- and 4-symbol maps (flags, pe_flags, literal_same, literal_same_length, numeric_small)
 //   big    [key | 256 x u16 | total]  the 128- and 256-symbol maps (literal, plain, numeric_size)
 // plus twelve fixed big models (mtf_flag, mtf_code[7], mtf_byte[4]).  Layout-free like everything else here: results depend
-// on model contents only.  Included by fqsx_api.hip after fqsx_qual.h (QEnc: the range coder).
+// on model contents only.  The worker state and the model helpers of both directions are here; fqsx_iddec.h is the decoder.
 #pragma once
-#include "fqsx_plat.h"
+#include "fqsx_qual.h"   // q_hash, q_find; the range coder (fqsx_rc.h)
 
 #define IDK_MAX_ID 1024u      // bytes of one id line (with its line feed) a worker stages in LDS
 #define IDK_MAX_TOK 128u      // tokens of one id
@@ -53,57 +53,87 @@ struct IdShared {
 struct IdK {
   const IdCfg *cfg;
   IdShared *sm;
-  QEnc e;
+  RcEnc e;
   u64 *small, *big, *fixed;
   u8 *mtf;
   u32 n_small, n_big, n_mtf;
   u32 cur_set;             // which of tb/te/tn/ts holds the current id's tokens (the other: the previous id's)
   u32 n_tok[2];
-  u32 prev_size;
   u64 ctx_flags, ctx_pe_flags;
   u32 err;
 };
+// The encoder's and the decoder's worker (IdK, IdD in fqsx_iddec.h) have the fields of this section in common and share the
+// code below through K.  (They are not a common base struct: with one, in the three field orders tried, k_id_decode keeps two
+// words of its state in 16 B of scratch and takes 196 instead of 126 VGPRs; tools/kernel_resources.sh.)
+template <class K>
+FQ_DEV void idw_open(K &k, const IdCfg &cfg, IdShared *sm, u32 tid) {
+  k.cfg = &cfg; k.sm = sm;
+  k.small = cfg.small + (u64)tid * (cfg.small_mask + 1) * 2;
+  k.big = cfg.big + (u64)tid * (cfg.big_mask + 1) * IDK_BIG_U64;
+  k.fixed = cfg.fixed + (u64)tid * IDK_FIXED * IDK_BIG_U64;
+  k.mtf = cfg.mtf + (u64)tid * cfg.mtf_cap * IDK_NAME;
+  k.n_small = cfg.state[4 * tid]; k.n_big = cfg.state[4 * tid + 1]; k.n_mtf = cfg.state[4 * tid + 2];
+  k.cur_set = 0; k.ctx_flags = 0; k.ctx_pe_flags = 0;   // ResetReadPrev, id.cpp:124-135 (with the callers' token counts)
+  k.err = 0;
+}
+template <class K>
+FQ_DEV void idw_store_counts(const K &k, u32 tid) {   // lane 0
+  k.cfg->state[4 * tid] = k.n_small; k.cfg->state[4 * tid + 1] = k.n_big; k.cfg->state[4 * tid + 2] = k.n_mtf;
+}
 
 // ---- models -----------------------------------------------------------------------------------------------------------
-// 2- / 4-symbol model of `map` at context `ctx` (created all ones on first use, rc.h:69-74): encode symbol x
-FQ_DEV void idk_small(IdK &k, u32 map, u64 ctx, u32 N, u32 x) {
+// The slot of model (map, ctx) in the small or the big table (n: its models so far), claimed on first use (fresh) while the
+// table is below 90 %; nullptr: IDK_ERR_TABLE
+template <class K>
+FQ_DEV u64 *idw_slot(K &k, u64 *tab, u64 mask, u32 width, u32 &n, u32 map, u64 ctx, bool &fresh) {
   const u64 key = ((u64)map << 56) | ctx;
-  u64 h = q_hash(key) & k.cfg->small_mask;
-  u64 *slot = nullptr;
-  u64 st = 0;
-  for (u64 it = 0; it <= k.cfg->small_mask; ++it) {
-    u64 *p = k.small + 2 * h;
-    const u64 kk = p[0];
-    if (kk == key) { slot = p; st = p[1]; break; }
-    if (kk == ~0ull) {
-      if ((u64)(k.n_small + 1) * 10 >= (k.cfg->small_mask + 1) * 9) { k.err = IDK_ERR_TABLE; return; }
-      slot = p;
-      st = N == 2 ? 0x0000000000010001ULL : 0x0001000100010001ULL;
-      if (FQ_LANE == 0) p[0] = key;
-      k.n_small += 1;
-      break;
-    }
-    h = (h + 1) & k.cfg->small_mask;
+  u64 *slot = q_find<false>(tab, mask, width, key, q_hash(key) & mask, 0, (u64)(n + 1) * 10 < (mask + 1) * 9, fresh);
+  if (fresh) n += 1;
+  if (!slot) k.err = IDK_ERR_TABLE;
+  return slot;
+}
+template <class K>
+FQ_DEV u64 *idw_small_slot(K &k, u32 map, u64 ctx, bool &fresh) { return idw_slot(k, k.small, k.cfg->small_mask, 2, k.n_small, map, ctx, fresh); }
+template <class K>
+FQ_DEV u64 *idw_big_slot(K &k, u32 map, u64 ctx, bool &fresh) { return idw_slot(k, k.big, k.cfg->big_mask, IDK_BIG_U64, k.n_big, map, ctx, fresh); }
+// 2- / 4-symbol model: one word of four 16-bit statistics (created all ones on first use, rc.h:69-74), no stored total
+FQ_DEV u32 idm_field(u64 v, u32 i) { return (u32)((v >> (16 * i)) & 0xffff); }
+FQ_DEV u64 idm_small_load(const u64 *slot, u32 N, bool fresh) {
+  return fresh ? (N == 2 ? 0x0000000000010001ULL : 0x0001000100010001ULL) : uniform64(slot[1]);
+}
+// one word of statistics halved (rc.h:41-55): the statistics below N only (`first` = index of the word's field 0)
+FQ_DEV u64 idm_halve_word(u64 v, u32 first, u32 N, u32 &part) {
+  u64 nv = 0;
+#pragma unroll
+  for (u32 f = 0; f < 4; ++f) {
+    u32 s = idm_field(v, f);
+    if (first + f < N) { s = (s + 1) / 2; part += s; }
+    nv |= (u64)s << (16 * f);
   }
-  if (!slot) { k.err = IDK_ERR_TABLE; return; }
-  u32 s[4] = {(u32)(st & 0xffff), (u32)((st >> 16) & 0xffff), (u32)((st >> 32) & 0xffff), (u32)(st >> 48)};
-  u32 tot = 0, cum = 0;
-  for (u32 i = 0; i < N; ++i) { tot += s[i]; if (i < x) cum += s[i]; }
-  q_encode(k.e, s[x], cum, tot);
-  s[x] += 1;
+  return nv;
+}
+// update (rc.h:41-55) of a small model of total `tot` after symbol x, and its way back into the slot
+FQ_DEV void idm_small_update_store(u64 *slot, u64 st, u32 N, u32 x, u32 tot) {
+  st += 1ull << (16 * x);
   tot += 1;
-  while (tot >= (1u << 15)) {
-    tot = 0;
-    for (u32 i = 0; i < N; ++i) { s[i] = (s[i] + 1) / 2; tot += s[i]; }
-  }
-  st = (u64)s[0] | ((u64)s[1] << 16) | ((u64)s[2] << 32) | ((u64)s[3] << 48);
+  while (tot >= (1u << 15)) { tot = 0; st = idm_halve_word(st, 0, N, tot); }
   if (FQ_LANE == 0) slot[1] = st;
   FQ_SYNC_MEM();
+}
+// small model of `map` at context `ctx`: encode symbol x
+FQ_DEV void idk_small(IdK &k, u32 map, u64 ctx, u32 N, u32 x) {
+  bool fresh;
+  u64 *slot = idw_small_slot(k, map, ctx, fresh);
+  if (!slot) return;
+  const u64 st = idm_small_load(slot, N, fresh);
+  u32 tot = 0, cum = 0;
+  for (u32 i = 0; i < N; ++i) { tot += idm_field(st, i); if (i < x) cum += idm_field(st, i); }
+  rc_step(k.e, idm_field(st, x), cum, tot, recip64_u16(tot));
+  idm_small_update_store(slot, st, N, x, tot);
 }
 // N-symbol model (N <= 256) in a big slot: four statistics per lane
 FQ_DEV void idk_big_encode(IdK &k, u64 *slot, u32 N, u32 x, bool fresh) {
   u64 *w = slot + 1;
-  u32 mine[4] = {0, 0, 0, 0};
   u32 tot, freq, cum = 0;
   if (fresh) {
     FQ_SYNC_MEM();
@@ -116,33 +146,22 @@ FQ_DEV void idk_big_encode(IdK &k, u64 *slot, u32 N, u32 x, bool fresh) {
     for (u32 l = FQ_LANE; l < 64; l += FQ_WAVE) {
       if (4 * l < N && 4 * l < x) {
         const u64 v = w[l];
-        for (u32 f = 0; f < 4; ++f) if (4 * l + f < x) part += (u32)((v >> (16 * f)) & 0xffff);
+        for (u32 f = 0; f < 4; ++f) if (4 * l + f < x) part += idm_field(v, f);
       }
     }
     cum = wave_sum32(part);
-    freq = (u32)((w[x >> 2] >> (16 * (x & 3))) & 0xffff);
+    freq = idm_field(w[x >> 2], x & 3);
     tot = (u32)w[64];
   }
-  (void)mine;
-  q_encode(k.e, freq, cum, tot);
+  rc_step(k.e, freq, cum, tot, recip64_u16(tot));
   // update (rc.h:41-55): stats[x] += 1, total += 1, halve everything while the total reaches 2^15
   tot += 1;
   if (FQ_LANE == 0) { w[x >> 2] += 1ull << (16 * (x & 3)); }
   FQ_SYNC_MEM();
   while (tot >= (1u << 15)) {
     u32 part = 0;
-    for (u32 l = FQ_LANE; l < 64; l += FQ_WAVE) {
-      if (4 * l < N) {
-        const u64 v = w[l];
-        u64 nv = 0;
-        for (u32 f = 0; f < 4; ++f) {
-          u32 s = (u32)((v >> (16 * f)) & 0xffff);
-          if (4 * l + f < N) { s = (s + 1) / 2; part += s; }
-          nv |= (u64)s << (16 * f);
-        }
-        w[l] = nv;
-      }
-    }
+    for (u32 l = FQ_LANE; l < 64; l += FQ_WAVE)
+      if (4 * l < N) w[l] = idm_halve_word(w[l], 4 * l, N, part);
     tot = wave_sum32(part);
     FQ_SYNC_MEM();
   }
@@ -150,22 +169,9 @@ FQ_DEV void idk_big_encode(IdK &k, u64 *slot, u32 N, u32 x, bool fresh) {
   FQ_SYNC_MEM();
 }
 FQ_DEV void idk_big(IdK &k, u32 map, u64 ctx, u32 N, u32 x) {
-  const u64 key = ((u64)map << 56) | ctx;
-  u64 h = q_hash(key) & k.cfg->big_mask;
-  for (u64 it = 0; it <= k.cfg->big_mask; ++it) {
-    u64 *p = k.big + IDK_BIG_U64 * h;
-    const u64 kk = p[0];
-    if (kk == key) { idk_big_encode(k, p, N, x, false); return; }
-    if (kk == ~0ull) {
-      if ((u64)(k.n_big + 1) * 10 >= (k.cfg->big_mask + 1) * 9) { k.err = IDK_ERR_TABLE; return; }
-      if (FQ_LANE == 0) p[0] = key;
-      k.n_big += 1;
-      idk_big_encode(k, p, N, x, true);
-      return;
-    }
-    h = (h + 1) & k.cfg->big_mask;
-  }
-  k.err = IDK_ERR_TABLE;
+  bool fresh;
+  u64 *slot = idw_big_slot(k, map, ctx, fresh);
+  if (slot) idk_big_encode(k, slot, N, x, fresh);
 }
 FQ_DEV void idk_fixed(IdK &k, u32 which, u32 N, u32 x) {   // the host initialises these at creation
   idk_big_encode(k, k.fixed + IDK_BIG_U64 * which, N, x, false);
@@ -261,7 +267,6 @@ FQ_DEV void idk_lossless(IdK &k, u32 size) {
   FQ_SYNC();
   for (u32 i = FQ_LANE; i < size; i += FQ_WAVE) sm->prev[i] = sm->cur[i];
   FQ_SYNC();
-  k.prev_size = size;
   k.cur_set = ps;
 }
 // bytes [0, size) of a line in HBM -> sm->cur / sm->cls; false if a byte is outside the 128-symbol alphabet
@@ -373,18 +378,10 @@ FQ_DEV void id_encode_body(const IdCfg &cfg, IdShared *sm, u32 tid, u32 n_reads,
   u64 first, last;
   worker_reads(tid, T, n_reads, first, last);
   IdK k;
-  k.cfg = &cfg; k.sm = sm;
-  k.e.low = 0; k.e.range = 0xff00000000000000ULL; k.e.len = 0; k.e.acc = 0; k.e.cap = cfg.out_cap; k.e.out = cfg.out + (u64)tid * cfg.out_cap; k.e.err = 0;
-  k.small = cfg.small + (u64)tid * (cfg.small_mask + 1) * 2;
-  k.big = cfg.big + (u64)tid * (cfg.big_mask + 1) * IDK_BIG_U64;
-  k.fixed = cfg.fixed + (u64)tid * IDK_FIXED * IDK_BIG_U64;
-  k.mtf = cfg.mtf + (u64)tid * cfg.mtf_cap * IDK_NAME;
-  k.n_small = cfg.state[4 * tid]; k.n_big = cfg.state[4 * tid + 1]; k.n_mtf = cfg.state[4 * tid + 2];
-  // ResetReadPrev, id.cpp:124-135
-  k.cur_set = 0; k.n_tok[0] = k.n_tok[1] = 0; k.prev_size = 0;
-  k.ctx_flags = 0; k.ctx_pe_flags = 0;
-  k.err = 0;
-  for (u64 i = first; i < last && !k.err && !k.e.err; i += paired ? 2 : 1) {
+  idw_open(k, cfg, sm, tid);
+  rc_open(k.e, cfg.out + (u64)tid * cfg.out_cap, cfg.out_cap);
+  k.n_tok[0] = k.n_tok[1] = 0;
+  for (u64 i = first; i < last && !k.err && !rc_overflowed(k.e); i += paired ? 2 : 1) {
     const u8 *p1 = cfg.ids + cfg.off[i];
     const u32 n1 = (u32)(cfg.off[i + 1] - cfg.off[i]);
     if (!paired) {
@@ -405,11 +402,10 @@ FQ_DEV void id_encode_body(const IdCfg &cfg, IdShared *sm, u32 tid, u32 n_reads,
       if (!k.err) idk_id_instrument(k, p2, n2);
     }
   }
-  for (int i = 0; i < 8; ++i) { q_put(k.e, (u8)(k.e.low >> 56)); k.e.low <<= 8; }  // End(), sub_rc.h:79-86
-  q_flush(k.e);
+  rc_end(k.e);
   if (FQ_LANE == 0) {
     cfg.lens[tid] = k.e.len;
-    cfg.state[4 * tid] = k.n_small; cfg.state[4 * tid + 1] = k.n_big; cfg.state[4 * tid + 2] = k.n_mtf;
-    if (k.err) *cfg.err = k.err; else if (k.e.err) *cfg.err = IDK_ERR_OUT;
+    idw_store_counts(k, tid);
+    if (k.err) *cfg.err = k.err; else if (rc_overflowed(k.e)) *cfg.err = IDK_ERR_OUT;
   }
 }

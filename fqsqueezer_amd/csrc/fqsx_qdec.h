@@ -17,9 +17,9 @@ struct QualDecArgs {
   u8 rev[96];          // quality_code_map_rev
 };
 
-// CRangeDecoder on wave-uniform state.  The stream is read as aligned 8-byte words, one word ahead of its use; bytes at and
-// beyond `len` read as 0 (rcd_byte, fqsx_dec.h) and words that lie wholly beyond it are not loaded.
-struct QDec { u64 low, range, buf, pos, len, cur, nxt; const u8 *in; };
+// CRangeDecoder (fqsx_rc.h) on wave-uniform state.  The stream is read as aligned 8-byte words, one word ahead of its use;
+// bytes at and beyond `len` read as 0 and words that lie wholly beyond it are not loaded.
+struct QDec { RcDec rc; u64 pos, len, cur, nxt; const u8 *in; };
 FQ_DEV u64 qd_word(const QDec &d, u64 p) {   // the word holding bytes [p, p + 8), p a multiple of 8
   if (p >= d.len) return 0;
   u64 v = uniform64(*(const u64 *)(d.in + p));
@@ -27,41 +27,20 @@ FQ_DEV u64 qd_word(const QDec &d, u64 p) {   // the word holding bytes [p, p + 8
   if (left < 8) v &= (1ull << (8 * (u32)left)) - 1ull;
   return v;
 }
-FQ_DEV u64 qd_byte(QDec &d) {
+FQ_DEV u64 rc_src_byte(QDec &d) {
   const u64 b = (d.cur >> (8 * (u32)(d.pos & 7))) & 0xff;
   ++d.pos;
   if ((d.pos & 7) == 0) { d.cur = d.nxt; d.nxt = qd_word(d, d.pos + 8); }
   return b;
 }
-FQ_DEV void qd_start(QDec &d) {  // Start(), sub_rc.h:112-125
+FQ_DEV void qd_start(QDec &d) {
   d.pos = 0;
-  d.buf = 0;
   d.cur = qd_word(d, 0);
   d.nxt = qd_word(d, 8);
-  if (d.len >= 8)
-    for (u32 i = 1; i <= 8; ++i) d.buf |= qd_byte(d) << (64 - i * 8);
-  d.low = 0;
-  d.range = 0xff00000000000000ULL;
+  rcd_start(d.rc, d, d.len);
 }
-FQ_DEV u32 qd_cum(QDec &d, u32 tot) {  // GetCumulativeFreq, sub_rc.h:127-131 (a well-formed stream gives a value below tot)
-  d.range = q_div(d.range, tot);
-  const u64 q = d.buf / d.range;   // (range > 2^56 before the division and tot < 2^16: never 0)
-  return uniform32(q > 0xffffffffull ? 0xffffffffu : (u32)q);
-}
-FQ_DEV void qd_update(QDec &d, u32 freq, u32 cum) {  // UpdateFrequency, sub_rc.h:133-151
-  const u64 Top = 0x00ffffffffffffULL, M = 0xff00000000000000ULL;
-  const u64 r = (u64)cum * d.range;
-  u64 low = d.low + r, range = d.range * freq;
-  d.buf -= r;
-  while (range <= Top) {
-    if ((low ^ (low + range)) & M) range = (low | Top) - low;
-    d.buf = (d.buf << 8) + qd_byte(d);
-    low <<= 8;
-    range <<= 8;
-  }
-  d.low = low;
-  d.range = range;
-}
+FQ_DEV u32 qd_cum(QDec &d, u32 tot) { return uniform32(rcd_cum(d.rc, tot)); }
+FQ_DEV void qd_update(QDec &d, u32 freq, u32 cum) { rcd_update(d.rc, d, freq, cum); }
 
 // The model of the current context in registers: N statistics and their total (the slot's packed u16 fields 0..N)
 #if FQ_WAVE > 1
@@ -162,24 +141,6 @@ FQ_DEV void qm_update_store(QModel &m, u32 N, u32 sym, u64 *slot, bool fresh) {
 }
 #endif
 
-// find_rc_context (quality.cpp:218-226) from probe `it0` of the sequence at slot index h: the context's slot, claimed if the
-// sequence ends at an empty one (fresh: its model does not exist yet); nullptr: no room (the host sizes the table)
-FQ_DEV u64 *qd_find(const QualCfg &cfg, u64 *tab, u64 ctx, u64 h, u64 it0, bool &fresh) {
-  fresh = false;
-  for (u64 it = it0; it <= cfg.cap_mask; ++it) {
-    u64 *p = tab + h * cfg.slot_u64;
-    const u64 k = uniform64(p[0]);
-    if (k == ~0ull) {
-      if (FQ_LANE == 0) p[0] = ctx;
-      fresh = true;
-      return p;
-    }
-    if (k == ctx) return p;
-    h = (h + 1) & cfg.cap_mask;
-  }
-  return nullptr;
-}
-
 // The home slots of the possible contexts of the next position, looked at while the current one is decoded.  Read-only:
 // only the context of the symbol that is decoded may be claimed (a claimed slot whose model is never written would later
 // pass for an existing one, and `filled` has to end equal to the encoder's).
@@ -252,7 +213,8 @@ FQ_DEV u64 *qd_open(const QualCfg &cfg, u64 *tab, u64 ctx, u32 sym, const QAhead
       it0 = 1;
     }
   }
-  if (!slot) slot = qd_find(cfg, tab, ctx, h, it0, fresh);
+  // find_rc_context (quality.cpp:218-226) from probe it0: claimed if the sequence ends at an empty slot (the host sizes the table)
+  if (!slot) slot = q_find<false>(tab, cfg.cap_mask, cfg.slot_u64, ctx, h, it0, true, fresh);
   if (!slot) return nullptr;
   if (fresh) {
     qm_fresh(m, N);

@@ -4,7 +4,7 @@
 // symbols, adder 1, halved at 2^15) kept in a per-worker open-addressed table in HBM whose slot is
 // [key | packed u16 stats | u16 total].  Included by fqsx_api.hip.
 #pragma once
-#include "fqsx_plat.h"
+#include "fqsx_rc.h"
 
 struct QualCfg {
   u32 T, mode, n_sym, bits, nctx, slot_u64;   // slot_u64 = 1 + ceil((n_sym+1)/4)
@@ -21,64 +21,40 @@ struct QualCfg {
   u8 fwd[96];          // quality_code_map_fwd
 };
 
-struct QEnc { u64 low, range, len, cap, acc; u8 *out; u32 err; };
-FQ_DEV void q_put(QEnc &e, u8 b) {   // output bytes leave as aligned 8-byte words (the stream starts at offset 0 of an aligned buffer)
-  e.acc |= (u64)b << (8 * (u32)(e.len & 7));
-  ++e.len;
-  if ((e.len & 7) == 0) {
-    if (e.len <= e.cap) ((u64 *)e.out)[(e.len >> 3) - 1] = e.acc; else e.err = 1;
-    e.acc = 0;
-  }
-}
-FQ_DEV void q_flush(QEnc &e) {
-  if (e.len > e.cap) { e.err = 1; return; }   // (a stream that ends inside the word beyond the buffer: q_put has not seen it)
-  if ((e.len & 7) && e.len < e.cap) ((u64 *)e.out)[e.len >> 3] = e.acc;
-}
-FQ_DEV u64 q_div(u64 x, u32 d) {  // exact x / d for d < 2^16 (see div_u64_small in fqsx_dev.h)
-  const double rd = 1.0 / (double)d;
-  u32 hi = (u32)(x >> 32), lo = (u32)x;
-  u32 qh = (u32)((double)hi * rd);
-  u32 ph = qh * d;
-  if (ph > hi) { --qh; ph -= d; } else if (hi - ph >= d) { ++qh; ph += d; }
-  u64 rem = ((u64)(hi - ph) << 32) | lo;
-  u64 q = (u64)((double)rem * rd);
-  u64 prod = q * d;
-  if (prod > rem) --q; else if (rem - prod >= d) ++q;
-  return ((u64)qh << 32) + q;
-}
-// CRangeEncoder::EncodeFrequency, sub_rc.h:60-77; m = floor((2^64-1) / tot): mulhi(range, m) is range / tot or one less
-FQ_DEV void q_encode_m(QEnc &e, u32 freq, u32 cum, u32 tot, u64 m) {
-  const u64 Top = 0x00ffffffffffffULL, M = 0xff00000000000000ULL;
-#ifndef FQSX_EMU
-  u64 range = __umul64hi(e.range, m);
-#else
-  u64 range = (u64)(((unsigned __int128)e.range * m) >> 64);
-#endif
-  if ((u32)e.range - (u32)range * tot >= tot) ++range;   // (remainder < 2 * tot < 2^17: the low words decide)
-  u64 low = e.low + range * cum;
-  range *= freq;
-  while (range <= Top) {
-    if ((low ^ (low + range)) & M) range = (low | Top) - low;
-    q_put(e, (u8)(low >> 56));
-    low <<= 8;
-    range <<= 8;
-  }
-  e.low = low;
-  e.range = range;
-}
-FQ_DEV void q_encode(QEnc &e, u32 freq, u32 cum, u32 tot) { q_encode_m(e, freq, cum, tot, q_div(~0ull, tot)); }
 FQ_DEV u64 q_hash(u64 h) {
   h ^= h >> 33; h *= 0xff51afd7ed558ccdULL; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ULL; h ^= h >> 33;
   return h;
+}
+// Find-or-claim of the slot of `key` in a per-worker open-addressed table of [key | words...] slots of `width` words (key
+// ~0 = empty; the layout is free: results do not depend on it), from probe `it0` of the sequence at slot index h.  An empty
+// slot ends the search: it is claimed (fresh: the caller creates its model) unless !may_claim (table at its load limit).
+// nullptr: no room.  Two flavours of the claim: wave-uniform (every lane looks for the same key, lane 0 stores it) and
+// per-lane (kCas: every lane its own key, a compare-and-swap decides between the lanes).
+template <bool kCas>
+FQ_DEV u64 *q_find(u64 *tab, u64 mask, u32 width, u64 key, u64 h, u64 it0, bool may_claim, bool &fresh) {
+  fresh = false;
+  for (u64 it = it0; it <= mask; ++it) {
+    u64 *p = tab + h * width;
+    u64 k = kCas ? p[0] : uniform64(p[0]);
+    if (k == ~0ull) {
+      if (!may_claim) return nullptr;
+      if (kCas) k = atomic_cas64(&p[0], ~0ull, key);   // (another lane's new key may get there first)
+      else if (FQ_LANE == 0) p[0] = key;
+      if (k == ~0ull) { fresh = true; return p; }
+    }
+    if (k == key) return p;
+    h = (h + 1) & mask;
+  }
+  return nullptr;
 }
 
 // One chunk of <= 64 quality symbols of a read, one position per lane.  The context of a position is its position in
 // the read plus the previous 2/6/9/10 quantised symbols (update_context, quality.cpp:209-215) -- a function of the input
 // alone, and different for every position of a read, so the look-ups, the model arithmetic and the model updates of a
 // chunk are independent of each other; only the range coder is sequential.  New contexts claim their table slot with
-// a compare-and-swap (the layout is free: results do not depend on it).
+// a compare-and-swap.  False: no room in the table.
 // lds_q[i - lq0] = quantised symbol of position i (the staged window of the read starts at position lq0)
-FQ_DEV void qual_chunk(const QualCfg &cfg, QEnc &e, u64 *tab, u32 &filled, const u8 *lds_q, u32 lq0, u32 pos0, u32 n, u32 *lds_f /*[3][64] emu only*/) {
+FQ_DEV bool qual_chunk(const QualCfg &cfg, RcEnc &e, u64 *tab, u32 &filled, const u8 *lds_q, u32 lq0, u32 pos0, u32 n, u32 *lds_f /*[3][64] emu only*/) {
   const u32 N = cfg.n_sym, W = cfg.slot_u64 - 1;
   u32 lane_f = 1, lane_c = 0, lane_t = 1;
   u64 lane_m = 0;
@@ -91,19 +67,8 @@ FQ_DEV void qual_chunk(const QualCfg &cfg, QEnc &e, u64 *tab, u32 &filled, const
     for (u32 j = i > cfg.nctx ? i - cfg.nctx : 0; j < i; ++j) hist = ((hist << cfg.bits) + lds_q[j - lq0]) & cfg.ctx_mask;
     const u64 ctx = ((u64)i << 48) + hist;
     // find_rc_context (quality.cpp:218-226): look the context up, create its model on first use
-    u64 h = q_hash(ctx) & cfg.cap_mask;
-    u64 *slot = nullptr;
-    bool fresh = false;
-    for (u64 it = 0; it <= cfg.cap_mask; ++it) {
-      u64 *p = tab + h * cfg.slot_u64;
-      u64 k = p[0];
-      if (k == ~0ull) {   // claim the empty slot (another lane's new context may get there first)
-        k = atomic_cas64(&p[0], ~0ull, ctx);
-        if (k == ~0ull) { slot = p; fresh = true; break; }
-      }
-      if (k == ctx) { slot = p; break; }
-      h = (h + 1) & cfg.cap_mask;
-    }
+    bool fresh;
+    u64 *slot = q_find<true>(tab, cfg.cap_mask, cfg.slot_u64, ctx, q_hash(ctx) & cfg.cap_mask, 0, true, fresh);
     if (!slot) { bad = true; continue; }
     n_new += fresh ? 1u : 0u;
     // the model: N 16-bit statistics and their total, packed four to a word (new model: all 1, total N; rc.h:69-74)
@@ -132,7 +97,7 @@ FQ_DEV void qual_chunk(const QualCfg &cfg, QEnc &e, u64 *tab, u32 &filled, const
       tot = (u32)((wt >> ts) & 0xffff);
     }
 #if FQ_WAVE > 1
-    lane_f = freq; lane_c = cum; lane_t = tot; lane_m = q_div(~0ull, tot);
+    lane_f = freq; lane_c = cum; lane_t = tot; lane_m = recip64_u16(tot);
 #else
     lds_f[t] = freq; lds_f[64 + t] = cum; lds_f[128 + t] = tot;
 #endif
@@ -164,20 +129,21 @@ FQ_DEV void qual_chunk(const QualCfg &cfg, QEnc &e, u64 *tab, u32 &filled, const
       slot[1 + tw] = (wt & ~(0xffffull << ts)) | ((u64)ntot << ts);
     }
   }
-  if (wave_any(bad)) { e.err = 2; return; }
+  if (wave_any(bad)) return false;
   filled += wave_sum32(n_new);
-  if ((u64)filled * 10 >= (cfg.cap_mask + 1) * 9) { e.err = 2; return; }   // (the host sizes the table for every symbol of the block)
+  if ((u64)filled * 10 >= (cfg.cap_mask + 1) * 9) return false;   // (the host sizes the table for every symbol of the block)
   // the range coder, in position order
 #if FQ_WAVE > 1
   for (u32 t = 0; t < n; ++t) {
     const u64 m = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(lane_m >> 32), t) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)lane_m, t);
-    q_encode_m(e, (u32)__builtin_amdgcn_readlane((int)lane_f, t), (u32)__builtin_amdgcn_readlane((int)lane_c, t),
+    rc_step(e, (u32)__builtin_amdgcn_readlane((int)lane_f, t), (u32)__builtin_amdgcn_readlane((int)lane_c, t),
                (u32)__builtin_amdgcn_readlane((int)lane_t, t), m);
   }
 #else
-  for (u32 t = 0; t < n; ++t) q_encode(e, lds_f[t], lds_f[64 + t], lds_f[128 + t]);
+  for (u32 t = 0; t < n; ++t) rc_step(e, lds_f[t], lds_f[64 + t], lds_f[128 + t], recip64_u16(lds_f[128 + t]));
 #endif
   FQ_SYNC_MEM();   // the models written here are read by the next chunks (same wave, other lanes)
+  return true;
 }
 
 // worker `tid` codes the qualities of its reads of the block (application.cpp:641, quality.cpp:152-175)
@@ -185,8 +151,9 @@ FQ_DEV void qual_encode_body(const QualCfg &cfg, u8 *lds_q /*[4096 + 96]*/, u32 
   const u64 T = cfg.T;
   u64 first, last;
   worker_reads(tid, T, n_reads, first, last);
-  QEnc e;
-  e.low = 0; e.range = 0xff00000000000000ULL; e.len = 0; e.acc = 0; e.cap = cfg.out_cap; e.out = cfg.out + (u64)tid * cfg.out_cap; e.err = 0;
+  RcEnc e;
+  rc_open(e, cfg.out + (u64)tid * cfg.out_cap, cfg.out_cap);
+  u32 err = 0;   // 1: the output buffer, 2: the context table
   u64 *tab = cfg.tab + (u64)tid * (cfg.cap_mask + 1) * cfg.slot_u64;
   u32 filled = cfg.filled[tid];
   u8 *lds_fwd = lds_q + 4096;   // quality_code_map_fwd next to the staged symbols
@@ -198,23 +165,24 @@ FQ_DEV void qual_encode_body(const QualCfg &cfg, u8 *lds_q /*[4096 + 96]*/, u32 
   static thread_local u32 lds_f_[192];
   u32 *lds_f = lds_f_;
 #endif
-  for (u64 r = first; r < last && !e.err; ++r) {
+  for (u64 r = first; r < last && !err && !rc_overflowed(e); ++r) {
     const u8 *q = cfg.quals + cfg.off[r];
     const u32 size = (u32)(cfg.off[r + 1] - cfg.off[r]);
     // the read's symbols are staged in LDS in windows of 4032 positions plus the 64 before them (contexts reach back)
-    for (u32 w0 = 0; w0 < size && !e.err; w0 += 4032) {
+    for (u32 w0 = 0; w0 < size && !err && !rc_overflowed(e); w0 += 4032) {
       const u32 lq0 = w0 ? w0 - 64 : 0, wend = size - w0 < 4032 ? size : w0 + 4032;
       FQ_SYNC();
       for (u32 i = lq0 + FQ_LANE; i < wend; i += FQ_WAVE) lds_q[i - lq0] = lds_fwd[(u8)(q[i] - 33) < 96 ? (u8)(q[i] - 33) : 95];
       FQ_SYNC();
-      for (u32 pos0 = w0; pos0 < wend && !e.err; pos0 += 64) qual_chunk(cfg, e, tab, filled, lds_q, lq0, pos0, wend - pos0 < 64 ? wend - pos0 : 64, lds_f);
+      for (u32 pos0 = w0; pos0 < wend && !err && !rc_overflowed(e); pos0 += 64)
+        if (!qual_chunk(cfg, e, tab, filled, lds_q, lq0, pos0, wend - pos0 < 64 ? wend - pos0 : 64, lds_f)) err = 2;
     }
   }
-  for (int i = 0; i < 8; ++i) { q_put(e, (u8)(e.low >> 56)); e.low <<= 8; }  // End(), sub_rc.h:79-86
-  q_flush(e);
+  rc_end(e);
+  if (rc_overflowed(e)) err = 1;
   if (FQ_LANE == 0) {
     cfg.lens[tid] = e.len;
     cfg.filled[tid] = filled;
-    if (e.err) *cfg.err = e.err;
+    if (err) *cfg.err = err;
   }
 }
