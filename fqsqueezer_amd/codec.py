@@ -428,3 +428,134 @@ class QualCodec:
             self.close()
         except Exception:
             pass
+
+
+FASTQ_PASSES = ["count", "scan_tiles", "index", "lengths", "scan_rtiles", "offsets", "gather"]
+
+
+class FastqParser:
+    """FASTQ text to columns on the GPU (fqsx_fastq_*): one chunk of text per call."""
+
+    def __init__(self, device: int = 0, lib_path: Optional[str] = None, max_chunk_bytes: int = 0):
+        L = self._lib = load_library(lib_path)
+        L.fqsx_fastq_create.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.fqsx_fastq_destroy.argtypes = [C.c_void_p]
+        L.fqsx_fastq_destroy.restype = None
+        L.fqsx_fastq_max_chunk.argtypes = [C.c_void_p]
+        L.fqsx_fastq_max_chunk.restype = C.c_uint64
+        L.fqsx_fastq_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.fqsx_fastq_columns.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+        L.fqsx_fastq_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        L.fqsx_fastq_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._h = C.c_void_p()
+        rc = L.fqsx_fastq_create(device, max_chunk_bytes, C.byref(self._h))
+        if rc:
+            raise FqsxError(f"fqsx_fastq_create: {rc}: {L.fqsx_last_error().decode()}")
+        self.max_chunk_bytes = int(L.fqsx_fastq_max_chunk(self._h))
+
+    def index(self, text: np.ndarray) -> dict:
+        """Upload a chunk (uint8 array) and find its records: sizes for columns()."""
+        a = (C.c_uint64 * 8)()
+        rc = self._lib.fqsx_fastq_index(self._h, text.ctypes.data if len(text) else None, len(text), a)
+        if rc:
+            raise FqsxError(f"fqsx_fastq_index: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return {"records": int(a[0]), "consumed": int(a[1]), "id_bytes": int(a[2]), "bases": int(a[3]), "quals": int(a[4]),
+                "max_id_line": int(a[5]), "length_mismatch": bool(a[6]), "line_feeds": int(a[7])}
+
+    def columns(self, info: dict):
+        """(ids, id_off, bases, read_off, quals, qual_off, plus_len) of the chunk indexed last."""
+        n = info["records"]
+        ids, bases, quals = (np.empty(info[k], dtype=np.uint8) for k in ("id_bytes", "bases", "quals"))
+        id_off, read_off, qual_off = (np.zeros(n + 1, dtype=np.uint64) for _ in range(3))
+        plus_len = np.empty(n, dtype=np.uint32)
+        rc = self._lib.fqsx_fastq_columns(self._h, ids.ctypes.data, id_off.ctypes.data, bases.ctypes.data, read_off.ctypes.data,
+                                          quals.ctypes.data, qual_off.ctypes.data, plus_len.ctypes.data)
+        if rc:
+            raise FqsxError(f"fqsx_fastq_columns: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return ids, id_off, bases, read_off, quals, qual_off, plus_len
+
+    def set_profiling(self, on: bool) -> None:
+        self._lib.fqsx_fastq_set_profiling(self._h, int(on))
+
+    def kernel_times(self) -> dict:
+        a = (C.c_double * 14)()
+        self._lib.fqsx_fastq_kernel_times(self._h, a)
+        return {name: {"ms": a[k], "launches": int(a[7 + k])} for k, name in enumerate(FASTQ_PASSES)}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.fqsx_fastq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _chunk_source(src):
+    """readinto-style reader over a path or over text already in memory (bytes / uint8 array)"""
+    if isinstance(src, (str, os.PathLike)):
+        f = open(src, "rb", buffering=0)
+        return f.readinto, f.close
+    data = np.frombuffer(src, dtype=np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.ascontiguousarray(src, dtype=np.uint8)
+    pos = [0]
+
+    def readinto(view) -> int:
+        k = min(len(view), len(data) - pos[0])
+        view[:k] = data[pos[0]:pos[0] + k]
+        pos[0] += k
+        return k
+    return readinto, lambda: None
+
+
+def parse_fastq(text_or_path, device: int = 0, lib_path: Optional[str] = None, max_chunk_bytes: int = 0, stats: Optional[dict] = None,
+                profile: bool = False):
+    """FASTQ text (bytes / uint8 array) or a file (path) to hostpipe.Columns, parsed on the GPU chunk by chunk: a file is read in
+    chunk-sized pieces into one reused buffer, the partial record at the end of a chunk is carried to the front of the next, and a
+    chunk that holds no complete record doubles the chunk size.  What follows the last complete record (the reference drops an
+    unterminated last record too) is not returned; its size is stats["tail_bytes"].  stats: also "chunks", "consumed",
+    "max_id_line", "length_mismatch" and -- profile -- "kernels"."""
+    from . import hostpipe as hp
+    p = FastqParser(device, lib_path, max_chunk_bytes)
+    readinto, close = _chunk_source(text_or_path)
+    parts, n_chunks, consumed, max_id, mismatch = [], 0, 0, 0, False
+    try:
+        p.set_profiling(profile)
+        size = p.max_chunk_bytes
+        buf = np.empty(size, dtype=np.uint8)
+        have, eof = 0, False
+        while True:
+            while have < size and not eof:   # (a raw file may return fewer bytes than asked for)
+                k = readinto(memoryview(buf)[have:size])
+                if not k:
+                    eof = True
+                have += k or 0
+            if have == 0:
+                break
+            info = p.index(buf[:have])
+            n_chunks += 1
+            if info["records"]:
+                parts.append(p.columns(info))
+                max_id = max(max_id, info["max_id_line"])
+                mismatch |= info["length_mismatch"]
+                used = info["consumed"]
+                consumed += used
+                buf[:have - used] = buf[used:have]   # the partial record goes to the front of the next chunk
+                have -= used
+            elif not eof:   # not one complete record in the chunk: a longer one
+                if 2 * size >= 1 << 32:
+                    raise FqsxError("a FASTQ record of 2 GiB or more")
+                size *= 2
+                buf = np.concatenate([buf[:have], np.empty(size - have, dtype=np.uint8)])
+            if eof:   # (the chunk held everything that was left: what it did not consume is no record)
+                break
+        if stats is not None:
+            stats.update(chunks=n_chunks, consumed=consumed, tail_bytes=have, max_id_line=max_id, length_mismatch=mismatch)
+            if profile:
+                stats["kernels"] = p.kernel_times()
+    finally:
+        close()
+        p.close()
+    return hp.Columns.from_chunks(parts)

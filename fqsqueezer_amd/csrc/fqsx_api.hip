@@ -2981,6 +2981,157 @@ extern "C" int fqsx_sort_order(const uint8_t *bases, const uint64_t *read_off, u
   return fqsx_sort_order_batched(bases, read_off, n_reads, device, 0, order_out, bin_start, nullptr);
 }
 
+// =======================================================================================================
+// FASTQ text -> columns (csrc/fqsx_fastq.h): what `fqs e` does first, reads_block.h:35-76 / io.h:451-482
+// =======================================================================================================
+#include "fqsx_fastq.h"
+
+enum { FQ_PASS_COUNT = 0, FQ_PASS_SCAN_TILES, FQ_PASS_INDEX, FQ_PASS_LENGTHS, FQ_PASS_SCAN_RTILES, FQ_PASS_OFFSETS, FQ_PASS_GATHER, FQ_N_PASS };
+
+struct fqsx_fastq : DevCtx {
+  u64 max_chunk = 0;
+  u8 *d_text = nullptr; u64 text_cap = 0;
+  u32 *d_tile_cnt = nullptr; u64 tile_cap = 0;
+  u64 *d_tile_pre = nullptr; u64 tile_pre_cap = 0;
+  u64 *d_line_end = nullptr; u64 lf_cap = 0;
+  u32 *d_len = nullptr; u64 len_cap = 0;          // [4][len_cap]
+  u32 *d_rt = nullptr; u64 rt_cap = 0;            // [5][n_rtiles] inside rt_cap tiles
+  u64 *d_rt_pre = nullptr; u64 rt_pre_cap = 0;    // [3][n_rtiles + 1]
+  u64 *d_off = nullptr; u64 off_cap = 0;          // [3][off_cap]
+  u8 *d_col = nullptr; u64 col_cap = 0;           // ids, bases, quals back to back
+  u64 *d_summary = nullptr;                       // [8]
+  FqCfg cfg;                                      // the chunk indexed last
+  u64 sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // ... and its summary (FQ_SUM_*)
+  bool indexed = false;
+  double pass_ms[FQ_N_PASS] = {0, 0, 0, 0, 0, 0, 0};
+  u64 pass_n[FQ_N_PASS] = {0, 0, 0, 0, 0, 0, 0};
+};
+
+// one parser kernel on the handle's chunk, its time (while profiling) booked under `pass`
+#define FQ_LAUNCH(h, pass, kern, grid)                      \
+  do {                                                      \
+    const double t0_ = (h)->k_ms[2];                        \
+    LAUNCH(h, 2, kern, grid, 256, (h)->cfg);                \
+    (h)->pass_ms[pass] += (h)->k_ms[2] - t0_;               \
+    (h)->pass_n[pass] += 1;                                 \
+  } while (0)
+
+extern "C" {
+
+void fqsx_fastq_destroy(fqsx_fastq *h) {
+  if (!h) return;
+  dev_close(h);
+  delete h;
+}
+
+int fqsx_fastq_create(int device, uint64_t max_chunk_bytes, fqsx_fastq **out) {
+  if (!out) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (max_chunk_bytes >> 32) { g_err = "max_chunk_bytes must be below 4 GiB (field lengths inside a chunk are 32-bit)"; return FQSX_E_ARG; }
+  fqsx_fastq *h = new fqsx_fastq();
+  int rc = dev_open(h, device);
+  if (rc) { delete h; return rc; }
+  h->max_chunk = max_chunk_bytes ? max_chunk_bytes : 256ull << 20;
+  memset(&h->cfg, 0, sizeof(h->cfg));
+  void *p = nullptr;
+  if ((rc = dalloc(h, &p, 8 * sizeof(u64), true))) { fqsx_fastq_destroy(h); return rc; }
+  h->d_summary = (u64 *)p;
+  *out = h;
+  return FQSX_OK;
+}
+
+uint64_t fqsx_fastq_max_chunk(fqsx_fastq *h) { return h ? h->max_chunk : 0; }
+
+int fqsx_fastq_index(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t out[8]) {
+  if (!h || !out || (n && !text)) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (n >> 32) { g_err = "a chunk of FASTQ text must be below 4 GiB: parse the file chunk by chunk"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(h));
+  h->indexed = false;
+  for (u32 k = 0; k < 8; ++k) out[k] = h->sum[k] = 0;
+  FqCfg &c = h->cfg;
+  memset(&c, 0, sizeof(c));
+  c.n = n;
+  c.n_tiles = (u32)((n + FQSX_FQ_TILE - 1) / FQSX_FQ_TILE);
+  c.summary = h->d_summary;
+  if (n == 0) { h->indexed = true; return FQSX_OK; }
+  DEVCHK(dfit(h, h->d_text, h->text_cap, n, n, 1));
+  DEVCHK(dfit(h, h->d_tile_cnt, h->tile_cap, c.n_tiles, c.n_tiles, sizeof(u32)));
+  DEVCHK(dfit(h, h->d_tile_pre, h->tile_pre_cap, (u64)c.n_tiles + 1, (u64)c.n_tiles + 1, sizeof(u64)));
+  DEVCHK(h2d(h, h->d_text, text, n));
+  c.text = h->d_text; c.tile_cnt = h->d_tile_cnt; c.tile_pre = h->d_tile_pre;
+  FQ_LAUNCH(h, FQ_PASS_COUNT, k_fq_count, c.n_tiles);
+  FQ_LAUNCH(h, FQ_PASS_SCAN_TILES, k_fq_scan_tiles, 1);
+  u64 n_lf = 0;
+  DEVCHK(d2h_sync(h, &n_lf, h->d_summary + FQ_SUM_LINE_FEEDS, sizeof(u64)));
+  if (n_lf > n) { g_err = "line feed count beyond the chunk's size"; return FQSX_E_DEVICE; }
+  c.n_lf = n_lf;
+  c.n_rec = n_lf / 4;
+  out[FQ_SUM_LINE_FEEDS] = h->sum[FQ_SUM_LINE_FEEDS] = n_lf;
+  if (c.n_rec == 0) { h->indexed = true; return FQSX_OK; }   // (nothing consumed: the caller carries the text on)
+  DEVCHK(dfit(h, h->d_line_end, h->lf_cap, n_lf, n_lf + n_lf / 8, sizeof(u64)));
+  c.line_end = h->d_line_end;
+  FQ_LAUNCH(h, FQ_PASS_INDEX, k_fq_index, c.n_tiles);
+  c.n_rtiles = (u32)((c.n_rec + FQSX_FQ_RTILE - 1) / FQSX_FQ_RTILE);
+  DEVCHK(dfit(h, h->d_len, h->len_cap, c.n_rec, c.n_rec + c.n_rec / 8, 4 * sizeof(u32)));
+  DEVCHK(dfit(h, h->d_rt, h->rt_cap, c.n_rtiles, (u64)c.n_rtiles + c.n_rtiles / 8, 5 * sizeof(u32)));
+  DEVCHK(dfit(h, h->d_rt_pre, h->rt_pre_cap, (u64)c.n_rtiles + 1, (u64)c.n_rtiles + c.n_rtiles / 8 + 1, 3 * sizeof(u64)));
+  c.len = h->d_len; c.len_stride = h->len_cap;
+  c.rt = h->d_rt; c.rt_pre = h->d_rt_pre;
+  FQ_LAUNCH(h, FQ_PASS_LENGTHS, k_fq_lengths, c.n_rtiles);
+  FQ_LAUNCH(h, FQ_PASS_SCAN_RTILES, k_fq_scan_rtiles, 1);
+  DEVCHK(d2h_sync(h, h->sum, h->d_summary, sizeof(h->sum)));
+  if (h->sum[FQ_SUM_RECORDS] != c.n_rec || h->sum[FQ_SUM_CONSUMED] > n ||
+      h->sum[FQ_SUM_ID_BYTES] + h->sum[FQ_SUM_BASES] + h->sum[FQ_SUM_QUALS] > n) {
+    g_err = "inconsistent chunk summary";
+    return FQSX_E_DEVICE;
+  }
+  for (u32 k = 0; k < 8; ++k) out[k] = h->sum[k];
+  h->indexed = true;
+  return FQSX_OK;
+}
+
+int fqsx_fastq_columns(fqsx_fastq *h, uint8_t *ids, uint64_t *id_off, uint8_t *bases, uint64_t *read_off, uint8_t *quals,
+                       uint64_t *qual_off, uint32_t *plus_len) {
+  if (!h) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (!h->indexed) { g_err = "fqsx_fastq_columns without a successful fqsx_fastq_index before it"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(h));
+  FqCfg &c = h->cfg;
+  if (c.n_rec == 0) {
+    if (id_off) id_off[0] = 0;
+    if (read_off) read_off[0] = 0;
+    if (qual_off) qual_off[0] = 0;
+    return FQSX_OK;
+  }
+  const u64 nb[3] = {h->sum[FQ_SUM_ID_BYTES], h->sum[FQ_SUM_BASES], h->sum[FQ_SUM_QUALS]};
+  DEVCHK(dfit(h, h->d_off, h->off_cap, c.n_rec + 1, c.n_rec + c.n_rec / 8 + 1, 3 * sizeof(u64)));
+  DEVCHK(dfit(h, h->d_col, h->col_cap, nb[0] + nb[1] + nb[2], nb[0] + nb[1] + nb[2], 1));
+  c.off = h->d_off; c.off_stride = h->off_cap;
+  c.col[0] = h->d_col; c.col[1] = c.col[0] + nb[0]; c.col[2] = c.col[1] + nb[1];
+  for (u32 q = 0; q < 3; ++q) c.col_n[q] = nb[q];
+  FQ_LAUNCH(h, FQ_PASS_OFFSETS, k_fq_offsets, c.n_rtiles);
+  FQ_LAUNCH(h, FQ_PASS_GATHER, k_fq_gather, (u32)((c.n_rec + 4 * FQSX_FQ_GBATCH - 1) / (4 * FQSX_FQ_GBATCH)));
+  u8 *const hc[3] = {ids, bases, quals};
+  u64 *const ho[3] = {id_off, read_off, qual_off};
+  for (u32 q = 0; q < 3; ++q) {
+    if (hc[q] && nb[q]) DEVCHK(d2h(h, hc[q], c.col[q], nb[q]));
+    if (ho[q]) DEVCHK(d2h(h, ho[q], c.off + q * c.off_stride, (c.n_rec + 1) * sizeof(u64)));
+  }
+  if (plus_len) DEVCHK(d2h(h, plus_len, c.len + FQ_LEN_PLUS * c.len_stride, c.n_rec * sizeof(u32)));
+  return dev_sync(h);
+}
+
+int fqsx_fastq_set_profiling(fqsx_fastq *h, int enable) {
+  if (!h) return FQSX_E_ARG;
+  h->profiling = enable != 0;
+  return FQSX_OK;
+}
+int fqsx_fastq_kernel_times(fqsx_fastq *h, double out[14]) {
+  if (!h || !out) return FQSX_E_ARG;
+  for (u32 k = 0; k < FQ_N_PASS; ++k) { out[k] = h->pass_ms[k]; out[FQ_N_PASS + k] = (double)h->pass_n[k]; }
+  return FQSX_OK;
+}
+
+}  // extern "C"
+
 #ifdef FQSX_EMU   // the emulation build is one translation unit
 #include "fqsx_k_se.hip"
 #include "fqsx_k_pe.hip"

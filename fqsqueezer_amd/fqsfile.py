@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DnaCodec, IdCodec, MetaCodec, QualCodec, sort_order
+from .codec import DnaCodec, IdCodec, MetaCodec, QualCodec, parse_fastq, sort_order
 
 
 def _gpu_groups(rec: hp.Records, device: int, lib_path: Optional[str]):
@@ -139,3 +139,114 @@ def compress_records_pe(rec1: hp.Records, rec2: hp.Records, threads: int, order:
     if as_blocks:
         return header, encode_blocks(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, stats=stats, gpu_ids=gpu_ids)
     return _encode(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, gpu_ids)
+
+
+_ID_SEPARATORS = np.zeros(256, dtype=bool)
+_ID_SEPARATORS[list(b" :._/-|=#")] = True
+
+
+def _id_columns_fit_the_kernel(cols: hp.Columns, max_id_line: int) -> bool:
+    """_ids_fit_the_kernel on columns: the parser's longest id line (it counts the line feed) and one pass over the id bytes."""
+    if max_id_line - 1 > _ID_LINE_MAX:
+        return False
+    off = cols.id_off.view(np.int64)
+    seps = np.zeros(len(cols.ids) + 1, dtype=np.int64)
+    np.cumsum(_ID_SEPARATORS[cols.ids], out=seps[1:])
+    return not bool(((np.diff(off) - 1 > 64) & (seps[off[1:]] - seps[off[:-1]] >= _ID_TOKENS_MAX // 2)).any())
+
+
+def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: str = "s", genome_size_mbp: int = 3100,
+                   quality_mode: str = "illumina_8", id_mode: str = "instrument", quality_thr: int = 20, device: int = 0,
+                   lib_path: Optional[str] = None, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None,
+                   max_chunk_bytes: int = 0):
+    """`fqs e` on FASTQ files: `-s` with one input, `-p` with two (text as bytes / uint8 array, or a path; the defaults are the
+    reference's, params.h:53-78).  The text is parsed on the GPU into columns (codec.parse_fastq), the sort pre-pass runs on the
+    base column, and the blocks are cut from the columns with vectorised gathers.  Returns what compress_records* return.
+    ValueError: a record whose quality line differs in length from its base line; mate files with different numbers of records.
+    gpu_ids: see compress_records.  stats: "parse" (one dict per input), "gpu_ids" (the choice made) and what encode_blocks adds."""
+    paired = text2_or_path2 is not None
+    cols, parse_stats = [], []
+    for src in (text_or_path, text2_or_path2)[:2 if paired else 1]:
+        st = {}
+        cols.append(parse_fastq(src, device=device, lib_path=lib_path, max_chunk_bytes=max_chunk_bytes, stats=st))
+        parse_stats.append(st)
+        if st["length_mismatch"]:
+            raise ValueError("a record's quality line differs in length from its base line (input %d)" % len(cols))
+    if paired and len(cols[0]) != len(cols[1]):
+        raise ValueError("the mate files hold different numbers of records: %d and %d" % (len(cols[0]), len(cols[1])))
+    if gpu_ids is None:
+        gpu_ids = id_mode == "none" or all(_id_columns_fit_the_kernel(c, st["max_id_line"]) for c, st in zip(cols, parse_stats))
+    if stats is not None:
+        stats["parse"], stats["gpu_ids"] = parse_stats, gpu_ids
+    mode = ("pe_" if paired else "se_") + ("sorted" if order == "s" else "original")
+    header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
+    c1 = cols[0]
+    groups = sort_order(c1.bases, c1.read_off, device=device, lib_path=lib_path) if order == "s" else None   # mates follow mate 1's order
+    if paired:
+        c2 = cols[1]
+        s1, s2 = c1.record_sizes(), c2.record_sizes()
+
+        def arrays(idx):
+            bases, off = c1.block_pe(c2, idx)
+            ids, id_off = c1.ids_of_pe(c2, idx) if id_mode != "none" else (None, None)
+            quals = c1.quals_of_pe(c2, idx)[0] if quality_mode != "none" else None
+            return bases, off, ids, id_off, quals
+
+        def sizes_of(idx):
+            z = np.empty(2 * len(idx), dtype=np.int64)
+            z[0::2], z[1::2] = s1[idx], s2[idx]
+            return z
+
+        blocks = hp.form_blocks_pe(c1, c2, mode, groups=groups)
+    else:
+        sizes = c1.record_sizes()
+
+        def arrays(idx):
+            bases, off = c1.block(idx)
+            ids, id_off = c1.ids_of(idx) if id_mode != "none" else (None, None)
+            quals = c1.quals_of(idx)[0] if quality_mode != "none" else None
+            return bases, off, ids, id_off, quals
+
+        def sizes_of(idx):
+            return sizes[idx]
+
+        blocks = hp.form_blocks(c1, mode, groups=groups)
+    gen = encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids)
+    return (header, gen) if as_blocks else hp.write_fqs(header, gen)
+
+
+_QM = {"o": "lossless", "8": "illumina_8", "4": "illumina_4", "2": "binary", "n": "none"}   # fqsqueezer.cpp:157-191
+_IM = {"o": "lossless", "i": "instrument", "n": "none"}
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m fqsqueezer_amd.fqsfile", description="compress FASTQ files to a .fqs file on the GPU (`fqs e`)")
+    ap.add_argument("cmd", choices=["e"])
+    ends = ap.add_mutually_exclusive_group()
+    ends.add_argument("-s", dest="paired", action="store_false", help="single-end: one input file (default)")
+    ends.add_argument("-p", dest="paired", action="store_true", help="paired-end: two input files")
+    ap.add_argument("-t", type=int, default=1, help="worker threads of the bitstream, 1..64")
+    ap.add_argument("-gs", type=int, default=3100, help="genome size in Mbp, 1..32768")
+    ap.add_argument("-om", choices=["o", "s"], default="s", help="read order: original / sorted")
+    ap.add_argument("-qm", choices=list(_QM), default="8", help="quality mode")
+    ap.add_argument("-qt", type=int, default=20, help="quality threshold of -qm 2")
+    ap.add_argument("-im", choices=list(_IM), default="i", help="id mode")
+    ap.add_argument("-out", default="output.fqs")
+    ap.add_argument("-device", type=int, default=0)
+    ap.add_argument("-lib", default=None, help="path of the library to load (default: the package's libfqsx.so)")
+    ap.add_argument("inputs", nargs="+")
+    a = ap.parse_args(argv)
+    if len(a.inputs) != (2 if a.paired else 1):
+        ap.error("-p takes two input files, -s one")
+    header, blocks = compress_fastq(a.inputs[0], a.inputs[1] if a.paired else None, threads=min(max(a.t, 1), 64), order=a.om,
+                                    genome_size_mbp=min(max(a.gs, 1), 32768), quality_mode=_QM[a.qm], id_mode=_IM[a.im], quality_thr=a.qt,
+                                    device=a.device, lib_path=a.lib, as_blocks=True)
+    with open(a.out, "wb") as f:
+        for chunk in hp.fqs_chunks(header, blocks):   # block by block: the file is never held whole
+            f.write(chunk)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -410,3 +410,103 @@ def qual_arrays_pe(rec1: Records, rec2: Records, idx: np.ndarray) -> Tuple[np.nd
     off = np.zeros(len(parts) + 1, dtype=np.uint64)
     off[1:] = np.cumsum([len(x) for x in parts])
     return np.frombuffer(b"".join(parts), dtype=np.uint8), off
+
+
+# ----------------------------------------------------------------------------------------
+# FASTQ records as the GPU parser delivers them (codec.parse_fastq)
+def _segments(off: np.ndarray, idx: np.ndarray):
+    """(lengths, source index of every byte) of the segments [off[i], off[i + 1]), i in idx, back to back"""
+    off = off.view(np.int64)
+    ln = off[idx + 1] - off[idx]
+    at = np.zeros(len(idx) + 1, dtype=np.int64)
+    at[1:] = np.cumsum(ln)
+    return ln, np.repeat(off[idx] - at[:-1], ln) + np.arange(int(at[-1]), dtype=np.int64)
+
+
+def _gather(src: np.ndarray, off: np.ndarray, idx: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    idx = np.asarray(idx, dtype=np.int64)
+    ln, at = _segments(off, idx)
+    out_off = np.zeros(len(idx) + 1, dtype=np.uint64)
+    out_off[1:] = np.cumsum(ln)
+    return src[at], out_off
+
+
+def _gather_pe(src1: np.ndarray, off1: np.ndarray, src2: np.ndarray, off2: np.ndarray, idx: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """the segments of two columns alternately: mate 1 of idx[0], mate 2 of idx[0], mate 1 of idx[1], ..."""
+    idx = np.asarray(idx, dtype=np.int64)
+    (l1, a1), (l2, a2) = _segments(off1, idx), _segments(off2, idx)
+    ln = np.empty(2 * len(idx), dtype=np.int64)
+    ln[0::2], ln[1::2] = l1, l2
+    out_off = np.zeros(2 * len(idx) + 1, dtype=np.uint64)
+    out_off[1:] = np.cumsum(ln)
+    out = np.empty(int(out_off[-1]), dtype=np.uint8)
+    start = out_off[:-1].view(np.int64)
+    for m, (l, a, src) in enumerate(((l1, a1, src1), (l2, a2, src2))):
+        own = np.zeros(len(idx) + 1, dtype=np.int64)
+        own[1:] = np.cumsum(l)
+        out[np.repeat(start[m::2] - own[:-1], l) + np.arange(int(own[-1]), dtype=np.int64)] = src[a]
+    return out, out_off
+
+
+@dataclass
+class Columns:
+    """The records of a FASTQ file column-wise: every field of every record back to back in one uint8 array, with n + 1
+    offsets (uint64).  ids: the id lines each with its line feed (read_desc_t::id_len counts it).  plus_len: per-record
+    length of the separator line, None when every one is a bare `+`.  qual_off is read_off itself unless a record's
+    quality line differs in length from its base line (such a file is refused by fqsfile.compress_fastq)."""
+    ids: np.ndarray
+    id_off: np.ndarray
+    bases: np.ndarray
+    read_off: np.ndarray
+    quals: np.ndarray
+    plus_len: Optional[np.ndarray] = None
+    qual_off: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        if self.qual_off is None:
+            self.qual_off = self.read_off
+
+    @classmethod
+    def from_chunks(cls, parts) -> "Columns":
+        """parts: (ids, id_off, bases, read_off, quals, qual_off, plus_len) per parsed chunk, offsets starting at 0"""
+        def col(k):
+            return np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, dtype=np.uint8)
+
+        def offs(k):
+            out, base = [np.zeros(1, dtype=np.uint64)], np.uint64(0)
+            for p in parts:
+                out.append(p[k][1:] + base)
+                base = base + p[k][-1]
+            return np.concatenate(out)
+
+        pl = np.concatenate([p[6] for p in parts]) if parts else np.zeros(0, dtype=np.uint32)
+        read_off, qual_off = offs(3), offs(5)
+        return cls(col(0), offs(1), col(2), read_off, col(4), None if bool((pl == 1).all()) else pl.astype(np.int64),
+                   read_off if np.array_equal(read_off, qual_off) else qual_off)
+
+    def __len__(self) -> int:
+        return len(self.read_off) - 1
+
+    def record_sizes(self) -> np.ndarray:
+        """read_size(), defs.h:79-81: all four lines incl. their EOLs (= Records.record_sizes())."""
+        pl = 1 if self.plus_len is None else np.asarray(self.plus_len, dtype=np.int64)
+        return np.diff(self.id_off.view(np.int64)) + np.diff(self.read_off.view(np.int64)) + 1 + pl + 1 + np.diff(self.qual_off.view(np.int64)) + 1
+
+    # what block_arrays / id_arrays / qual_arrays (and their _pe forms, with the mate file's Columns) give for the same reads
+    def block(self, idx) -> Tuple[np.ndarray, np.ndarray]:
+        return _gather(self.bases, self.read_off, idx)
+
+    def ids_of(self, idx) -> Tuple[np.ndarray, np.ndarray]:
+        return _gather(self.ids, self.id_off, idx)
+
+    def quals_of(self, idx) -> Tuple[np.ndarray, np.ndarray]:
+        return _gather(self.quals, self.qual_off, idx)
+
+    def block_pe(self, mate2: "Columns", idx) -> Tuple[np.ndarray, np.ndarray]:
+        return _gather_pe(self.bases, self.read_off, mate2.bases, mate2.read_off, idx)
+
+    def ids_of_pe(self, mate2: "Columns", idx) -> Tuple[np.ndarray, np.ndarray]:
+        return _gather_pe(self.ids, self.id_off, mate2.ids, mate2.id_off, idx)
+
+    def quals_of_pe(self, mate2: "Columns", idx) -> Tuple[np.ndarray, np.ndarray]:
+        return _gather_pe(self.quals, self.qual_off, mate2.quals, mate2.qual_off, idx)

@@ -260,3 +260,19 @@ def synth_mixed_lengths(n_reads: int = 1500, genome_len: int = 40000, seed: int 
         seqs.append(s.tobytes())
         quals.append(b"I" * L)
     return ids, seqs, quals
+
+
+def fastq_text(ids, seqs, quals, plus_id_every: int = 0, final_eol: bool = True) -> bytes:
+    """FASTQ text of the records; plus_id_every = k > 0: every k-th record's separator line repeats the id (`+rag.7`);
+    final_eol = False: the last line lacks its line feed."""
+    out = []
+    for i, (name, s, q) in enumerate(zip(ids, seqs, quals)):
+        sep = b"+" + bytes(name)[1:] if plus_id_every and i % plus_id_every == 0 else b"+"
+        out.append(bytes(name) + b"\n" + bytes(s) + b"\n" + sep + b"\n" + bytes(q) + b"\n")
+    text = b"".join(out)
+    return text if final_eol or not text else text[:-1]
+
+
+def synth_c25_text() -> bytes:
+    """2000 ragged reads, every third separator line carries the id, the text ends without a line feed (tests/golden/c25_*)"""
+    return fastq_text(*synth_ragged(2000, 50000, 25), plus_id_every=3, final_eol=False)

@@ -329,6 +329,34 @@ int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *read_off, uint
  * result in idx_out.  Same libstdc++ algorithm on the same initial order = same order of equal reads. */
 int fqsx_sort_bin(const uint8_t *bases, const uint64_t *off, const uint32_t *idx_in, uint32_t n, uint32_t *idx_out);
 
+/* FASTQ text to columns on the GPU (csrc/fqsx_fastq.h): what the reference's readers do byte by byte (CReadsBlock::get_read,
+ * fqs/reads_block.h:35-76; CSortedFASTQFile::get_read, fqs/io.h:451-482).  A line ends at 0x0A only (a 0x0D stays in its
+ * field), four line feeds make a record, bytes behind the last fourth line feed belong to no record; any field may be empty.
+ * One handle parses one chunk of text at a time and owns its device buffers.  max_chunk_bytes: the chunk size the caller
+ * intends to use (0: 256 MiB; below 4 GiB), reported back by fqsx_fastq_max_chunk -- cutting a file into chunks is the
+ * caller's job: the unconsumed tail of a chunk goes to the front of the next one, and a chunk without a complete record
+ * has to be made longer (fqsqueezer_amd/codec.py: parse_fastq).
+ * fqsx_fastq_index: uploads text[0 .. n_bytes) (n_bytes below 4 GiB), finds its line feeds and the field lengths.
+ *   out[0] records  out[1] bytes consumed (= position of the first byte that belongs to no record)
+ *   out[2] / out[3] / out[4] bytes of the id column (id lines with their line feeds, as read_desc_t::id_len counts them) /
+ *   of the base column / of the quality column (both without line feeds)  out[5] the longest id line  out[6] 1 if a
+ *   record's quality line and base line differ in length  out[7] line feeds in the chunk
+ * fqsx_fastq_columns: the columns of the chunk indexed last, into caller buffers of the sizes fqsx_fastq_index reported:
+ *   ids[out[2]], bases[out[3]], quals[out[4]], the three offset arrays with records + 1 entries each (qual_off equals
+ *   read_off unless out[6]), plus_len[records] = length of every separator line without its line feed.  A null pointer
+ *   skips that array.
+ * fqsx_fastq_kernel_times (after fqsx_fastq_set_profiling): out[0..6] = milliseconds of the count, tile scan, index, lengths,
+ *   record-tile scan, offsets and gather kernels, out[7..13] = their launches. */
+typedef struct fqsx_fastq fqsx_fastq;
+int fqsx_fastq_create(int device, uint64_t max_chunk_bytes, fqsx_fastq **out);
+void fqsx_fastq_destroy(fqsx_fastq *);
+uint64_t fqsx_fastq_max_chunk(fqsx_fastq *);
+int fqsx_fastq_index(fqsx_fastq *, const uint8_t *text, uint64_t n_bytes, uint64_t out[8]);
+int fqsx_fastq_columns(fqsx_fastq *, uint8_t *ids, uint64_t *id_off, uint8_t *bases, uint64_t *read_off, uint8_t *quals,
+                       uint64_t *qual_off, uint32_t *plus_len);
+int fqsx_fastq_set_profiling(fqsx_fastq *, int enable);
+int fqsx_fastq_kernel_times(fqsx_fastq *, double out[14]);
+
 const char *fqsx_last_error(void);
 const char *fqsx_version(void);
 

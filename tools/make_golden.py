@@ -48,6 +48,8 @@ Fixtures (data only -- inputs are re-generated deterministically by fqsqueezer_a
                             Each .json: SHA-256 and read count of the FASTQ text `fqs d` writes (per mate file when paired) and,
                             separately, the SHA-256 of its id lines.  JSON only for two committed files: c24_c10_full_o_t3.json
                             (c10_full_o_t3.fqs) and c24_c4_ragged_o_t3.json (c4_ragged_o_t3.fqs: -im n -qm n)
+  c25_plus_nolf_o_t3.fqs + .json, c25_plus_nolf_s_t2.json   `fqs e -qm o -im o` on synth_c25_text(): ragged reads, `+id` separator
+                            lines on every third record, the last record without its line feed (--only c25)
 Usage: python tools/make_golden.py [--work /tmp/w] [--only c1|c2|c3]
 """
 import argparse, hashlib, json, os, subprocess, sys
@@ -254,6 +256,8 @@ def main():
         c23(a)
     if a.only in ("", "c24"):
         c24(a)
+    if a.only in ("", "c25"):
+        c25(a)
     if a.only in ("", "c3"):
         fq = os.path.join(a.work, "c3.fq")
         if not os.path.exists(fq):
@@ -501,6 +505,23 @@ def c24(a):
     for f in os.listdir(GOLD):
         if f.startswith("c24_"):
             assert os.path.getsize(os.path.join(GOLD, f)) < 245705, f
+
+
+def c25(a):
+    """What `fqs e` makes of a text whose last record lacks its line feed and whose separator lines carry the id on some records:
+    the -om o file itself and the digests of the -om o and -om s files, all -qm o -im o."""
+    from fqsqueezer_amd.synth import synth_c25_text
+    fq = os.path.join(a.work, "c25.fq")
+    open(fq, "wb").write(synth_c25_text())
+    for om, t in (("o", 3), ("s", 2)):
+        tag = f"c25_plus_nolf_{om}_t{t}"
+        out = os.path.join(GOLD if om == "o" else a.work, tag + ".fqs")
+        subprocess.check_call([REF, "e", "-s", "-om", om, "-t", str(t), "-gs", "1", "-qm", "o", "-im", "o", "-v", "0",
+                               "-tmp", os.path.join(a.work, "tmp25_"), "-out", out, fq], stdout=subprocess.DEVNULL)
+        meta = {"input": "synth_c25_text(): 2000 ragged reads (G=50kbp, seed 25), `+id` on every third record, no final line feed",
+                "om": om, "qm": "o", "im": "o", "threads": t}
+        json.dump(fdigest(out, meta), open(os.path.join(GOLD, tag + ".json"), "w"))
+        assert os.path.getsize(out) < 1 << 20
 
 
 def c4_ref_decode(a, fq):
