@@ -70,6 +70,17 @@ def _load(path: str):
     lib.fqsx_id_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.fqsx_id_destroy.argtypes = [C.c_void_p]
     lib.fqsx_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "fqsx_cols_create"):   # (as above: builds that predate the device-resident columns)
+        lib.fqsx_cols_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.fqsx_cols_destroy.argtypes = [C.c_void_p]
+        lib.fqsx_cols_destroy.restype = None
+        lib.fqsx_cols_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.fqsx_fastq_columns_into.argtypes = [C.c_void_p] * 6
+        lib.fqsx_cols_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
+        lib.fqsx_cols_bases.argtypes = [C.c_void_p, C.c_void_p]
+        lib.fqsx_cols_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.fqsx_cols_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        lib.fqsx_cols_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.fqsx_last_error.restype = C.c_char_p
     lib.fqsx_version.restype = C.c_char_p
     return lib
@@ -369,13 +380,15 @@ class QualCodec:
             raise FqsxError(f"fqsx_qual_encode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
         return [C.string_at(self._streams[w], self._lens[w]) if self._lens[w] else b"" for w in range(self.T)]
 
-    def encode_block_dev(self, d_quals_ptr: int, d_off_ptr: int, read_off: np.ndarray) -> int:
-        """Device-resident entry point; returns the total stream bytes of the block."""
+    def encode_block_dev(self, d_quals_ptr: int, d_off_ptr: int, read_off: np.ndarray, collect: bool = False):
+        """Device-resident entry point; returns the total stream bytes of the block or -- collect -- its T streams."""
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
         self._lib.fqsx_qual_encode_block_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         rc = self._lib.fqsx_qual_encode_block_dev(self._h, d_quals_ptr, d_off_ptr, read_off.ctypes.data, len(read_off) - 1, self._streams, self._lens)
         if rc:
             raise FqsxError(f"fqsx_qual_encode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
+        if collect:
+            return [C.string_at(self._streams[w], self._lens[w]) if self._lens[w] else b"" for w in range(self.T)]
         return sum(self._lens[w] for w in range(self.T))
 
     def decode_block(self, streams, read_off: np.ndarray) -> np.ndarray:
@@ -474,6 +487,18 @@ class FastqParser:
             raise FqsxError(f"fqsx_fastq_columns: {rc}: {self._lib.fqsx_last_error().decode()}")
         return ids, id_off, bases, read_off, quals, qual_off, plus_len
 
+    def columns_into(self, info: dict, store: "DeviceColumns"):
+        """(ids, id_off, read_off, plus_len) of the chunk indexed last; its base and quality columns are appended to `store`
+        without leaving the device.  FqsxError, the store unchanged: a record whose quality line differs in length from its base line."""
+        n = info["records"]
+        ids = np.empty(info["id_bytes"], dtype=np.uint8)
+        id_off, read_off = (np.zeros(n + 1, dtype=np.uint64) for _ in range(2))
+        plus_len = np.empty(n, dtype=np.uint32)
+        rc = self._lib.fqsx_fastq_columns_into(self._h, store._h, ids.ctypes.data, id_off.ctypes.data, read_off.ctypes.data, plus_len.ctypes.data)
+        if rc:
+            raise FqsxError(f"fqsx_fastq_columns_into: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return ids, id_off, read_off, plus_len
+
     def set_profiling(self, on: bool) -> None:
         self._lib.fqsx_fastq_set_profiling(self._h, int(on))
 
@@ -485,6 +510,126 @@ class FastqParser:
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.fqsx_fastq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBlock:
+    """A container block in device memory (DeviceColumns.block_dev): device pointers of its bases, its qualities and its
+    offsets, valid until the next block is cut from the same columns, and the offsets on the host."""
+    __slots__ = ("bases", "quals", "d_off", "off")
+
+    def __init__(self, bases: int, quals: int, d_off: int, off: np.ndarray):
+        self.bases, self.quals, self.d_off, self.off = bases, quals, d_off, off
+
+
+class DeviceColumns:
+    """The records of a FASTQ file with the base and the quality column resident in device memory (fqsx_cols_*), filled chunk by
+    chunk by FastqParser.columns_into.  ids, id_off, read_off and plus_len are host arrays as in hostpipe.Columns, so that
+    record_sizes(), ids_of / ids_of_pe and the block formation work as they do there; block_dev / block_pe_dev cut a block on
+    the device where Columns.block / quals_of (block_pe / quals_of_pe) gather on the host."""
+
+    def __init__(self, device: int = 0, lib_path: Optional[str] = None):
+        from . import hostpipe as hp
+        self._lib = load_library(lib_path)
+        self._h = C.c_void_p()
+        rc = self._lib.fqsx_cols_create(device, C.byref(self._h))
+        if rc:
+            raise FqsxError(f"fqsx_cols_create: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._set_host(hp.Columns.from_chunks([]))
+
+    def _set_host(self, host) -> None:
+        self._host = host
+        self.ids, self.id_off, self.read_off, self.plus_len = host.ids, host.id_off, host.read_off, host.plus_len
+
+    def set_host_columns(self, parts) -> None:
+        """parts: what FastqParser.columns_into returned for every chunk appended to this store, in order"""
+        from . import hostpipe as hp
+        none = np.zeros(0, dtype=np.uint8)
+        self._set_host(hp.Columns.from_chunks([(ids, id_off, none, read_off, none, read_off, plus_len) for ids, id_off, read_off, plus_len in parts]))
+
+    def __len__(self) -> int:
+        return len(self.read_off) - 1
+
+    def record_sizes(self) -> np.ndarray:
+        return self._host.record_sizes()
+
+    def ids_of(self, idx):
+        return self._host.ids_of(idx)
+
+    def ids_of_pe(self, mate2: "DeviceColumns", idx):
+        return self._host.ids_of_pe(mate2._host, idx)
+
+    def info(self) -> dict:
+        a = (C.c_uint64 * 4)()
+        if self._lib.fqsx_cols_info(self._h, a):
+            raise FqsxError(f"fqsx_cols_info: {self._lib.fqsx_last_error().decode()}")
+        return {"records": int(a[0]), "bases": int(a[1]), "device_bytes": int(a[2]), "device_bytes_peak": int(a[3])}
+
+    def gather(self, idx, off: np.ndarray, mate2: Optional["DeviceColumns"] = None) -> DeviceBlock:
+        """fqsx_cols_gather: the block of the reads idx (with mate2: of the pairs idx, mates interleaved) whose offsets are off."""
+        idx = np.asarray(idx)
+        if len(idx) and (int(idx.min()) < 0 or int(idx.max()) >> 32):
+            raise ValueError("read indices are 32-bit")
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if len(off) != len(idx) * (2 if mate2 is not None else 1) + 1:
+            raise ValueError("a block of n reads has n + 1 offsets")
+        out = [C.c_void_p() for _ in range(3)]
+        rc = self._lib.fqsx_cols_gather(self._h, mate2._h if mate2 is not None else None, idx.ctypes.data if len(idx) else None, len(idx),
+                                        off.ctypes.data, *[C.byref(p) for p in out])
+        if rc:
+            raise FqsxError(f"fqsx_cols_gather: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return DeviceBlock(out[0].value, out[1].value, out[2].value, off)
+
+    def block_dev(self, idx) -> DeviceBlock:
+        idx = np.asarray(idx, dtype=np.int64)
+        off = np.zeros(len(idx) + 1, dtype=np.uint64)
+        ro = self.read_off.view(np.int64)
+        off[1:] = np.cumsum(ro[idx + 1] - ro[idx])
+        return self.gather(idx, off)
+
+    def block_pe_dev(self, mate2: "DeviceColumns", idx) -> DeviceBlock:
+        idx = np.asarray(idx, dtype=np.int64)
+        ln = np.empty(2 * len(idx), dtype=np.int64)
+        r1, r2 = self.read_off.view(np.int64), mate2.read_off.view(np.int64)
+        ln[0::2], ln[1::2] = r1[idx + 1] - r1[idx], r2[idx + 1] - r2[idx]
+        off = np.zeros(2 * len(idx) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(ln)
+        return self.gather(idx, off, mate2)
+
+    def download(self, d_ptr: int, n_bytes: int) -> np.ndarray:
+        """n_bytes of the store's device memory (a DeviceBlock's buffers) as a host array"""
+        out = np.empty(n_bytes, dtype=np.uint8)
+        rc = self._lib.fqsx_cols_download(self._h, d_ptr, out.ctypes.data, n_bytes)
+        if rc:
+            raise FqsxError(f"fqsx_cols_download: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return out
+
+    def bases_to_host(self) -> np.ndarray:
+        """the whole base column (the sort pre-pass bins on the host)"""
+        out = np.empty(int(self.read_off[-1]), dtype=np.uint8)
+        rc = self._lib.fqsx_cols_bases(self._h, out.ctypes.data)
+        if rc:
+            raise FqsxError(f"fqsx_cols_bases: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return out
+
+    def set_profiling(self, on: bool) -> None:
+        self._lib.fqsx_cols_set_profiling(self._h, int(on))
+
+    def kernel_times(self) -> dict:
+        a = (C.c_double * 4)()
+        self._lib.fqsx_cols_kernel_times(self._h, a)
+        return {"gather_ms": a[0], "gather_launches": int(a[1]), "check_ms": a[2], "check_launches": int(a[3])}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.fqsx_cols_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -511,14 +656,17 @@ def _chunk_source(src):
 
 
 def parse_fastq(text_or_path, device: int = 0, lib_path: Optional[str] = None, max_chunk_bytes: int = 0, stats: Optional[dict] = None,
-                profile: bool = False):
+                profile: bool = False, resident: bool = False):
     """FASTQ text (bytes / uint8 array) or a file (path) to hostpipe.Columns, parsed on the GPU chunk by chunk: a file is read in
     chunk-sized pieces into one reused buffer, the partial record at the end of a chunk is carried to the front of the next, and a
     chunk that holds no complete record doubles the chunk size.  What follows the last complete record (the reference drops an
     unterminated last record too) is not returned; its size is stats["tail_bytes"].  stats: also "chunks", "consumed",
-    "max_id_line", "length_mismatch" and -- profile -- "kernels"."""
+    "max_id_line", "length_mismatch" and -- profile -- "kernels".
+    resident: a DeviceColumns instead -- the base and quality columns never come to the host (the caller closes it); ValueError
+    for a record whose quality line differs in length from its base line, which resident columns cannot hold."""
     from . import hostpipe as hp
     p = FastqParser(device, lib_path, max_chunk_bytes)
+    store = DeviceColumns(device, lib_path) if resident else None
     readinto, close = _chunk_source(text_or_path)
     parts, n_chunks, consumed, max_id, mismatch = [], 0, 0, 0, False
     try:
@@ -537,7 +685,9 @@ def parse_fastq(text_or_path, device: int = 0, lib_path: Optional[str] = None, m
             info = p.index(buf[:have])
             n_chunks += 1
             if info["records"]:
-                parts.append(p.columns(info))
+                if resident and info["length_mismatch"]:
+                    raise ValueError("a record's quality line differs in length from its base line: resident columns keep one offset array")
+                parts.append(p.columns_into(info, store) if resident else p.columns(info))
                 max_id = max(max_id, info["max_id_line"])
                 mismatch |= info["length_mismatch"]
                 used = info["consumed"]
@@ -555,7 +705,14 @@ def parse_fastq(text_or_path, device: int = 0, lib_path: Optional[str] = None, m
             stats.update(chunks=n_chunks, consumed=consumed, tail_bytes=have, max_id_line=max_id, length_mismatch=mismatch)
             if profile:
                 stats["kernels"] = p.kernel_times()
+    except BaseException:
+        if store is not None:
+            store.close()
+        raise
     finally:
         close()
         p.close()
+    if resident:
+        store.set_host_columns(parts)
+        return store
     return hp.Columns.from_chunks(parts)

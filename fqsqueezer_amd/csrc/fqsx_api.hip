@@ -3089,26 +3089,22 @@ int fqsx_fastq_index(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t ou
   return FQSX_OK;
 }
 
-int fqsx_fastq_columns(fqsx_fastq *h, uint8_t *ids, uint64_t *id_off, uint8_t *bases, uint64_t *read_off, uint8_t *quals,
-                       uint64_t *qual_off, uint32_t *plus_len) {
-  if (!h) { g_err = "null argument"; return FQSX_E_ARG; }
-  if (!h->indexed) { g_err = "fqsx_fastq_columns without a successful fqsx_fastq_index before it"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(h));
+// Offsets and gather of the chunk indexed last (records in it), then what the caller wants on the host (a null pointer skips
+// the array).  The base and quality columns go behind the ids in the parser's own buffer, or -- d_bases / d_quals, device
+// memory of the chunk's sizes -- where the caller keeps them, with read_off copied to d_read_off on the device.
+static int fq_columns_impl(fqsx_fastq *h, u8 *d_bases, u8 *d_quals, u64 *d_read_off, uint8_t *ids, uint64_t *id_off, uint8_t *bases,
+                           uint64_t *read_off, uint8_t *quals, uint64_t *qual_off, uint32_t *plus_len) {
   FqCfg &c = h->cfg;
-  if (c.n_rec == 0) {
-    if (id_off) id_off[0] = 0;
-    if (read_off) read_off[0] = 0;
-    if (qual_off) qual_off[0] = 0;
-    return FQSX_OK;
-  }
   const u64 nb[3] = {h->sum[FQ_SUM_ID_BYTES], h->sum[FQ_SUM_BASES], h->sum[FQ_SUM_QUALS]};
+  const u64 own = d_bases ? nb[0] : nb[0] + nb[1] + nb[2];
   DEVCHK(dfit(h, h->d_off, h->off_cap, c.n_rec + 1, c.n_rec + c.n_rec / 8 + 1, 3 * sizeof(u64)));
-  DEVCHK(dfit(h, h->d_col, h->col_cap, nb[0] + nb[1] + nb[2], nb[0] + nb[1] + nb[2], 1));
+  DEVCHK(dfit(h, h->d_col, h->col_cap, own, own, 1));
   c.off = h->d_off; c.off_stride = h->off_cap;
-  c.col[0] = h->d_col; c.col[1] = c.col[0] + nb[0]; c.col[2] = c.col[1] + nb[1];
+  c.col[0] = h->d_col; c.col[1] = d_bases ? d_bases : c.col[0] + nb[0]; c.col[2] = d_bases ? d_quals : c.col[1] + nb[1];
   for (u32 q = 0; q < 3; ++q) c.col_n[q] = nb[q];
   FQ_LAUNCH(h, FQ_PASS_OFFSETS, k_fq_offsets, c.n_rtiles);
   FQ_LAUNCH(h, FQ_PASS_GATHER, k_fq_gather, (u32)((c.n_rec + 4 * FQSX_FQ_GBATCH - 1) / (4 * FQSX_FQ_GBATCH)));
+  if (d_read_off) DEVCHK(d2d(h, d_read_off, c.off + c.off_stride, (c.n_rec + 1) * sizeof(u64)));
   u8 *const hc[3] = {ids, bases, quals};
   u64 *const ho[3] = {id_off, read_off, qual_off};
   for (u32 q = 0; q < 3; ++q) {
@@ -3119,6 +3115,20 @@ int fqsx_fastq_columns(fqsx_fastq *h, uint8_t *ids, uint64_t *id_off, uint8_t *b
   return dev_sync(h);
 }
 
+int fqsx_fastq_columns(fqsx_fastq *h, uint8_t *ids, uint64_t *id_off, uint8_t *bases, uint64_t *read_off, uint8_t *quals,
+                       uint64_t *qual_off, uint32_t *plus_len) {
+  if (!h) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (!h->indexed) { g_err = "fqsx_fastq_columns without a successful fqsx_fastq_index before it"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(h));
+  if (h->cfg.n_rec == 0) {
+    if (id_off) id_off[0] = 0;
+    if (read_off) read_off[0] = 0;
+    if (qual_off) qual_off[0] = 0;
+    return FQSX_OK;
+  }
+  return fq_columns_impl(h, nullptr, nullptr, nullptr, ids, id_off, bases, read_off, quals, qual_off, plus_len);
+}
+
 int fqsx_fastq_set_profiling(fqsx_fastq *h, int enable) {
   if (!h) return FQSX_E_ARG;
   h->profiling = enable != 0;
@@ -3127,6 +3137,185 @@ int fqsx_fastq_set_profiling(fqsx_fastq *h, int enable) {
 int fqsx_fastq_kernel_times(fqsx_fastq *h, double out[14]) {
   if (!h || !out) return FQSX_E_ARG;
   for (u32 k = 0; k < FQ_N_PASS; ++k) { out[k] = h->pass_ms[k]; out[FQ_N_PASS + k] = (double)h->pass_n[k]; }
+  return FQSX_OK;
+}
+
+}  // extern "C"
+
+// =======================================================================================================
+// Device-resident columns (csrc/fqsx_cols.h): the base and quality columns of a file stay where the parser wrote them,
+// and the container blocks are cut out of them on the device
+// =======================================================================================================
+#include "fqsx_cols.h"
+
+struct fqsx_cols : DevCtx {
+  std::vector<ColsChunk> chunks;   // (device pointers) one allocation per parsed chunk: offsets, bases, qualities
+  u64 n_rec = 0, n_bases = 0;
+  ColsChunk *d_chunks = nullptr; u64 chunks_cap = 0;
+  bool table_stale = false;        // chunks appended since d_chunks was written
+  // the block gathered last: bases, qualities, and its offsets in one of two buffers (a refused gather leaves the other alone)
+  u8 *d_out[2] = {nullptr, nullptr}; u64 out_cap[2] = {0, 0};
+  u64 *d_boff[2] = {nullptr, nullptr}; u64 boff_cap[2] = {0, 0};
+  u32 boff_cur = 0;
+  u32 *d_idx = nullptr; u64 idx_cap = 0;
+  u32 *d_err = nullptr;            // [4]
+};
+
+static u64 up16(u64 x) { return (x + 15) & ~15ull; }
+
+// the store's chunk table in device memory
+static int cols_fit_table(fqsx_cols *s) {
+  if (!s->table_stale) return FQSX_OK;
+  DEVCHK(dev_enter(s));
+  const u64 n = s->chunks.size();
+  DEVCHK(dfit(s, s->d_chunks, s->chunks_cap, n, n + n / 2 + 8, sizeof(ColsChunk)));
+  DEVCHK(h2d(s, s->d_chunks, s->chunks.data(), n * sizeof(ColsChunk)));
+  DEVCHK(dev_sync(s));
+  s->table_stale = false;
+  return FQSX_OK;
+}
+
+static int cols_launch(fqsx_cols *a, const ColsCfg &cfg, u32 kidx) {
+  const u64 per_group = (u64)COLS_WAVES * FQ_WAVE;
+  const u32 grid = (u32)((cfg.n_out + per_group - 1) / per_group);
+  LAUNCH(a, kidx, k_cols_gather, grid, 256, cfg);
+  return FQSX_OK;
+}
+
+extern "C" {
+
+void fqsx_cols_destroy(fqsx_cols *s) {
+  if (!s) return;
+  dev_close(s);
+  delete s;
+}
+
+int fqsx_cols_create(int device, fqsx_cols **out) {
+  if (!out) { g_err = "null argument"; return FQSX_E_ARG; }
+  fqsx_cols *s = new fqsx_cols();
+  int rc = dev_open(s, device);
+  if (rc) { delete s; return rc; }
+  void *p = nullptr;
+  if ((rc = dalloc(s, &p, 4 * sizeof(u32), true))) { fqsx_cols_destroy(s); return rc; }
+  s->d_err = (u32 *)p;
+  *out = s;
+  return FQSX_OK;
+}
+
+int fqsx_cols_info(fqsx_cols *s, uint64_t out[4]) {
+  if (!s || !out) { g_err = "null argument"; return FQSX_E_ARG; }
+  out[0] = s->n_rec; out[1] = s->n_bases; out[2] = s->dev_bytes; out[3] = s->dev_bytes_peak;
+  return FQSX_OK;
+}
+
+int fqsx_fastq_columns_into(fqsx_fastq *h, fqsx_cols *s, uint8_t *ids, uint64_t *id_off, uint64_t *read_off, uint32_t *plus_len) {
+  if (!h || !s) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (!h->indexed) { g_err = "fqsx_fastq_columns_into without a successful fqsx_fastq_index before it"; return FQSX_E_ARG; }
+  if (h->device != s->device) { g_err = "the parser and the column store are on different devices"; return FQSX_E_ARG; }
+  if (h->sum[FQ_SUM_MISMATCH] || h->sum[FQ_SUM_BASES] != h->sum[FQ_SUM_QUALS]) {
+    g_err = "a record's quality line differs in length from its base line: resident columns keep one offset array";
+    return FQSX_E_ARG;
+  }
+  DEVCHK(dev_enter(h));
+  FqCfg &c = h->cfg;
+  if (c.n_rec == 0) {
+    if (id_off) id_off[0] = 0;
+    if (read_off) read_off[0] = 0;
+    return FQSX_OK;
+  }
+  if (s->n_rec + c.n_rec > 0xffffffffull) { g_err = "a block is cut by 32-bit record indices: 2^32 records or more in one store"; return FQSX_E_ARG; }
+  const u64 nb = h->sum[FQ_SUM_BASES], off_bytes = up16((c.n_rec + 1) * sizeof(u64));
+  void *mem = nullptr;
+  DEVCHK(dalloc(s, &mem, off_bytes + 2 * up16(nb), false));
+  ColsChunk ck;
+  ck.off = (const u64 *)mem;
+  ck.bases = (const u8 *)mem + off_bytes;
+  ck.quals = ck.bases + up16(nb);
+  ck.rec0 = s->n_rec; ck.n_rec = c.n_rec; ck.n_bytes = nb;
+  const int rc = fq_columns_impl(h, (u8 *)ck.bases, (u8 *)ck.quals, (u64 *)ck.off, ids, id_off, nullptr, read_off, nullptr, nullptr, plus_len);
+  if (rc) {   // (the store is what it was)
+    dev_drain(h);
+    dfree(s, mem);
+    return rc;
+  }
+  s->chunks.push_back(ck);
+  s->n_rec += c.n_rec;
+  s->n_bases += nb;
+  s->table_stale = true;
+  return FQSX_OK;
+}
+
+int fqsx_cols_gather(fqsx_cols *a, fqsx_cols *b, const uint32_t *idx, uint32_t n, const uint64_t *h_off, const uint8_t **d_bases,
+                     const uint8_t **d_quals, const uint64_t **d_off) {
+  if (!a || (n && !idx) || !h_off || !d_bases || !d_quals || !d_off) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (b && b->device != a->device) { g_err = "the two column stores are on different devices"; return FQSX_E_ARG; }
+  const u64 n_out = (u64)n * (b ? 2 : 1);
+  if (n_out > 0xffffffffull) { g_err = "a block of 2^32 reads or more"; return FQSX_E_ARG; }
+  if (h_off[0] != 0) { g_err = "block offsets must start at 0"; return FQSX_E_ARG; }
+  DEVCHK(cols_fit_table(a));
+  if (b) DEVCHK(cols_fit_table(b));
+  DEVCHK(dev_enter(a));
+  const u32 nxt = a->boff_cur ^ 1u;
+  DEVCHK(dfit(a, a->d_idx, a->idx_cap, std::max<u64>(n, 1), (u64)n + n / 4 + 16, sizeof(u32)));
+  DEVCHK(dfit(a, a->d_boff[nxt], a->boff_cap[nxt], n_out + 1, n_out + n_out / 4 + 16, sizeof(u64)));
+  if (n) DEVCHK(h2d(a, a->d_idx, idx, (u64)n * sizeof(u32)));
+  DEVCHK(h2d(a, a->d_boff[nxt], h_off, (n_out + 1) * sizeof(u64)));
+  DEVCHK(dzero(a, a->d_err, 4 * sizeof(u32)));
+  ColsCfg cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.src[0].chunk = a->d_chunks; cfg.src[0].n_chunks = (u32)a->chunks.size(); cfg.src[0].n_rec = a->n_rec;
+  if (b) { cfg.src[1].chunk = b->d_chunks; cfg.src[1].n_chunks = (u32)b->chunks.size(); cfg.src[1].n_rec = b->n_rec; }
+  cfg.n_src = b ? 2 : 1;
+  cfg.idx = a->d_idx; cfg.off = a->d_boff[nxt]; cfg.n_out = n_out;
+  cfg.out_n = h_off[n_out];
+  cfg.err = a->d_err;
+  u32 err[4] = {0, 0, 0, 0};
+  // every record checked before the block buffers are touched (or grown): a refused block leaves the previous one as it was
+  if (n_out) DEVCHK(cols_launch(a, cfg, 2));
+  DEVCHK(d2h_sync(a, err, a->d_err, sizeof(err)));
+  if (!err[COLS_ERR_INDEX] && !err[COLS_ERR_LENGTH] && !err[COLS_ERR_RANGE]) {
+    const u64 need = cfg.out_n + 64;
+    for (u32 q = 0; q < 2; ++q) DEVCHK(dfit(a, a->d_out[q], a->out_cap[q], need, need + need / 4, 1));
+    cfg.out[0] = a->d_out[0]; cfg.out[1] = a->d_out[1];
+    cfg.store = 1;
+    if (n_out) DEVCHK(cols_launch(a, cfg, 0));
+    DEVCHK(d2h_sync(a, err, a->d_err, sizeof(err)));   // (the stream is drained: the coders read the block from streams of their own)
+  }
+  if (err[COLS_ERR_INDEX]) { g_err = "a read index beyond the records of the column store"; return FQSX_E_ARG; }
+  if (err[COLS_ERR_LENGTH]) { g_err = "the block's offsets give a read another length than the column store holds"; return FQSX_E_ARG; }
+  if (err[COLS_ERR_RANGE]) { g_err = "device error in the column gather: a source or destination range outside its buffer"; return FQSX_E_DEVICE; }
+  a->boff_cur = nxt;
+  *d_bases = a->d_out[0]; *d_quals = a->d_out[1]; *d_off = a->d_boff[nxt];
+  return FQSX_OK;
+}
+
+int fqsx_cols_bases(fqsx_cols *s, uint8_t *out) {
+  if (!s || (s->n_bases && !out)) { g_err = "null argument"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(s));
+  u64 at = 0;
+  for (const ColsChunk &ck : s->chunks) {
+    if (ck.n_bytes) DEVCHK(d2h(s, out + at, ck.bases, ck.n_bytes));
+    at += ck.n_bytes;
+  }
+  return dev_sync(s);
+}
+
+int fqsx_cols_download(fqsx_cols *s, const void *d_src, void *h_dst, uint64_t n_bytes) {
+  if (!s || (n_bytes && (!d_src || !h_dst))) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (!n_bytes) return FQSX_OK;
+  DEVCHK(dev_enter(s));
+  return d2h_sync(s, h_dst, d_src, n_bytes);
+}
+
+int fqsx_cols_set_profiling(fqsx_cols *s, int enable) {
+  if (!s) return FQSX_E_ARG;
+  s->profiling = enable != 0;
+  return FQSX_OK;
+}
+int fqsx_cols_kernel_times(fqsx_cols *s, double out[4]) {
+  if (!s || !out) return FQSX_E_ARG;
+  out[0] = s->k_ms[0]; out[1] = (double)s->k_n[0];
+  out[2] = s->k_ms[2]; out[3] = (double)s->k_n[2];
   return FQSX_OK;
 }
 

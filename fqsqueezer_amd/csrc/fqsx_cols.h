@@ -1,0 +1,108 @@
+// fqsx_cols.h -- a container block cut out of device-resident columns by read index.
+//
+// The FASTQ parser (fqsx_fastq.h) can leave the base and the quality column of every chunk it parses in device memory: one
+// allocation per chunk that never moves, holding the chunk's own read offsets (n + 1, starting at 0), its bases and its
+// qualities (one offset array serves both: a chunk whose quality lines differ in length from its base lines is refused).  A
+// store is the table of those chunks; record r of the file is record r - rec0 of the last chunk whose rec0 is not above r.
+//   k_cols_gather   read i of the block is record idx[i] of the store, or -- two stores, the mates of a paired file -- read 2i
+//                   record idx[i] of the first and read 2i + 1 record idx[i] of the second.  The lanes of a wave look up one
+//                   record each (index, chunk, source range, the block's own offsets) and check it; then the wave copies its
+//                   records, sixteen lanes to a record, 16 bytes per lane where the destination is aligned.
+// A record that fails a check sets its error word and is not copied, so nothing outside the block buffers is ever written;
+// with store = 0 the kernel only checks, which is how the host refuses a block before a byte of the previous one is touched.
+// Workgroups are 256 threads (4 waves); the emulation build runs them as one 1-lane wave.
+#pragma once
+#include "fqsx_plat.h"
+
+#ifndef FQSX_EMU
+#define COLS_WAVES 4u   // waves of a workgroup
+#define COLS_SUB 16u    // lanes that copy one record
+#else
+#define COLS_WAVES 1u
+#define COLS_SUB 1u
+#endif
+enum { COLS_ERR_INDEX = 0, COLS_ERR_LENGTH = 1, COLS_ERR_RANGE = 2, COLS_N_ERR = 3 };
+
+struct ColsChunk {
+  const u8 *bases, *quals;   // [n_bytes] each
+  const u64 *off;            // [n_rec + 1], off[0] = 0, off[n_rec] = n_bytes
+  u64 rec0, n_rec, n_bytes;  // first record of the file in this chunk, its records and its bases
+};
+struct ColsSrc {
+  const ColsChunk *chunk;    // [n_chunks], rec0 ascending from 0
+  u32 n_chunks;
+  u64 n_rec;
+};
+struct ColsCfg {
+  ColsSrc src[2];
+  u32 n_src;        // 1, or 2: the reads of the block alternate between the two stores
+  u32 store;        // 0: check only
+  const u32 *idx;   // [n_out / n_src]
+  const u64 *off;   // [n_out + 1]: the block's offsets
+  u64 n_out;        // reads of the block
+  u8 *out[2];       // bases, quals: [out_n]
+  u64 out_n;
+  u32 *err;         // [COLS_N_ERR], nonzero: a record with an index beyond the store / whose length differs from the block's
+                    // offsets / whose source or destination range is not inside its buffer
+};
+
+struct ColsRec { const u8 *sb, *sq; u64 d; u32 len; };   // source of the bases and of the qualities, destination offset, bytes
+struct alignas(16) Cols16 { u64 lo, hi; };
+
+// read i of the block: where it comes from and where it goes, len = 0 unless every check passes
+FQ_DEV ColsRec cols_lookup(const ColsCfg &c, u64 i) {
+  ColsRec r = {nullptr, nullptr, 0, 0};
+  if (i >= c.n_out) return r;
+  const bool second = c.n_src == 2 && (i & 1);
+  const ColsChunk *chunk = second ? c.src[1].chunk : c.src[0].chunk;
+  const u32 n_chunks = second ? c.src[1].n_chunks : c.src[0].n_chunks;
+  const u64 n_rec = second ? c.src[1].n_rec : c.src[0].n_rec;
+  const u64 rec = c.idx[c.n_src == 2 ? i >> 1 : i];
+  if (rec >= n_rec) { c.err[COLS_ERR_INDEX] = 1; return r; }
+  if (n_chunks == 0) { c.err[COLS_ERR_RANGE] = 1; return r; }
+  u32 lo = 0, hi = n_chunks;   // chunk[lo].rec0 <= rec < chunk[hi].rec0
+  while (hi - lo > 1) {
+    const u32 mid = lo + (hi - lo) / 2;
+    if (chunk[mid].rec0 <= rec) lo = mid; else hi = mid;
+  }
+  const ColsChunk ch = chunk[lo];
+  if (rec < ch.rec0 || rec - ch.rec0 >= ch.n_rec) { c.err[COLS_ERR_RANGE] = 1; return r; }
+  const u64 so = ch.off[rec - ch.rec0], se = ch.off[rec - ch.rec0 + 1];
+  if (se < so || se > ch.n_bytes || se - so > 0xffffffffull) { c.err[COLS_ERR_RANGE] = 1; return r; }
+  const u64 d0 = c.off[i], d1 = c.off[i + 1];
+  if (d1 < d0 || d1 - d0 != se - so) { c.err[COLS_ERR_LENGTH] = 1; return r; }
+  if (d1 > c.out_n) { c.err[COLS_ERR_RANGE] = 1; return r; }
+  r.sb = ch.bases + so; r.sq = ch.quals + so; r.d = d0; r.len = (u32)(se - so);
+  return r;
+}
+
+// len bytes from src to dst by the COLS_SUB lanes of a record (sl: this lane among them): source and destination are aligned
+// to nothing, so bytes up to the destination's first 16-byte boundary, 16-byte groups (loads from wherever the source
+// happens to lie, aligned stores), then the bytes that are left
+FQ_DEV void cols_copy(u8 *dst, const u8 *src, u32 len, u32 sl) {
+  const u32 to_boundary = (u32)((16u - ((u64)(uintptr_t)dst & 15u)) & 15u), head = to_boundary < len ? to_boundary : len;
+  const u32 groups = (len - head) / 16u, tail = head + 16u * groups;
+  for (u32 p = sl; p < head; p += COLS_SUB) dst[p] = src[p];
+  for (u32 g = sl; g < groups; g += COLS_SUB) {
+    Cols16 v;
+    __builtin_memcpy(&v, src + head + 16u * g, 16);
+    *(Cols16 *)(dst + head + 16u * g) = v;
+  }
+  for (u32 p = tail + sl; p < len; p += COLS_SUB) dst[p] = src[p];
+}
+
+FQ_KERNEL256 void k_cols_gather(ColsCfg c) {
+  const u64 i0 = ((u64)FQ_BLOCK * COLS_WAVES + FQ_WAVE_ID) * FQ_WAVE;
+  const ColsRec mine = cols_lookup(c, i0 + FQ_LANE);
+  if (!c.store) return;
+  for (u32 j0 = 0; j0 < FQ_WAVE; j0 += FQ_WAVE / COLS_SUB) {
+    const u32 from = j0 + FQ_LANE / COLS_SUB, sl = FQ_LANE % COLS_SUB;
+    const u32 len = wave_bcast32(mine.len, from);
+    const u64 d = wave_bcast64(mine.d, from);
+    const u8 *sb = (const u8 *)(uintptr_t)wave_bcast64((u64)(uintptr_t)mine.sb, from);
+    const u8 *sq = (const u8 *)(uintptr_t)wave_bcast64((u64)(uintptr_t)mine.sq, from);
+    if (len == 0) continue;
+    cols_copy(c.out[0] + d, sb, len, sl);
+    cols_copy(c.out[1] + d, sq, len, sl);
+  }
+}

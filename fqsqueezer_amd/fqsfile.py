@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DnaCodec, IdCodec, MetaCodec, QualCodec, parse_fastq, sort_order
+from .codec import DeviceBlock, DnaCodec, IdCodec, MetaCodec, QualCodec, parse_fastq, sort_order
 
 
 def _gpu_groups(rec: hp.Records, device: int, lib_path: Optional[str]):
@@ -23,7 +23,8 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
     """Generator of the file's container blocks.  Per block the four coders run side by side, as the reference's worker
     codes meta, id, DNA and quality of a read in one loop (application.cpp:633-641): the DNA kernels and the quality kernel
     and the id kernel on their own HIP streams (host threads inside the C ABI, which releases the GIL), the meta coder on a host
-    thread meanwhile."""
+    thread meanwhile.  arrays(idx) may hand back the bases as a codec.DeviceBlock (a block cut on the device, its qualities with
+    it): the DNA and quality coders then read it where it lies."""
     from concurrent.futures import ThreadPoolExecutor
     threads = header[4]
     stored = hp.stored_streams(header)
@@ -38,9 +39,14 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
         for g, idx in enumerate(blocks):
             bases, off, ids, id_off, quals = arrays(idx)
             n = len(off) - 1
-            jobs = {hp.STREAM_DNA: pool.submit(dna.encode_block, bases, off, g)}
-            if qual is not None:
-                jobs[hp.STREAM_QUALITY] = pool.submit(qual.encode_block, quals, off)
+            if isinstance(bases, DeviceBlock):
+                jobs = {hp.STREAM_DNA: pool.submit(dna.encode_block_dev, bases.bases, bases.d_off, off, g)}
+                if qual is not None:
+                    jobs[hp.STREAM_QUALITY] = pool.submit(qual.encode_block_dev, bases.quals, bases.d_off, off, True)
+            else:
+                jobs = {hp.STREAM_DNA: pool.submit(dna.encode_block, bases, off, g)}
+                if qual is not None:
+                    jobs[hp.STREAM_QUALITY] = pool.submit(qual.encode_block, quals, off)
             if idc is not None:
                 jobs[hp.STREAM_ID] = pool.submit(idc.encode_block, ids, id_off, paired)
             st = {hp.STREAM_META: meta.encode_block(np.diff(off.astype(np.int64)).astype(np.uint32), paired)}
@@ -158,20 +164,53 @@ def _id_columns_fit_the_kernel(cols: hp.Columns, max_id_line: int) -> bool:
 def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: str = "s", genome_size_mbp: int = 3100,
                    quality_mode: str = "illumina_8", id_mode: str = "instrument", quality_thr: int = 20, device: int = 0,
                    lib_path: Optional[str] = None, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None,
-                   max_chunk_bytes: int = 0):
+                   max_chunk_bytes: int = 0, resident: bool = False, profile: bool = False):
     """`fqs e` on FASTQ files: `-s` with one input, `-p` with two (text as bytes / uint8 array, or a path; the defaults are the
     reference's, params.h:53-78).  The text is parsed on the GPU into columns (codec.parse_fastq), the sort pre-pass runs on the
     base column, and the blocks are cut from the columns with vectorised gathers.  Returns what compress_records* return.
     ValueError: a record whose quality line differs in length from its base line; mate files with different numbers of records.
-    gpu_ids: see compress_records.  stats: "parse" (one dict per input), "gpu_ids" (the choice made) and what encode_blocks adds."""
+    gpu_ids: see compress_records.  stats: "parse" (one dict per input), "gpu_ids" (the choice made) and what encode_blocks adds.
+    resident: the base and quality columns stay in device memory (codec.DeviceColumns, one store per input) and the blocks are
+    cut there; the same bytes.  Sorted order brings the base column to the host once, for the sort pre-pass; qualities never
+    come to the host.  stats then also has "columns" (DeviceColumns.info() per input once the last block is written, with
+    -- profile -- the gather kernel's "kernels")."""
     paired = text2_or_path2 is not None
     cols, parse_stats = [], []
-    for src in (text_or_path, text2_or_path2)[:2 if paired else 1]:
-        st = {}
-        cols.append(parse_fastq(src, device=device, lib_path=lib_path, max_chunk_bytes=max_chunk_bytes, stats=st))
-        parse_stats.append(st)
-        if st["length_mismatch"]:
-            raise ValueError("a record's quality line differs in length from its base line (input %d)" % len(cols))
+    try:
+        for src in (text_or_path, text2_or_path2)[:2 if paired else 1]:
+            st = {}
+            try:
+                cols.append(parse_fastq(src, device=device, lib_path=lib_path, max_chunk_bytes=max_chunk_bytes, stats=st, resident=resident))
+            except ValueError:   # (resident columns cannot hold such a record: parse_fastq stops at its chunk)
+                st["length_mismatch"] = True
+            parse_stats.append(st)
+            if st["length_mismatch"]:
+                raise ValueError("a record's quality line differs in length from its base line (input %d)" % len(parse_stats))
+        out = _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr, device, lib_path, gpu_ids,
+                                stats, resident, profile)
+    except BaseException:
+        if resident:
+            for c in cols:
+                c.close()
+        raise
+    return out if as_blocks else hp.write_fqs(*out)
+
+
+def _closing_columns(gen, cols, stats: Optional[dict], profile: bool):
+    """the blocks of gen; then the device columns are released"""
+    try:
+        yield from gen
+        if stats is not None:
+            stats["columns"] = [dict(c.info(), **({"kernels": c.kernel_times()} if profile else {})) for c in cols]
+    finally:
+        for c in cols:
+            c.close()
+
+
+def _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr, device, lib_path, gpu_ids,
+                      stats, resident, profile):
+    """(header, generator of container blocks) from the parsed columns of compress_fastq's one or two inputs"""
+    paired = len(cols) == 2
     if paired and len(cols[0]) != len(cols[1]):
         raise ValueError("the mate files hold different numbers of records: %d and %d" % (len(cols[0]), len(cols[1])))
     if gpu_ids is None:
@@ -181,14 +220,20 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
     mode = ("pe_" if paired else "se_") + ("sorted" if order == "s" else "original")
     header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
     c1 = cols[0]
-    groups = sort_order(c1.bases, c1.read_off, device=device, lib_path=lib_path) if order == "s" else None   # mates follow mate 1's order
+    # mates follow mate 1's order
+    groups = sort_order(c1.bases_to_host() if resident else c1.bases, c1.read_off, device=device, lib_path=lib_path) if order == "s" else None
+    if resident and profile:
+        c1.set_profiling(True)
     if paired:
         c2 = cols[1]
         s1, s2 = c1.record_sizes(), c2.record_sizes()
 
         def arrays(idx):
-            bases, off = c1.block_pe(c2, idx)
             ids, id_off = c1.ids_of_pe(c2, idx) if id_mode != "none" else (None, None)
+            if resident:
+                blk = c1.block_pe_dev(c2, idx)
+                return blk, blk.off, ids, id_off, None
+            bases, off = c1.block_pe(c2, idx)
             quals = c1.quals_of_pe(c2, idx)[0] if quality_mode != "none" else None
             return bases, off, ids, id_off, quals
 
@@ -202,8 +247,11 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
         sizes = c1.record_sizes()
 
         def arrays(idx):
-            bases, off = c1.block(idx)
             ids, id_off = c1.ids_of(idx) if id_mode != "none" else (None, None)
+            if resident:
+                blk = c1.block_dev(idx)
+                return blk, blk.off, ids, id_off, None
+            bases, off = c1.block(idx)
             quals = c1.quals_of(idx)[0] if quality_mode != "none" else None
             return bases, off, ids, id_off, quals
 
@@ -212,7 +260,7 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
 
         blocks = hp.form_blocks(c1, mode, groups=groups)
     gen = encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids)
-    return (header, gen) if as_blocks else hp.write_fqs(header, gen)
+    return header, (_closing_columns(gen, cols, stats, profile) if resident else gen)
 
 
 _QM = {"o": "lossless", "8": "illumina_8", "4": "illumina_4", "2": "binary", "n": "none"}   # fqsqueezer.cpp:157-191
@@ -235,13 +283,14 @@ def main(argv=None) -> int:
     ap.add_argument("-out", default="output.fqs")
     ap.add_argument("-device", type=int, default=0)
     ap.add_argument("-lib", default=None, help="path of the library to load (default: the package's libfqsx.so)")
+    ap.add_argument("-resident", action="store_true", help="keep the base and quality columns in device memory and cut the blocks there")
     ap.add_argument("inputs", nargs="+")
     a = ap.parse_args(argv)
     if len(a.inputs) != (2 if a.paired else 1):
         ap.error("-p takes two input files, -s one")
     header, blocks = compress_fastq(a.inputs[0], a.inputs[1] if a.paired else None, threads=min(max(a.t, 1), 64), order=a.om,
                                     genome_size_mbp=min(max(a.gs, 1), 32768), quality_mode=_QM[a.qm], id_mode=_IM[a.im], quality_thr=a.qt,
-                                    device=a.device, lib_path=a.lib, as_blocks=True)
+                                    device=a.device, lib_path=a.lib, as_blocks=True, resident=a.resident)
     with open(a.out, "wb") as f:
         for chunk in hp.fqs_chunks(header, blocks):   # block by block: the file is never held whole
             f.write(chunk)

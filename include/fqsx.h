@@ -357,6 +357,37 @@ int fqsx_fastq_columns(fqsx_fastq *, uint8_t *ids, uint64_t *id_off, uint8_t *ba
 int fqsx_fastq_set_profiling(fqsx_fastq *, int enable);
 int fqsx_fastq_kernel_times(fqsx_fastq *, double out[14]);
 
+/* Device-resident columns (csrc/fqsx_cols.h): a store keeps the base column and the quality column of one input file in
+ * device memory, chunk by chunk as the parser produces them -- one allocation per chunk that never moves, so the file is
+ * never held twice -- and cuts container blocks out of them by read index.  Ids stay host columns.
+ * fqsx_cols_info: out[0] records  out[1] bases  out[2] / out[3] device bytes the store holds now / held at most so far.
+ * fqsx_fastq_columns_into: what fqsx_fastq_columns does for the chunk indexed last, with the base and quality columns appended
+ *   to the store instead of copied to the host; ids[out[2]], id_off, read_off (the chunk's, records + 1 entries from 0) and
+ *   plus_len come back as there (a null pointer skips the array).  FQSX_E_ARG, the store unchanged: a chunk with a record
+ *   whose quality line differs in length from its base line (the store keeps one offset array for both columns).
+ * fqsx_cols_gather: the block whose read i is record idx[i] of store a; with b, read 2i is record idx[i] of a and read 2i + 1
+ *   record idx[i] of b (mate 1 / mate 2 of a paired file).  idx[n] and h_off[reads + 1], reads = n or 2 n, are host arrays;
+ *   h_off holds the block's offsets (from 0), which the caller knows from the read lengths.  *d_bases, *d_quals and *d_off
+ *   (h_off in device memory) are device buffers of store a with h_off[reads] + 64 bytes, valid until the next gather on it;
+ *   the call returns with its stream drained.  Every record is checked on the device before anything is stored: an index
+ *   that is no record of the store, or offsets that give a read another length than the store holds: FQSX_E_ARG; a range
+ *   outside a buffer: FQSX_E_DEVICE.  A refused call leaves the buffers of the previous block as they were.
+ * fqsx_cols_bases: the whole base column into out[bases] (the sort pre-pass bins on the host).
+ * fqsx_cols_download: n_bytes of the store's device memory (a gathered block) to the host.
+ * fqsx_cols_kernel_times (after fqsx_cols_set_profiling): out[0] / out[1] milliseconds and launches of the copying gather,
+ *   out[2] / out[3] of the checking pass in front of it. */
+typedef struct fqsx_cols fqsx_cols;
+int fqsx_cols_create(int device, fqsx_cols **out);
+void fqsx_cols_destroy(fqsx_cols *);
+int fqsx_cols_info(fqsx_cols *, uint64_t out[4]);
+int fqsx_fastq_columns_into(fqsx_fastq *, fqsx_cols *, uint8_t *ids, uint64_t *id_off, uint64_t *read_off, uint32_t *plus_len);
+int fqsx_cols_gather(fqsx_cols *a, fqsx_cols *b, const uint32_t *idx, uint32_t n, const uint64_t *h_off, const uint8_t **d_bases,
+                     const uint8_t **d_quals, const uint64_t **d_off);
+int fqsx_cols_bases(fqsx_cols *, uint8_t *out);
+int fqsx_cols_download(fqsx_cols *, const void *d_src, void *h_dst, uint64_t n_bytes);
+int fqsx_cols_set_profiling(fqsx_cols *, int enable);
+int fqsx_cols_kernel_times(fqsx_cols *, double out[4]);
+
 const char *fqsx_last_error(void);
 const char *fqsx_version(void);
 

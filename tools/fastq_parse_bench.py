@@ -3,9 +3,12 @@
   (b) the host path it replaces: hostpipe.read_fastq, then block_arrays, id_arrays and qual_arrays over all reads, then record_sizes,
 on a rectangular text (every read --len bases) and a ragged one (read lengths 2/3 --len .. --len), ids from synth.read_id.
 --compress PAIRS: also compress_fastq (-p -om s -qm o -im o) on the ragged text of PAIRS pairs against compress_records_pe on
-Records lists of the same reads, in Mbases/s.
+Records lists of the same reads, in Mbases/s, and against compress_fastq(resident=True): columns kept in device memory, blocks
+cut there.  --shapes: the same for other inputs and orders (se_o, se_s: mate 1 alone; pe_o, pe_s); per shape the host-column
+and the resident run alternate, and one more resident run with events around the gather launches gives the kernel's own time.
 A warm-up run, then --repeats timed runs; reported: median, min and max.  One JSON document on stdout (and --out).
-Usage: python tools/fastq_parse_bench.py [--reads 1000000] [--len 150] [--repeats 5] [--compress 1000000] [--out profiles/x.json]"""
+Usage: python tools/fastq_parse_bench.py [--reads 1000000] [--len 150] [--repeats 5] [--compress 1000000] [--shapes se_o,se_s,pe_o,pe_s]
+       [--out profiles/x.json]"""
 import argparse
 import json
 import os
@@ -38,6 +41,19 @@ def timed(fn, repeats: int):
     return {"median_s": float(np.median(t)), "min_s": min(t), "max_s": max(t), "runs": repeats}
 
 
+def alternately(fns: dict, repeats: int):
+    """the functions of fns in turn, a warm-up round and then `repeats` timed rounds: what one of them meets on a shared machine
+    the others meet too"""
+    t = {k: [] for k in fns}
+    for r in range(repeats + 1):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            if r:
+                t[k].append(time.perf_counter() - t0)
+    return {k: {"median_s": float(np.median(v)), "min_s": min(v), "max_s": max(v), "runs": repeats} for k, v in t.items()}
+
+
 def host_path(path: str):
     rec = hp.read_fastq(path)
     idx = np.arange(len(rec), dtype=np.int64)
@@ -50,6 +66,8 @@ def main() -> int:
     ap.add_argument("--len", type=int, default=150)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--compress", type=int, default=0, metavar="PAIRS")
+    ap.add_argument("--shapes", default="pe_s", help="comma-separated: se_o, se_s, pe_o, pe_s")
+    ap.add_argument("--compress-repeats", type=int, default=2)
     ap.add_argument("--threads", type=int, default=64)
     ap.add_argument("--gs", type=int, default=8)
     ap.add_argument("--device", type=int, default=0)
@@ -90,24 +108,43 @@ def main() -> int:
             p1, p2 = os.path.join(tmp, "1.fq"), os.path.join(tmp, "2.fq")
             open(p1, "wb").write(t1)
             open(p2, "wb").write(t2)
-            kw = dict(threads=a.threads, order="s", genome_size_mbp=a.gs, quality_mode="lossless", id_mode="lossless", device=a.device)
+            kw = dict(threads=a.threads, genome_size_mbp=a.gs, quality_mode="lossless", id_mode="lossless", device=a.device)
+            # (a record is its id, 2 L bases and qualities, a `+` and four line feeds)
+            n_bases = [(len(t) - 5 * n - sum(len(read_id(i, m + 1)) for i in range(n))) // 2 for m, t in enumerate((t1, t2))]
+            for shape in a.shapes.split(","):
+                ends, order = shape.split("_")
+                paths = (p1, p2) if ends == "pe" else (p1,)
+                bases = sum(n_bases[:len(paths)])
 
-            def via_fastq():
-                header, blocks = compress_fastq(p1, p2, as_blocks=True, **kw)
-                return sum(len(c) for c in hp.fqs_chunks(header, blocks))
+                def via_fastq(resident=False, stats=None, profile=False):
+                    header, blocks = compress_fastq(*paths, as_blocks=True, order=order, resident=resident, stats=stats, profile=profile, **kw)
+                    return sum(len(c) for c in hp.fqs_chunks(header, blocks))
 
-            rec = [hp.read_fastq(p) for p in (p1, p2)]   # (not timed: the Records path has no file reader of its own)
-            bases = sum(len(x) for r in rec for x in r.seq)
+                fns = {"compress_fastq": via_fastq, "compress_fastq_resident": lambda: via_fastq(True)}
+                if shape == "pe_s":
+                    rec = [hp.read_fastq(p) for p in (p1, p2)]   # (not timed: the Records path has no file reader of its own)
+                    assert bases == sum(len(x) for r in rec for x in r.seq)
 
-            def via_records():
-                header, blocks = compress_records_pe(rec[0], rec[1], kw["threads"], "s", a.gs, device=a.device, quality_mode="lossless", id_mode="lossless", as_blocks=True)
-                return sum(len(c) for c in hp.fqs_chunks(header, blocks))
+                    def via_records():
+                        header, blocks = compress_records_pe(rec[0], rec[1], kw["threads"], "s", a.gs, device=a.device, quality_mode="lossless", id_mode="lossless", as_blocks=True)
+                        return sum(len(c) for c in hp.fqs_chunks(header, blocks))
 
-            assert via_fastq() == via_records()
-            c = {"pairs": n, "bases": bases, "compress_fastq": timed(via_fastq, 2), "compress_records_pe": timed(via_records, 2)}
-            for k in ("compress_fastq", "compress_records_pe"):
-                c[k]["Mbases_per_s"] = round(bases / 1e6 / c[k]["median_s"], 2)
-            res["compress_ragged_pe"] = c
+                    fns["compress_records_pe"] = via_records
+                    assert via_fastq() == via_records()
+                assert via_fastq() == via_fastq(True)
+                c = dict({"pairs" if ends == "pe" else "reads": n, "bases": bases}, **alternately(fns, a.compress_repeats))
+                for k in fns:
+                    c[k]["Mbases_per_s"] = round(bases / 1e6 / c[k]["median_s"], 2)
+                c["ratio_resident_over_host_columns"] = round(c["compress_fastq"]["median_s"] / c["compress_fastq_resident"]["median_s"], 3)
+                st = {}
+                via_fastq(True, st, True)   # (a run of its own: events around every gather launch)
+                k = st["columns"][0]["kernels"]
+                c["blocks"] = k["gather_launches"]
+                c["gather_kernel_ms_per_block"] = round(k["gather_ms"] / max(1, k["gather_launches"]), 4)
+                c["gather_check_ms_per_block"] = round(k["check_ms"] / max(1, k["check_launches"]), 4)
+                c["columns"] = [{x: y for x, y in d.items() if x != "kernels"} for d in st["columns"]]
+                res["compress_ragged_" + ("pe" if shape == "pe_s" else shape)] = c
+                print(shape, json.dumps(c), file=sys.stderr, flush=True)
     out = json.dumps(res, indent=1)
     print(out)
     if a.out:
