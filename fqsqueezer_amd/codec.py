@@ -81,6 +81,18 @@ def _load(path: str):
         lib.fqsx_cols_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         lib.fqsx_cols_set_profiling.argtypes = [C.c_void_p, C.c_int]
         lib.fqsx_cols_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    if hasattr(lib, "fqsx_fqtext_create"):   # (as above: builds that predate the text assembler)
+        lib.fqsx_dna_decode_block_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        lib.fqsx_idg_decode_block_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        lib.fqsx_fqtext_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.fqsx_fqtext_destroy.argtypes = [C.c_void_p]
+        lib.fqsx_fqtext_destroy.restype = None
+        lib.fqsx_fqtext_block.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.fqsx_fqtext_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.fqsx_fqtext_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        lib.fqsx_fqtext_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.fqsx_last_error.restype = C.c_char_p
     lib.fqsx_version.restype = C.c_char_p
     return lib
@@ -157,6 +169,19 @@ class DnaCodec:
         if rc:
             raise FqsxError(f"fqsx_dna_decode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
         return out[:int(read_off[-1])]
+
+    def decode_block_dev(self, streams, read_off: np.ndarray, generation: int) -> int:
+        """The same, leaving the block in device memory: returns the device pointer (the codec's output buffer, valid until
+        the next call on this codec)."""
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
+        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        d_out = C.c_void_p()
+        rc = self._lib.fqsx_dna_decode_block_dev(self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
+                                                 generation, C.byref(d_out))
+        if rc:
+            raise FqsxError(f"fqsx_dna_decode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return d_out.value or 0
 
     def stats(self) -> dict:
         a = (C.c_uint64 * 64)()
@@ -308,17 +333,35 @@ class IdCodec:
         ids, off = C.c_void_p(), C.c_void_p()
         rc = f(self._h, arr, lens.ctypes.data, n_reads, int(paired), C.byref(ids), C.byref(off))
         if rc:
-            msg = L.fqsx_last_error().decode() if self._gpu else ("a worker's stream is shorter than 8 bytes or a bad argument" if rc == -1 else "malformed or truncated id stream")
-            e = FqsxError(f"{name}: {rc}: {msg}")
-            e.staging = False
-            if self._gpu:   # what the kernel reported: 5 / 6 = beyond its staging sizes / its list of instrument names
-                L.fqsx_idg_error_kind.argtypes = [C.c_void_p]
-                e.staging = rc == -5 and L.fqsx_idg_error_kind(self._h) in (5, 6)
-            raise e
+            raise self._decode_error(name, rc)
         id_off = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(n_reads + 1,)).copy()
         n = int(id_off[-1])
         out = np.ctypeslib.as_array(C.cast(ids, C.POINTER(C.c_uint8)), shape=(max(n, 1),))[:n].copy()
         return out, id_off
+
+    def _decode_error(self, name: str, rc: int) -> FqsxError:
+        L = self._lib
+        msg = L.fqsx_last_error().decode() if self._gpu else ("a worker's stream is shorter than 8 bytes or a bad argument" if rc == -1 else "malformed or truncated id stream")
+        e = FqsxError(f"{name}: {rc}: {msg}")
+        e.staging = False
+        if self._gpu:   # what the kernel reported: 5 / 6 = beyond its staging sizes / its list of instrument names
+            L.fqsx_idg_error_kind.argtypes = [C.c_void_p]
+            e.staging = rc == -5 and L.fqsx_idg_error_kind(self._h) in (5, 6)
+        return e
+
+    def decode_block_dev(self, streams, n_reads: int, paired: bool = False):
+        """GPU flavour only: decode_block leaving the block in device memory.  Returns (d_ids, d_id_len, id_bytes): the device
+        pointers of the id lines back to back and of their n_reads uint32 lengths (both the codec's, valid until its next call)
+        and the bytes of the lines.  Errors as decode_block's, `staging` included."""
+        if not self._gpu:
+            raise FqsxError("decode_block_dev: the host id decoder has no device output")
+        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
+        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        ids, idl, nb = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        rc = self._lib.fqsx_idg_decode_block_dev(self._h, arr, lens.ctypes.data, n_reads, int(paired), C.byref(ids), C.byref(idl), C.byref(nb))
+        if rc:
+            raise self._decode_error("fqsx_idg_decode_block_dev", rc)
+        return ids.value or 0, idl.value or 0, int(nb.value)
 
     def stats(self) -> dict:
         """GPU flavour: how often the decoder had to grow (fqsx_idg_stats) and its capacities."""
@@ -510,6 +553,78 @@ class FastqParser:
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.fqsx_fastq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FQTEXT_PASSES = ["sizes", "scan_tiles", "offsets", "scatter"]
+
+
+class FastqText:
+    """Columns to FASTQ text on the GPU (fqsx_fqtext_*): one container block per call, the text `fqs d` writes for it."""
+
+    def __init__(self, device: int = 0, lib_path: Optional[str] = None):
+        L = self._lib = load_library(lib_path)
+        self._h = C.c_void_p()
+        rc = L.fqsx_fqtext_create(device, C.byref(self._h))
+        if rc:
+            raise FqsxError(f"fqsx_fqtext_create: {rc}: {L.fqsx_last_error().decode()}")
+        self.text_bytes = (0, 0)
+
+    def block(self, read_off: np.ndarray, d_bases: int, d_quals: Optional[int] = None, ids=None, id_len=None, id_bytes: Optional[int] = None,
+              paired: bool = False, qual_fill: int = 0):
+        """Assemble the block whose reads lie under read_off (uint64[n + 1], from 0) in the device columns d_bases / d_quals
+        (device pointers; d_quals None: every quality is the byte qual_fill).  ids / id_len: device pointers with id_bytes (what
+        IdCodec.decode_block_dev returns), or host arrays (uint8 id lines back to back, their uint32 lengths), or None: every id
+        line is "@\n".  Returns (n0, n1), the bytes of the two outputs (n1 = 0 unless paired).  FqsxError with `.code` -1 for
+        inputs that contradict each other, -5 for a range outside a buffer; the previous block's text stays as it was."""
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n = len(read_off) - 1
+        on_device, keep = 0, None
+        if ids is None:
+            p_ids, p_len, nb = None, None, 0
+        elif isinstance(ids, np.ndarray):
+            keep = (np.ascontiguousarray(ids, dtype=np.uint8), np.ascontiguousarray(id_len, dtype=np.uint32))
+            if len(keep[1]) != n:
+                raise ValueError("id_len must have one entry per read")
+            p_ids, p_len = keep[0].ctypes.data, keep[1].ctypes.data
+            nb = len(keep[0]) if id_bytes is None else int(id_bytes)
+        else:
+            p_ids, p_len, nb, on_device = int(ids), int(id_len), int(id_bytes), 1
+        out = (C.c_uint64 * 2)()
+        rc = self._lib.fqsx_fqtext_block(self._h, n, int(paired), p_ids, p_len, on_device, nb, d_bases or None, d_quals or None,
+                                         int(qual_fill), read_off.ctypes.data, out)
+        if rc:
+            e = FqsxError(f"fqsx_fqtext_block: {rc}: {self._lib.fqsx_last_error().decode()}")
+            e.code = rc
+            raise e
+        self.text_bytes = (int(out[0]), int(out[1]))
+        return self.text_bytes
+
+    def download(self, mate: int = 0) -> np.ndarray:
+        """Output `mate` of the block assembled last (uint8[])."""
+        out = np.empty(self.text_bytes[mate], dtype=np.uint8)
+        rc = self._lib.fqsx_fqtext_download(self._h, mate, out.ctypes.data if len(out) else None)
+        if rc:
+            raise FqsxError(f"fqsx_fqtext_download: {rc}: {self._lib.fqsx_last_error().decode()}")
+        return out
+
+    def set_profiling(self, on: bool) -> None:
+        self._lib.fqsx_fqtext_set_profiling(self._h, int(on))
+
+    def kernel_times(self) -> dict:
+        a = (C.c_double * 8)()
+        self._lib.fqsx_fqtext_kernel_times(self._h, a)
+        return {name: {"ms": a[k], "launches": int(a[4 + k])} for k, name in enumerate(FQTEXT_PASSES)}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.fqsx_fqtext_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1279,7 +1279,7 @@ int block_finish(fqsx_dna *c, const u64 *h_off, const u8 **streams, u64 *lens, u
       g_err = "device error " + std::to_string(derr) + " while decoding block " + std::to_string(generation);
       return FQSX_E_DEVICE;
     }
-    return d2h_sync(c, bases_out, cfg.dout, h_off[n_reads]);
+    return bases_out ? d2h_sync(c, bases_out, cfg.dout, h_off[n_reads]) : FQSX_OK;   // (null: the block stays in cfg.dout)
   }
   LAUNCH(c, 2, k_finish_block, T, 64, cfg, c->d_lens, c->d_end);
   // ---- results: stream lengths, context-table occupancies (for the next block's sizing) and the error word at once
@@ -1545,6 +1545,21 @@ int fqsx_dna_decode_block(fqsx_dna *c, const uint8_t *const *streams, const uint
   if ((rc = dfit(c, c->d_off, c->dev_off_cap, no, no + no / 4, 1))) return rc;
   if ((rc = h2d(c, c->d_off, off, no))) return rc;
   return encode_block_impl(c, nullptr, c->d_off, off, n_reads, generation, nullptr, nullptr, streams, lens, bases_out);
+}
+
+int fqsx_dna_decode_block_dev(fqsx_dna *c, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *off, uint32_t n_reads,
+                              uint32_t generation, const uint8_t **d_bases_out) {
+  if (d_bases_out) *d_bases_out = nullptr;
+  if (!c || !streams || !lens || !off || !d_bases_out) { g_err = "null argument"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(c));
+  int rc;
+  u64 no = ((u64)n_reads + 1) * sizeof(u64);
+  if ((rc = dfit(c, c->d_off, c->dev_off_cap, no, no + no / 4, 1))) return rc;
+  if ((rc = h2d(c, c->d_off, off, no))) return rc;
+  // (block_finish reads the error word back synchronously: the stream is drained when this returns)
+  if ((rc = encode_block_impl(c, nullptr, c->d_off, off, n_reads, generation, nullptr, nullptr, streams, lens, nullptr))) return rc;
+  *d_bases_out = c->cfg.dout;
+  return FQSX_OK;
 }
 
 // ---- sharded mode: one synchronisation phase in steps, with the collectives in between left to the caller ----------
@@ -2540,6 +2555,8 @@ struct fqsx_idg : DevCtx {
   u8 *d_in;
   u32 *d_idlen;
   u64 in_cap, idlen_cap;
+  u8 *d_cat;       // fqsx_idg_decode_block_dev: the block's id lines back to back
+  u64 cat_cap;
   u64 *snap_small, *snap_big, *snap_fixed;
   u8 *snap_mtf;
   u64 snap_small_cap, snap_big_cap;
@@ -2663,9 +2680,9 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
 // cannot see them, so it runs a block from a snapshot: the small / big / fixed / move-to-front tables are copied device to
 // device before the launch, and when the kernel reports IDK_ERR_TABLE or IDK_ERR_OUT the snapshot is put back, the capacity
 // that ran out is doubled (k_qual_rehash) and the block runs again.  A valid stream never fails for want of pre-sizing.
-int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
-                          const uint8_t **ids_out, const uint64_t **id_off_out) {
-  if (!q || !streams || !lens || !ids_out || !id_off_out || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
+// (the part both entry points share: the block decoded, the state words taken over, the line lengths on the host, their sum
+// checked against the workers' output; *total_out: the bytes of the block's id lines)
+static int idg_decode_run(fqsx_idg *q, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired, u64 *total_out) {
   DevCtx *c = q;
   IdCfg &cfg = q->cfg;
   const u64 T = q->T;
@@ -2759,18 +2776,57 @@ int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint
     if (q->h_lens[t] > cfg.out_cap) { g_err = "id decoder output overflow"; return FQSX_E_DEVICE; }
     total += q->h_lens[t];
   }
-  q->h_ids.resize(total + 8);
-  u64 at = 0;
-  for (u64 t = 0; t < T; ++t) {
-    if (q->h_lens[t] && (rc = d2h(c, q->h_ids.data() + at, cfg.out + t * cfg.out_cap, q->h_lens[t]))) return rc;
-    at += q->h_lens[t];
-  }
   DEVCHK(dev_sync(c));
   q->h_idoff.assign((u64)n_reads + 1, 0);
   for (u64 i = 0; i < n_reads; ++i) q->h_idoff[i + 1] = q->h_idoff[i] + q->h_idlen[i];
   if (q->h_idoff[n_reads] != total) { g_err = "id decoder: line lengths and output disagree"; return FQSX_E_DEVICE; }
+  *total_out = total;
+  return FQSX_OK;
+}
+
+int fqsx_idg_decode_block(fqsx_idg *q, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                          const uint8_t **ids_out, const uint64_t **id_off_out) {
+  if (!q || !streams || !lens || !ids_out || !id_off_out || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
+  u64 total = 0;
+  int rc = idg_decode_run(q, streams, lens, n_reads, paired, &total);
+  if (rc) return rc;
+  DevCtx *c = q;
+  const IdCfg &cfg = q->cfg;
+  q->h_ids.resize(total + 8);
+  u64 at = 0;
+  for (u64 t = 0; t < q->T; ++t) {
+    if (q->h_lens[t] && (rc = d2h(c, q->h_ids.data() + at, cfg.out + t * cfg.out_cap, q->h_lens[t]))) return rc;
+    at += q->h_lens[t];
+  }
+  DEVCHK(dev_sync(c));
   *ids_out = q->h_ids.data();
   *id_off_out = q->h_idoff.data();
+  return FQSX_OK;
+}
+
+// The same, leaving the block on the device: the kernel wrote one region per worker, the regions are moved side by side into
+// d_cat (device-to-device copies on the codec's stream), and the line lengths are where the kernel left them.
+int fqsx_idg_decode_block_dev(fqsx_idg *q, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                              const uint8_t **d_ids_out, const uint32_t **d_id_len_out, uint64_t *id_bytes_out) {
+  if (d_ids_out) *d_ids_out = nullptr;
+  if (d_id_len_out) *d_id_len_out = nullptr;
+  if (!q || !streams || !lens || !d_ids_out || !d_id_len_out || !id_bytes_out || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
+  *id_bytes_out = 0;
+  u64 total = 0;
+  int rc = idg_decode_run(q, streams, lens, n_reads, paired, &total);
+  if (rc) return rc;
+  DevCtx *c = q;
+  const IdCfg &cfg = q->cfg;
+  if ((rc = dfit(c, q->d_cat, q->cat_cap, total + 64, total + total / 4 + 64, 1))) return rc;
+  u64 at = 0;
+  for (u64 t = 0; t < q->T; ++t) {
+    if (q->h_lens[t] && (rc = d2d(c, q->d_cat + at, cfg.out + t * cfg.out_cap, q->h_lens[t]))) return rc;
+    at += q->h_lens[t];
+  }
+  DEVCHK(dev_sync(c));
+  *d_ids_out = q->d_cat;
+  *d_id_len_out = q->d_idlen;
+  *id_bytes_out = total;
   return FQSX_OK;
 }
 
@@ -3316,6 +3372,171 @@ int fqsx_cols_kernel_times(fqsx_cols *s, double out[4]) {
   if (!s || !out) return FQSX_E_ARG;
   out[0] = s->k_ms[0]; out[1] = (double)s->k_n[0];
   out[2] = s->k_ms[2]; out[3] = (double)s->k_n[2];
+  return FQSX_OK;
+}
+
+}  // extern "C"
+
+// =======================================================================================================
+// Columns -> FASTQ text (csrc/fqsx_fqtext.h): what `fqs d` does last, application.cpp:871-889 / 980-982
+// =======================================================================================================
+#include "fqsx_fqtext.h"
+
+enum { FT_PASS_SIZES = 0, FT_PASS_SCAN_TILES, FT_PASS_OFFSETS, FT_PASS_SCATTER, FT_N_PASS };
+#define FT_PIN_HALF (8ull << 20)   /* bytes of one half of the pinned staging buffer: a download moves through the two in turn */
+
+struct fqsx_fqtext : DevCtx {
+  // the text of the block assembled last is in d_text[cur]; the next block is written to the other pair, so that a refused
+  // call leaves it alone.  That guarantee is all the second pair serves, at the price of two blocks of text in device memory:
+  // calls on a handle are serialised, so a download never runs beside the next assembly
+  u8 *d_text[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; u64 text_cap[2][2] = {{0, 0}, {0, 0}};
+  u32 cur = 0;
+  u64 text_n[2] = {0, 0};                            // its bytes per mate
+  u64 *d_roff = nullptr; u64 roff_cap = 0;           // the block's read offsets
+  u8 *d_ids = nullptr; u64 ids_cap = 0;              // host ids, uploaded
+  u32 *d_idlen = nullptr; u64 idlen_cap = 0;
+  u64 *d_tile = nullptr; u64 tile_cap = 0;           // [FT_N_SUM][n_tiles]
+  u64 *d_tile_pre = nullptr; u64 tile_pre_cap = 0;   // [FT_N_SUM][n_tiles + 1]
+  u64 *d_rec = nullptr; u64 rec_cap = 0;             // [2][rec_cap]: start, id_off
+  u64 *d_res = nullptr;                              // [FT_N_RES]
+  u8 *h_pin = nullptr;                               // [2][FT_PIN_HALF]; the result words come back through its first bytes
+  double pass_ms[FT_N_PASS] = {0, 0, 0, 0};
+  u64 pass_n[FT_N_PASS] = {0, 0, 0, 0};
+};
+
+// one assembler kernel, its time (while profiling) booked under `pass`
+#define FT_LAUNCH(h, pass, kern, grid, cfg)                 \
+  do {                                                      \
+    const double t0_ = (h)->k_ms[2];                        \
+    LAUNCH(h, 2, kern, grid, 256, cfg);                     \
+    (h)->pass_ms[pass] += (h)->k_ms[2] - t0_;               \
+    (h)->pass_n[pass] += 1;                                 \
+  } while (0)
+
+static int ft_results(fqsx_fqtext *h, u64 res[FT_N_RES]) {
+  DEVCHK(d2h_sync(h, h->h_pin, h->d_res, FT_N_RES * sizeof(u64)));
+  memcpy(res, h->h_pin, FT_N_RES * sizeof(u64));
+  return FQSX_OK;
+}
+
+extern "C" {
+
+void fqsx_fqtext_destroy(fqsx_fqtext *h) {
+  if (!h) return;
+  dev_drain(h);
+  pinned_free(h->h_pin);
+  dev_close(h);
+  delete h;
+}
+
+int fqsx_fqtext_create(int device, fqsx_fqtext **out) {
+  if (!out) { g_err = "null argument"; return FQSX_E_ARG; }
+  fqsx_fqtext *h = new fqsx_fqtext();
+  int rc = dev_open(h, device);
+  if (rc) { delete h; return rc; }
+  void *p = nullptr;
+  if ((rc = dalloc(h, &p, FT_N_RES * sizeof(u64), true))) { fqsx_fqtext_destroy(h); return rc; }
+  h->d_res = (u64 *)p;
+  if ((rc = pinned_alloc(&p, 2 * FT_PIN_HALF))) { fqsx_fqtext_destroy(h); return rc; }
+  h->h_pin = (u8 *)p;
+  *out = h;
+  return FQSX_OK;
+}
+
+int fqsx_fqtext_block(fqsx_fqtext *h, uint32_t n_reads, int paired, const uint8_t *ids, const uint32_t *id_len, int ids_on_device,
+                      uint64_t id_bytes, const uint8_t *d_bases, const uint8_t *d_quals, int qual_fill, const uint64_t *h_read_off,
+                      uint64_t text_bytes[2]) {
+  if (!h || !h_read_off || !text_bytes) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (paired && (n_reads & 1)) { g_err = "a paired block with an odd number of reads"; return FQSX_E_ARG; }
+  if (h_read_off[0] != 0) { g_err = "read offsets must start at 0"; return FQSX_E_ARG; }
+  if (ids && !id_len && n_reads) { g_err = "ids without their lengths"; return FQSX_E_ARG; }
+  const u64 n = n_reads, n_bases = h_read_off[n];
+  if ((n_bases && !d_bases) || (qual_fill & ~0xff)) { g_err = "bases missing or a fill that is no byte"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(h));
+  const u32 nxt = h->cur ^ 1u;
+  if (n == 0) {
+    h->cur = nxt;
+    text_bytes[0] = text_bytes[1] = h->text_n[0] = h->text_n[1] = 0;
+    return FQSX_OK;
+  }
+  FtCfg c;
+  memset(&c, 0, sizeof(c));
+  c.n = n_reads; c.paired = paired ? 1u : 0u;
+  c.n_tiles = (u32)((n + FQSX_FT_RTILE - 1) / FQSX_FT_RTILE);
+  DEVCHK(dfit(h, h->d_roff, h->roff_cap, n + 1, n + n / 8 + 1, sizeof(u64)));
+  DEVCHK(dfit(h, h->d_tile, h->tile_cap, c.n_tiles, (u64)c.n_tiles + c.n_tiles / 8, FT_N_SUM * sizeof(u64)));
+  DEVCHK(dfit(h, h->d_tile_pre, h->tile_pre_cap, (u64)c.n_tiles + 1, (u64)c.n_tiles + c.n_tiles / 8 + 1, FT_N_SUM * sizeof(u64)));
+  DEVCHK(dfit(h, h->d_rec, h->rec_cap, n, n + n / 8, 2 * sizeof(u64)));
+  DEVCHK(h2d(h, h->d_roff, h_read_off, (n + 1) * sizeof(u64)));
+  if (ids && !ids_on_device) {   // (the path after the id decoder has fallen back to the host)
+    DEVCHK(dfit(h, h->d_ids, h->ids_cap, id_bytes, id_bytes + id_bytes / 8 + 64, 1));
+    DEVCHK(dfit(h, h->d_idlen, h->idlen_cap, n, n + n / 8, sizeof(u32)));
+    if (id_bytes) DEVCHK(h2d(h, h->d_ids, ids, id_bytes));
+    DEVCHK(h2d(h, h->d_idlen, id_len, n * sizeof(u32)));
+    c.ids = h->d_ids; c.id_len = h->d_idlen;
+  } else if (ids) {
+    c.ids = ids; c.id_len = id_len;
+  }
+  c.id_bytes = ids ? id_bytes : 0;
+  c.bases = d_bases; c.quals = d_quals; c.fill = (u32)qual_fill; c.n_bases = n_bases;
+  c.read_off = h->d_roff;
+  c.tile = h->d_tile; c.tile_pre = h->d_tile_pre;
+  c.start = h->d_rec; c.id_off = h->d_rec + h->rec_cap;
+  c.res = h->d_res;
+  DEVCHK(dzero(h, h->d_res, FT_N_RES * sizeof(u64)));
+  // every record checked, and the totals known, before an output buffer is touched (or grown): a refused block leaves the
+  // previous one as it was
+  FT_LAUNCH(h, FT_PASS_SIZES, k_ft_sizes, c.n_tiles, c);
+  FT_LAUNCH(h, FT_PASS_SCAN_TILES, k_ft_scan_tiles, 1, c);
+  u64 res[FT_N_RES];
+  DEVCHK(ft_results(h, res));
+  if (res[FT_ERR_OFFSETS]) { g_err = "read offsets do not ascend"; return FQSX_E_ARG; }
+  if (res[FT_ERR_LENGTH]) { g_err = "a read of 2^24 bases or more"; return FQSX_E_ARG; }
+  if (res[FT_ERR_ID]) { g_err = "an id line of 0 bytes: a line has at least its line feed"; return FQSX_E_ARG; }
+  if (ids && res[FT_RES_ID_BYTES] != id_bytes) { g_err = "the id lengths do not add up to id_bytes"; return FQSX_E_ARG; }
+  if (res[FT_RES_BASES] != n_bases) { g_err = "the read lengths do not add up to the last read offset"; return FQSX_E_ARG; }
+  for (u32 m = 0; m < 2; ++m) {
+    const u64 need = res[FT_RES_TEXT0 + m] + 64;
+    DEVCHK(dfit(h, h->d_text[nxt][m], h->text_cap[nxt][m], need, need + need / 8, 1));
+    c.out[m] = h->d_text[nxt][m];
+    c.out_n[m] = res[FT_RES_TEXT0 + m];
+  }
+  FT_LAUNCH(h, FT_PASS_OFFSETS, k_ft_offsets, c.n_tiles, c);
+  const u64 per_group = (u64)COLS_WAVES * FQ_WAVE;
+  FT_LAUNCH(h, FT_PASS_SCATTER, k_ft_scatter, (u32)((n + per_group - 1) / per_group), c);
+  DEVCHK(ft_results(h, res));   // (the stream is drained: the decoders may write their next block)
+  if (res[FT_ERR_RANGE]) { g_err = "device error in the text scatter: a range outside its buffer"; return FQSX_E_DEVICE; }
+  h->cur = nxt;
+  for (u32 m = 0; m < 2; ++m) text_bytes[m] = h->text_n[m] = c.out_n[m];
+  return FQSX_OK;
+}
+
+int fqsx_fqtext_download(fqsx_fqtext *h, int mate, uint8_t *dst) {
+  if (!h || mate < 0 || mate > 1) { g_err = "bad argument"; return FQSX_E_ARG; }
+  const u64 n = h->text_n[mate];
+  if (n && !dst) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (!n) return FQSX_OK;
+  DEVCHK(dev_enter(h));
+  const u8 *src = h->d_text[h->cur][mate];
+  // piece k + 1 is on its way into one half of the pinned buffer while piece k leaves the other for dst
+  const u64 n_pieces = (n + FT_PIN_HALF - 1) / FT_PIN_HALF;
+  DEVCHK(d2h(h, h->h_pin, src, std::min<u64>(n, FT_PIN_HALF)));
+  for (u64 k = 0; k < n_pieces; ++k) {
+    DEVCHK(dev_sync(h));
+    if (k + 1 < n_pieces) DEVCHK(d2h(h, h->h_pin + ((k + 1) & 1) * FT_PIN_HALF, src + (k + 1) * FT_PIN_HALF, std::min<u64>(n - (k + 1) * FT_PIN_HALF, FT_PIN_HALF)));
+    memcpy(dst + k * FT_PIN_HALF, h->h_pin + (k & 1) * FT_PIN_HALF, std::min<u64>(n - k * FT_PIN_HALF, FT_PIN_HALF));
+  }
+  return FQSX_OK;
+}
+
+int fqsx_fqtext_set_profiling(fqsx_fqtext *h, int enable) {
+  if (!h) return FQSX_E_ARG;
+  h->profiling = enable != 0;
+  return FQSX_OK;
+}
+int fqsx_fqtext_kernel_times(fqsx_fqtext *h, double out[8]) {
+  if (!h || !out) return FQSX_E_ARG;
+  for (u32 k = 0; k < FT_N_PASS; ++k) { out[k] = h->pass_ms[k]; out[FT_N_PASS + k] = (double)h->pass_n[k]; }
   return FQSX_OK;
 }
 

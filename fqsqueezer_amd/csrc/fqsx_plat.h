@@ -108,6 +108,15 @@ FQ_DEV u32 wave_excl_scan32(u32 v) {
   }
   return x - v;
 }
+FQ_DEV u64 wave_excl_scan64(u64 v) {
+  u64 x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    u64 y = __shfl_up(x, o, 64);
+    if ((int)(threadIdx.x & 63u) >= o) x += y;
+  }
+  return x - v;
+}
 FQ_DEV void lds_inc32(u32 *p) { atomicAdd(p, 1u); }
 FQ_DEV void lds_or64(u64 *p, u64 v) { atomicOr((unsigned long long *)p, (unsigned long long)v); }
 FQ_DEV bool wave_any(bool p) { return __ballot(p) != 0ull; }
@@ -184,6 +193,7 @@ static thread_local u32 fq_emu_block = 0, fq_emu_nblocks = 1;
 FQ_DEV u32 wave_sum32(u32 v) { return v; }
 FQ_DEV u64 wave_sum64(u64 v) { return v; }
 FQ_DEV u32 wave_excl_scan32(u32) { return 0; }
+FQ_DEV u64 wave_excl_scan64(u64) { return 0; }
 FQ_DEV void lds_inc32(u32 *p) { ++*p; }
 FQ_DEV void lds_or64(u64 *p, u64 v) { *p |= v; }
 FQ_DEV bool wave_any(bool p) { return p; }

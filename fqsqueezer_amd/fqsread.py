@@ -3,16 +3,19 @@ codec.QualCodec.decode_block) from the read lengths of the meta stream (codec.Me
 files fqsfile writes and on those of the reference's `fqs e`.  decompress_reads gives lengths, bases and qualities (the id
 stream, if the file has one, is skipped); decompress_records also restores the read ids (codec.IdCodec.decode_block: the GPU id
 decoder on a stream of its own, the host decoder for files whose ids are beyond the kernel's staging limits) and
-decompress_fastq assembles the FASTQ text `fqs d` writes.  Command line: python -m fqsqueezer_amd.fqsread d in.fqs -out a.fq
-[-out2 b.fq]."""
+decompress_fastq assembles the FASTQ text `fqs d` writes.  decompress_fastq_chunks is the streaming form: the file is read block
+by block (hostpipe.iter_fqs), the decoders leave their columns on the device, the text is assembled there
+(codec.FastqText) and comes back one container block at a time.  Command line: python -m fqsqueezer_amd.fqsread d in.fqs
+-out a.fq [-out2 b.fq] [-host-text], which writes every block's text as it arrives."""
 from __future__ import annotations
 
+import os
 from typing import Iterator, List, Optional, Tuple, Union
 
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DnaCodec, FqsxError, IdCodec, MetaCodec, QualCodec
+from .codec import DnaCodec, FastqText, FqsxError, IdCodec, MetaCodec, QualCodec
 
 
 def decompress_reads(data: bytes, device: int = 0, lib_path: Optional[str] = None) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
@@ -59,10 +62,12 @@ class _Ids:
         self.seen: List[tuple] = []   # (streams, n_reads) of the blocks decoded on the GPU so far
         self.fell_back = False
 
-    def decode(self, streams, n_reads: int):
+    def decode(self, streams, n_reads: int, dev: bool = False):
+        """(ids, id_off) of the block; dev: (d_ids, d_id_len, id_bytes) in device memory while the kernel decodes the file and
+        (ids, id_len uint32[], id_bytes) as host arrays once the host decoder has taken over."""
         if self.on_gpu:
             try:
-                out = self.dec.decode_block(streams, n_reads, self.paired)
+                out = (self.dec.decode_block_dev if dev else self.dec.decode_block)(streams, n_reads, self.paired)
                 self.seen.append((streams, n_reads))
                 return out
             except FqsxError as e:
@@ -74,7 +79,8 @@ class _Ids:
             for st, n in self.seen:
                 self.dec.decode_block(st, n, self.paired)
             self.seen = []
-        return self.dec.decode_block(streams, n_reads, self.paired)
+        ids, id_off = self.dec.decode_block(streams, n_reads, self.paired)
+        return (ids, np.diff(id_off).astype(np.uint32), len(ids)) if dev else (ids, id_off)
 
     def close(self):
         self.dec.close()
@@ -179,6 +185,105 @@ def decompress_fastq(data: bytes, device: int = 0, lib_path: Optional[str] = Non
     return (b"".join(parts[0]), b"".join(parts[1])) if paired else b"".join(parts[0])
 
 
+def _mates(text: np.ndarray, rec_off: np.ndarray, paired: bool):
+    """a block's text as decompress_fastq_chunks yields it: record i of a paired block goes to output i & 1"""
+    if not paired:
+        return text.tobytes()
+    n = len(rec_off) - 1
+    return tuple(_take(text, rec_off, np.arange(m, n, 2, dtype=np.int64)).tobytes() for m in (0, 1))
+
+
+def decompress_fastq_chunks(src, device: int = 0, lib_path: Optional[str] = None, stats: Optional[dict] = None, gpu_ids: bool = True,
+                            gpu_text: bool = True) -> Iterator[Union[bytes, Tuple[bytes, bytes]]]:
+    """decompress_fastq block by block: a generator over the container blocks of the file `src` (a path, a binary file object
+    or bytes), each item the FASTQ text of one block -- bytes for a single-end file, (mate 1 text, mate 2 text) for a paired
+    one.  The file is read as the blocks are asked for (hostpipe.iter_fqs).  Per block the meta stream is decoded on the host,
+    the DNA, quality and id decoders run side by side and leave their columns in device memory, codec.FastqText assembles
+    the text there, and its download runs on a worker thread while the next block decodes: a run holds one block of streams
+    and two blocks of text.  quality_mode none: the assembler fills in 33 + quality_thr; id_mode none: its constant id line.
+    After a staging-limit fallback of the id decoder (_Ids) the ids reach the assembler as host arrays.  gpu_text=False: the
+    same chunks through the decoders' host entry points and fastq_text / _take.  stats: as decompress_records, plus 'text':
+    {'gpu_text', 'bytes': [mate 1, mate 2], 'blocks'} and -- stats['profile_text'] set by the caller -- 'kernels'."""
+    import io
+    from concurrent.futures import ThreadPoolExecutor
+    own = isinstance(src, (bytes, bytearray, memoryview, str, os.PathLike))
+    f = io.BytesIO(src) if isinstance(src, (bytes, bytearray, memoryview)) else open(src, "rb") if own else src
+    dna = meta = qual = idd = text = None
+    pool = ThreadPoolExecutor(max_workers=4)
+    written, n_blocks = [0, 0], 0
+    try:
+        blocks = hp.iter_fqs(f)
+        header = next(blocks)
+        threads, paired = header[4], header[5] >= 2
+        stored = hp.stored_streams(header)
+        fill = 33 + header[8]
+        dna = DnaCodec(header, device=device, lib_path=lib_path)
+        meta = MetaCodec(threads, lib_path=lib_path)
+        qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
+        idd = _Ids(header, device, lib_path, gpu_ids) if hp.STREAM_ID in stored else None
+        if gpu_text:
+            text = FastqText(device=device, lib_path=lib_path)
+            text.set_profiling(bool(stats and stats.get("profile_text")))
+
+        def download():
+            return (text.download(0).tobytes(), text.download(1).tobytes()) if paired else text.download(0).tobytes()
+
+        def count(chunk):
+            nonlocal n_blocks
+            n_blocks += 1
+            for m, part in enumerate(chunk if paired else (chunk,)):
+                written[m] += len(part)
+            return chunk
+
+        pending = None   # the download of the block assembled last
+        for g, blk in enumerate(blocks):
+            st = lambda sid: [blk.streams[w][sid] for w in range(threads)]   # noqa: E731
+            # (dev: what the assembler takes -- device pointers from the id kernel, host arrays with their lengths from the host decoder)
+            ji = pool.submit(idd.decode, st(hp.STREAM_ID), blk.n_reads, bool(gpu_text)) if idd is not None else None
+            read_len = meta.decode_block(st(hp.STREAM_META), blk.n_reads, paired)
+            off = np.zeros(blk.n_reads + 1, dtype=np.uint64)
+            off[1:] = np.cumsum(read_len, dtype=np.uint64)
+            if not gpu_text:
+                jd = pool.submit(dna.decode_block, st(hp.STREAM_DNA), off, g)
+                jq = pool.submit(qual.decode_block, st(hp.STREAM_QUALITY), off) if qual is not None else None
+                quals = jq.result() if jq is not None else np.full(int(off[-1]), fill, dtype=np.uint8)
+                if ji is not None:
+                    ids, id_off = ji.result()
+                else:
+                    ids = np.tile(np.frombuffer(b"@\n", dtype=np.uint8), blk.n_reads)
+                    id_off = np.arange(blk.n_reads + 1, dtype=np.uint64) * np.uint64(2)
+                yield count(_mates(*fastq_text(read_len, jd.result(), quals, ids, id_off), paired))
+                continue
+            jd = pool.submit(dna.decode_block_dev, st(hp.STREAM_DNA), off, g)
+            jq = pool.submit(qual.decode_block_dev, st(hp.STREAM_QUALITY), off) if qual is not None else None
+            d_quals = jq.result() if jq is not None else None
+            d_bases = jd.result()
+            ids, id_len, id_bytes = ji.result() if ji is not None else (None, None, None)
+            done = pending.result() if pending is not None else None   # (one call at a time on the assembler's handle)
+            text.block(off, d_bases, d_quals, ids=ids, id_len=id_len, id_bytes=id_bytes, paired=paired, qual_fill=fill)
+            pending = pool.submit(download)
+            if done is not None:
+                yield count(done)
+        if pending is not None:
+            done, pending = pending.result(), None
+            yield count(done)
+    finally:
+        pool.shutdown(wait=True)
+        if stats is not None:
+            stats["text"] = {"gpu_text": bool(gpu_text), "bytes": list(written), "blocks": n_blocks}
+            if text is not None and stats.get("profile_text"):
+                stats["text"]["kernels"] = text.kernel_times()
+            if idd is not None:
+                stats["id_host_fallback"] = idd.fell_back
+                if idd.on_gpu:
+                    stats["id_decoder"] = idd.dec.stats()
+        for c in (dna, meta, qual, idd, text):
+            if c is not None:
+                c.close()
+        if own:
+            f.close()
+
+
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m fqsqueezer_amd.fqsread", description="decompress a .fqs file to FASTQ on the GPU")
@@ -188,15 +293,23 @@ def main(argv=None) -> int:
     ap.add_argument("-out2")
     ap.add_argument("-device", type=int, default=0)
     ap.add_argument("-lib", default=None, help="path of the library to load (default: the package's libfqsx.so)")
+    ap.add_argument("-host-text", dest="host_text", action="store_true", help="assemble the FASTQ text on the host instead of the GPU")
     a = ap.parse_args(argv)
-    text = decompress_fastq(open(a.input, "rb").read(), device=a.device, lib_path=a.lib)
-    if isinstance(text, tuple):
-        if not a.out2:
+    with open(a.input, "rb") as f:
+        head = f.read(18)
+        if len(head) < 18 or head[0] != 17:
+            raise ValueError("not a .fqs file (header length byte)")
+        paired = head[6] >= 2   # header byte 5: the DNA mode
+        if paired and not a.out2:
             ap.error("a paired file needs -out2")
-        open(a.out, "wb").write(text[0])
-        open(a.out2, "wb").write(text[1])
-    else:
-        open(a.out, "wb").write(text)
+        f.seek(0)
+        with open(a.out, "wb") as o1, (open(a.out2, "wb") if paired else open(os.devnull, "wb")) as o2:
+            for chunk in decompress_fastq_chunks(f, device=a.device, lib_path=a.lib, gpu_text=not a.host_text):
+                if paired:
+                    o1.write(chunk[0])
+                    o2.write(chunk[1])
+                else:
+                    o1.write(chunk)
     return 0
 
 

@@ -270,6 +270,62 @@ def parse_fqs(data: bytes) -> Tuple[bytes, List[FqsBlock]]:
     return header, blocks
 
 
+def iter_fqs(fileobj, read_size: int = 1 << 20):
+    """parse_fqs over a binary file object, block by block: yields the 17 header bytes first and then one FqsBlock at a time.
+    The file is read in pieces of at most read_size bytes, a piece only when the bytes at hand do not suffice, so that never
+    more than the block being completed and one piece are held.  ValueError as parse_fqs, and for a file that ends inside a
+    block."""
+    buf, pos = bytearray(), 0
+
+    def need(k: int, inside: bool = True) -> bool:
+        """k bytes at hand from pos on; False at the end of the file if that is allowed here"""
+        while len(buf) - pos < k:
+            piece = fileobj.read(read_size)
+            if not piece:
+                if inside or len(buf) - pos:
+                    raise ValueError("not a complete .fqs file: it ends inside a block")
+                return False
+            buf.extend(piece)
+        return True
+
+    def varint() -> int:
+        nonlocal pos
+        need(1)
+        need(2 if buf[pos] >> 7 == 0 else 3 if buf[pos] >> 6 == 0b10 else 4)
+        v, pos = get_varint(buf, pos)
+        return v
+
+    if not need(1, inside=False) or buf[0] != 17:
+        raise ValueError("not a .fqs file (header length byte)")
+    try:
+        need(18)
+    except ValueError:
+        raise ValueError("not a .fqs file (magic)") from None
+    header = bytes(buf[1:18])
+    if header[:4] != b"KCSD":
+        raise ValueError("not a .fqs file (magic)")
+    pos = 18
+    T, sids = header[4], stored_streams(header)
+    yield header
+    while True:
+        del buf[:pos]   # (what is left over belongs to the next block)
+        pos = 0
+        if not need(1, inside=False):
+            return
+        blk = FqsBlock(varint())
+        for _ in range(T):
+            blk.offsets.append(varint())
+            st = {}
+            for sid in sids:
+                size = varint()
+                need(size)
+                st[sid] = bytes(buf[pos:pos + size])
+                del buf[:pos + size]   # (the stream is in the block now: the buffer keeps what follows it, less than a piece)
+                pos = 0
+            blk.streams.append(st)
+        yield blk
+
+
 def fqs_chunks(header: bytes, blocks: Iterable[FqsBlock]):
     """The file as a sequence of byte chunks: the header, then one chunk per container block."""
     yield bytes([17]) + header

@@ -97,6 +97,11 @@ int fqsx_dna_encode_block_dev(fqsx_dna *, const uint8_t *d_bases, const uint64_t
 int fqsx_dna_decode_block(fqsx_dna *, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off,
                           uint32_t n_reads, uint32_t generation, uint8_t *bases_out);
 
+/* The same, leaving the block in device memory: *d_bases_out is the codec's own output buffer, valid until the next call on
+ * the codec; null on error.  The call returns with the codec's stream drained, so another stream may read the block. */
+int fqsx_dna_decode_block_dev(fqsx_dna *, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off,
+                              uint32_t n_reads, uint32_t generation, const uint8_t **d_bases_out);
+
 /* Accounting counters summed over workers since creation:
  * [0] global probes [1] global slots read [2] local probes [3] local slots read
  * [4] global inserts [5] slots read by them [6] siv words touched [7] context slots read
@@ -292,6 +297,12 @@ void fqsx_idg_destroy(fqsx_idg *);
  * per-worker output capacity of the decoder (bytes, at least 64). */
 int fqsx_idg_decode_block(fqsx_idg *, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
                           const uint8_t **ids_out, const uint64_t **id_off_out);
+/* fqsx_idg_decode_block leaving the block in device memory: *d_ids_out = the block's id lines back to back in block order,
+ * *d_id_len_out = their n_reads lengths, *id_bytes_out = the bytes of *d_ids_out.  Both buffers are the codec's, valid until
+ * its next call; null on error.  Errors, fqsx_idg_error_kind and the run-again behaviour are those of fqsx_idg_decode_block;
+ * the call returns with the codec's stream drained. */
+int fqsx_idg_decode_block_dev(fqsx_idg *, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
+                              const uint8_t **d_ids_out, const uint32_t **d_id_len_out, uint64_t *id_bytes_out);
 int fqsx_id_decode_block(fqsx_id *, const uint8_t *const *streams, const uint64_t *lens, uint32_t n_reads, int paired,
                          const uint8_t **ids_out, const uint64_t **id_off_out);
 /* out[0] = blocks the decoder ran again, out[1] / out[2] / out[3] = growths of the small table, the big table and the decoder's
@@ -387,6 +398,32 @@ int fqsx_cols_bases(fqsx_cols *, uint8_t *out);
 int fqsx_cols_download(fqsx_cols *, const void *d_src, void *h_dst, uint64_t n_bytes);
 int fqsx_cols_set_profiling(fqsx_cols *, int enable);
 int fqsx_cols_kernel_times(fqsx_cols *, double out[4]);
+
+/* Columns to FASTQ text on the device (csrc/fqsx_fqtext.h): the text `fqs d` writes for one container block, from the columns
+ * the *_decode_block_dev entry points leave in device memory.  Per read: id line (with its line feed) + bases + "\n+\n" +
+ * qualities + "\n"; paired != 0: read i goes to output i & 1 (application.cpp:871-889, 980-982).
+ * fqsx_fqtext_block: ids = the id lines back to back (id_bytes of them) and id_len[n_reads] their lengths, both in device
+ *   memory (ids_on_device != 0) or both host arrays that the call uploads; ids == NULL: every id line is "@\n".  d_bases /
+ *   d_quals: device columns under h_read_off (host, n_reads + 1 offsets from 0); d_quals == NULL: every quality is the byte
+ *   qual_fill.  text_bytes[m] = bytes of output m.  The call reads buffers other handles own -- their streams must be
+ *   drained -- and returns when the text is complete in the handle's own buffers.  Every record is checked on the device
+ *   before anything is stored: offsets that do not ascend, a read of 2^24 bases or more, an id line of 0 bytes, id lengths
+ *   that do not add up to id_bytes, paired with an odd n_reads: FQSX_E_ARG; a range outside a buffer: FQSX_E_DEVICE.  A
+ *   refused call leaves the text of the previous block as it was.
+ * fqsx_fqtext_download: output `mate` of the block assembled last into dst[text_bytes[mate]] (through a pinned staging buffer).
+ *   Calls on one handle are serialised by the caller: a download may run on another host thread while the decoders work on
+ *   the next block, but the next fqsx_fqtext_block waits for it.
+ * fqsx_fqtext_kernel_times (after fqsx_fqtext_set_profiling): out[0..3] = milliseconds of the size, tile scan, offset and
+ *   scatter kernels, out[4..7] = their launches. */
+typedef struct fqsx_fqtext fqsx_fqtext;
+int fqsx_fqtext_create(int device, fqsx_fqtext **out);
+void fqsx_fqtext_destroy(fqsx_fqtext *);
+int fqsx_fqtext_block(fqsx_fqtext *, uint32_t n_reads, int paired, const uint8_t *ids, const uint32_t *id_len, int ids_on_device,
+                      uint64_t id_bytes, const uint8_t *d_bases, const uint8_t *d_quals, int qual_fill, const uint64_t *h_read_off,
+                      uint64_t text_bytes[2]);
+int fqsx_fqtext_download(fqsx_fqtext *, int mate, uint8_t *dst);
+int fqsx_fqtext_set_profiling(fqsx_fqtext *, int enable);
+int fqsx_fqtext_kernel_times(fqsx_fqtext *, double out[8]);
 
 const char *fqsx_last_error(void);
 const char *fqsx_version(void);
