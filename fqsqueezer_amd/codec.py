@@ -295,6 +295,7 @@ class IdCodec:
     def __init__(self, header: bytes, lib_path: Optional[str] = None, device: Optional[int] = None):
         self._lib = load_library(lib_path)
         self.T = header[4]
+        self._mode = header[7]   # 0 lossless, 1 instrument
         self._h = C.c_void_p()
         self._gpu = device is not None
         L = self._lib
@@ -317,8 +318,34 @@ class IdCodec:
         f = self._lib.fqsx_idg_encode_block if self._gpu else self._lib.fqsx_id_encode_block
         rc = f(self._h, ids.ctypes.data, id_off.ctypes.data, len(id_off) - 1, int(paired), self._streams, self._lens)
         if rc:
-            raise FqsxError(f"fqsx_id{'g' if self._gpu else ''}_encode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
+            raise self._encode_error(rc, ids, id_off, paired)
         return [C.string_at(self._streams[w], self._lens[w]) for w in range(self.T)]
+
+    def _encode_error(self, rc: int, ids: np.ndarray, id_off: np.ndarray, paired: bool) -> FqsxError:
+        """GPU flavour: `staging` is True if the kernel met an id beyond its staging sizes or its list of instrument names (kinds
+        5 and 6); its models have moved by then, so the file goes on with the host flavour (fqsfile.encode_blocks).  The host
+        flavour never sets the library's error text: its one return code gets its message here."""
+        L = self._lib
+        e = FqsxError()
+        e.staging = False
+        if self._gpu:
+            L.fqsx_idg_error_kind.argtypes = [C.c_void_p]
+            e.staging = rc == -5 and L.fqsx_idg_error_kind(self._h) in (5, 6)
+            msg = L.fqsx_last_error().decode()
+        elif paired and (len(id_off) - 1) & 1:
+            msg = "a paired block with an odd number of reads"
+        else:   # (the two reasons for which the host coder refuses an id, fqsx_host.cpp id_lossless / id_instrument)
+            ends = np.zeros(len(ids) + 1, dtype=np.int64)
+            np.cumsum((ids == 0x2E) | (ids == 0x20) | (ids == 0x3A), out=ends[1:])
+            off = id_off.astype(np.int64)
+            if self._mode == 1 and bool((ends[off[1:]] == ends[off[:-1]]).any()):
+                msg = "no instrument name: an id line without '.', ' ' or ':'"
+            elif len(ids) and int(ids.max()) >= 128:
+                msg = "byte outside the 128-symbol alphabet in an id line"
+            else:
+                msg = "bad argument"
+        e.args = (f"fqsx_id{'g' if self._gpu else ''}_encode_block: {rc}: {msg}",)
+        return e
 
     def decode_block(self, streams, n_reads: int, paired: bool = False):
         """Inverse of encode_block: the T id streams of a block -> (ids uint8[], id_off uint64[n_reads + 1]), the id lines the
@@ -362,6 +389,11 @@ class IdCodec:
         if rc:
             raise self._decode_error("fqsx_idg_decode_block_dev", rc)
         return ids.value or 0, idl.value or 0, int(nb.value)
+
+    def error_kind(self) -> int:
+        """GPU flavour: what the kernel reported in the last block (fqsx_idg_error_kind; 0 = nothing)"""
+        self._lib.fqsx_idg_error_kind.argtypes = [C.c_void_p]
+        return int(self._lib.fqsx_idg_error_kind(self._h)) if self._gpu else 0
 
     def stats(self) -> dict:
         """GPU flavour: how often the decoder had to grow (fqsx_idg_stats) and its capacities."""

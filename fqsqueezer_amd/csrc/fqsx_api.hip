@@ -2564,7 +2564,7 @@ struct fqsx_idg : DevCtx {
   std::vector<u32> h_idlen;
   std::vector<u8> h_ids;
   u64 n_retry, n_grow_small, n_grow_big, n_grow_out;
-  u32 last_kind = 0;             // the kernel's error word of the last decode (fqsx_idg_error_kind)
+  u32 last_kind = 0;             // the kernel's error word of the last encode or decode (fqsx_idg_error_kind)
   u64 dec_out_init = 1u << 18;   // first per-worker capacity of the decoder's output
 };
 
@@ -2665,6 +2665,7 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
   if ((rc = d2h_sync(c, q->h_lens.data(), cfg.lens, (T + 2 + 2 * T) * sizeof(u64)))) return rc;
   memcpy(q->h_state.data(), q->h_lens.data() + T + 2, 4 * T * sizeof(u32));
   const u32 err = (u32)q->h_lens[T];
+  q->last_kind = err;
   if (err) {
     static const char *what[] = {"", "byte outside the 128-symbol alphabet", "no instrument name", "stream overflow", "model table full",
                                  "id, token count or instrument name beyond the kernel's staging sizes", "more than 4096 instrument names"};
@@ -2844,9 +2845,10 @@ int fqsx_idg_state(fqsx_idg *q, uint32_t *out) {
   memcpy(out, q->h_state.data(), 4 * (u64)q->T * sizeof(u32));
   return FQSX_OK;
 }
-// What the kernel reported in the last fqsx_idg_decode_block: 0 none, 3 output, 4 model table (both grown and run again unless the
-// stream cannot be valid), 5 a line, its tokens or an instrument name beyond the staging sizes, 6 more than 4096 instrument names
-// (5 and 6: decode the file with fqsx_id_decode_block), 7 malformed or truncated stream
+// What the kernel reported in the last fqsx_idg_encode_block / fqsx_idg_decode_block: 0 none, 1 a byte >= 128, 2 no instrument name
+// (both: the encoder only), 3 output, 4 model table (the decoder grows both and runs again unless the stream cannot be valid), 5 a
+// line, its tokens or an instrument name beyond the staging sizes, 6 more than 4096 instrument names (5 and 6: code the file with
+// fqsx_id_encode_block / fqsx_id_decode_block, whose coder has no such limits), 7 malformed or truncated stream
 int fqsx_idg_error_kind(fqsx_idg *q) { return q ? (int)q->last_kind : FQSX_E_ARG; }
 int fqsx_idg_set_profiling(fqsx_idg *q, int enable) {
   if (!q) return FQSX_E_ARG;

@@ -12,14 +12,16 @@
 #pragma once
 #include "fqsx_qual.h"   // q_hash, q_find; the range coder (fqsx_rc.h)
 
+// (fqsfile.py mirrors the next three numbers and cfg.mtf_cap's rule in its pre-scan, _ID_LINE_MAX / _ID_TOKENS_MAX / _ID_NAME_MAX:
+// a file with an id beyond them goes to the host coder, which has no limits)
 #define IDK_MAX_ID 1024u      // bytes of one id line (with its line feed) a worker stages in LDS
 #define IDK_MAX_TOK 128u      // tokens of one id
-#define IDK_NAME 64u          // bytes of a move-to-front entry: length byte + up to 63 characters
+#define IDK_NAME 64u          // bytes of a move-to-front entry: length byte + up to 62 characters (nl + 1 <= IDK_NAME - 1)
 #define IDK_BIG_U64 66u       // big slot: key, 64 words of statistics (256 x u16), total
 #define IDK_FIXED 12u         // mtf_flag, mtf_code[0..6], mtf_byte[0..3]
 enum { IDM_FLAGS = 1, IDM_PE_FLAGS, IDM_NUM_SMALL, IDM_LIT_SAME, IDM_LIT_SAME_LEN, IDM_NUM_SIZE, IDM_LITERAL, IDM_PLAIN };
 enum { IDK_ERR_BYTE = 1 /* byte >= 128 (the reference's 128-symbol models, id.cpp:99,104) */, IDK_ERR_NO_INSTRUMENT = 2, IDK_ERR_OUT = 3,
-       IDK_ERR_TABLE = 4, IDK_ERR_TOO_LONG = 5 /* id longer than IDK_MAX_ID, more than IDK_MAX_TOK tokens, instrument name beyond 63 bytes */,
+       IDK_ERR_TABLE = 4, IDK_ERR_TOO_LONG = 5 /* id longer than IDK_MAX_ID, more than IDK_MAX_TOK tokens, instrument name beyond IDK_NAME - 2 = 62 bytes */,
        IDK_ERR_MTF_FULL = 6 };
 
 struct IdCfg {
@@ -292,7 +294,7 @@ FQ_DEV void idk_id_lossless(IdK &k, const u8 *p, u32 size) {
 FQ_DEV void idk_id_instrument(IdK &k, const u8 *p, u32 size) {
   IdShared *sm = k.sm;
   if (size > IDK_MAX_ID) { k.err = IDK_ERR_TOO_LONG; return; }
-  if (!idk_stage(k, p, size)) { k.err = IDK_ERR_BYTE; return; }
+  const bool ascii = idk_stage(k, p, size);   // false: a byte >= 128 somewhere in the line -- an error only in a new name (below)
   u32 n = 0;
   while (n < size && sm->cur[n] != '.' && sm->cur[n] != ' ' && sm->cur[n] != ':') ++n;
   if (n == size) { k.err = IDK_ERR_NO_INSTRUMENT; return; }   // the reference would write its terminator over the first base here
@@ -317,6 +319,11 @@ FQ_DEV void idk_id_instrument(IdK &k, const u8 *p, u32 size) {
 #endif
   }
   if (code < 0) {
+    if (!ascii) {   // only the new name's bytes meet the 128-symbol models: what follows the name is not coded (id.cpp:421-495)
+      bool bad = false;
+      for (u32 i = FQ_LANE; i < n; i += FQ_WAVE) bad |= sm->cur[i] >= 128;
+      if (wave_any(bad)) { k.err = IDK_ERR_BYTE; return; }
+    }
     idk_fixed(k, 0, 11, 0);
     // the name and a terminating NUL through compress_lossless (id.cpp:441-446)
     FQ_SYNC();

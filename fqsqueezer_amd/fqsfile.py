@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DeviceBlock, DnaCodec, IdCodec, MetaCodec, QualCodec, parse_fastq, sort_order
+from .codec import DeviceBlock, DnaCodec, FqsxError, IdCodec, MetaCodec, QualCodec, parse_fastq, sort_order
 
 
 def _gpu_groups(rec: hp.Records, device: int, lib_path: Optional[str]):
@@ -18,13 +18,48 @@ def _gpu_groups(rec: hp.Records, device: int, lib_path: Optional[str]):
     return sort_order(bases, off, device=device, lib_path=lib_path)
 
 
+class _Ids:
+    """The id coder of one file: the GPU kernel, or -- once the kernel reports an id beyond its staging limits or its list of
+    instrument names (IdCodec.encode_block, `staging`) -- the host coder, brought to the same state by coding again the id
+    columns of the blocks written so far (of which only the index arrays are kept; ids_of(idx) cuts the columns again).  The
+    blocks already written stay as they are: both coders write the same bytes.  The encoder's twin of fqsread._Ids."""
+
+    def __init__(self, header: bytes, device: int, lib_path: Optional[str], gpu_ids: bool, paired: bool, ids_of):
+        self.header, self.lib_path, self.paired, self.ids_of = header, lib_path, paired, ids_of
+        self.enc = IdCodec(header, lib_path=lib_path, device=device if gpu_ids else None)
+        self.on_gpu = gpu_ids
+        self.seen = []   # the index arrays of the blocks coded on the GPU so far
+        self.fell_back = False
+
+    def encode(self, idx, ids, id_off):
+        if self.on_gpu:
+            try:
+                out = self.enc.encode_block(ids, id_off, self.paired)
+                self.seen.append(idx)
+                return out
+            except FqsxError as e:
+                if not getattr(e, "staging", False):
+                    raise
+            self.enc.close()
+            self.enc = IdCodec(self.header, lib_path=self.lib_path)
+            self.on_gpu, self.fell_back = False, True
+            for j in self.seen:
+                self.enc.encode_block(*self.ids_of(j), self.paired)
+            self.seen = []
+        return self.enc.encode_block(ids, id_off, self.paired)
+
+    def close(self):
+        self.enc.close()
+
+
 def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device: int, lib_path: Optional[str], stats: Optional[dict] = None,
-                  gpu_ids: bool = True):
+                  gpu_ids: bool = True, ids_of=None):
     """Generator of the file's container blocks.  Per block the four coders run side by side, as the reference's worker
     codes meta, id, DNA and quality of a read in one loop (application.cpp:633-641): the DNA kernels and the quality kernel
     and the id kernel on their own HIP streams (host threads inside the C ABI, which releases the GIL), the meta coder on a host
     thread meanwhile.  arrays(idx) may hand back the bases as a codec.DeviceBlock (a block cut on the device, its qualities with
-    it): the DNA and quality coders then read it where it lies."""
+    it): the DNA and quality coders then read it where it lies.  ids_of(idx): the id columns of a block alone (default: from
+    arrays), for the id coder's change-over to the host coder in mid-file (_Ids); stats then has "id_host_fallback" True."""
     from concurrent.futures import ThreadPoolExecutor
     threads = header[4]
     stored = hp.stored_streams(header)
@@ -32,7 +67,7 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
     meta = MetaCodec(threads, lib_path=lib_path)
     # (the id stream comes from the GPU coder too: fqsx_idg_*, one wavefront per worker on a stream of its own; gpu_ids = False:
     # the host coder, one host thread per worker -- the same bytes)
-    idc = IdCodec(header, lib_path=lib_path, device=device if gpu_ids else None) if hp.STREAM_ID in stored else None
+    idc = _Ids(header, device, lib_path, gpu_ids, paired, ids_of or (lambda idx: arrays(idx)[2:4])) if hp.STREAM_ID in stored else None
     qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
     pool = ThreadPoolExecutor(max_workers=3)
     try:
@@ -48,7 +83,7 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
                 if qual is not None:
                     jobs[hp.STREAM_QUALITY] = pool.submit(qual.encode_block, quals, off)
             if idc is not None:
-                jobs[hp.STREAM_ID] = pool.submit(idc.encode_block, ids, id_off, paired)
+                jobs[hp.STREAM_ID] = pool.submit(idc.encode, idx, ids, id_off)
             st = {hp.STREAM_META: meta.encode_block(np.diff(off.astype(np.int64)).astype(np.uint32), paired)}
             for k, f in jobs.items():
                 st[k] = f.result()
@@ -61,6 +96,7 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
         if stats is not None:
             stats["dna"] = dna.stats()
             stats["dna_capacity"] = dna.capacity()
+            stats["id_host_fallback"] = idc is not None and idc.fell_back
             try:   # everything this process holds on the device at the end of the file: DNA tables + quality models + id models + block buffers
                 import torch
                 free, total = torch.cuda.mem_get_info(device)
@@ -77,47 +113,92 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
             qual.close()
 
 
-def _encode(header: bytes, blocks, arrays, sizes_of, paired: bool, device: int, lib_path: Optional[str], gpu_ids: bool = True) -> bytes:
-    return hp.write_fqs(header, encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, gpu_ids=gpu_ids))
+def _encode(header: bytes, blocks, arrays, sizes_of, paired: bool, device: int, lib_path: Optional[str], gpu_ids: bool = True,
+            stats: Optional[dict] = None, ids_of=None) -> bytes:
+    return hp.write_fqs(header, encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids, ids_of=ids_of))
 
 
-# the id kernel stages an id line in LDS: lines up to 1024 bytes, 128 tokens, instrument names up to 63 bytes (csrc/fqsx_idk.h:15-17)
-_ID_LINE_MAX, _ID_TOKENS_MAX = 1024, 128
+# What the id kernel stages of an id line in LDS, the one place on this side that states csrc/fqsx_idk.h's IDK_MAX_ID, IDK_MAX_TOK
+# and IDK_NAME - 2: a line of at most 1024 bytes with its line feed, at most 128 tokens, an instrument name of at most 62 bytes
+_ID_LINE_MAX, _ID_TOKENS_MAX, _ID_NAME_MAX = 1024, 128, 62
+_ID_LITERAL = np.zeros(256, dtype=bool)   # idk_is_lit (id.cpp:57-70): every other byte ends a token, the line feed included
+_ID_LITERAL[list(b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz@")] = True
+_ID_NAME_END = np.zeros(256, dtype=bool)
+_ID_NAME_END[list(b". :")] = True
 
 
-def _ids_fit_the_kernel(*recs) -> bool:
+def _first_at_or_after(marks: np.ndarray, start: np.ndarray, stop: np.ndarray) -> np.ndarray:
+    """per line [start, stop): the position of its first marked byte, stop if it has none (marks: sorted positions)"""
+    if not len(marks):
+        return stop.copy()
+    k = np.searchsorted(marks, start)
+    at = marks[np.minimum(k, len(marks) - 1)]
+    return np.where((k < len(marks)) & (at < stop), at, stop)
+
+
+def _id_lines_fit_the_kernel(ids: np.ndarray, id_off: np.ndarray, id_mode: str) -> bool:
+    """The id kernel's rule (idk_id_lossless / idk_id_instrument / idk_lossless, csrc/fqsx_idk.h) for the id lines `ids` (each
+    with its line feed), in one pass: False if the kernel would answer one of them with IDK_ERR_TOO_LONG.  Lossless mode: the
+    line with its line feed within _ID_LINE_MAX bytes and within _ID_TOKENS_MAX tokens.  Instrument mode: the line within
+    _ID_LINE_MAX; the name -- up to the first '.', ' ' or ':', cut short at a NUL -- within _ID_NAME_MAX bytes; and, as a new
+    name is coded through the lossless path with a terminating NUL, the bytes up to the '.', ' ' or ':' within _ID_TOKENS_MAX
+    tokens with that terminator.  (A line without a name, or with a byte >= 128 where it is coded, is refused by both coders: not a
+    staging matter.)"""
+    off = np.asarray(id_off).astype(np.int64)
+    if len(off) < 2:
+        return True
+    start, stop = off[:-1], off[1:]
+    if int((stop - start).max()) > _ID_LINE_MAX:
+        return False
+    ids = np.asarray(ids)
+    seps = np.zeros(len(ids) + 1, dtype=np.int64)
+    np.cumsum(~_ID_LITERAL[ids], out=seps[1:])
+    if id_mode != "instrument":
+        return int((seps[stop] - seps[start]).max()) <= _ID_TOKENS_MAX
+    end = _first_at_or_after(np.flatnonzero(_ID_NAME_END[ids]), start, stop)
+    named = end < stop
+    name_len = _first_at_or_after(np.flatnonzero(ids == 0), start, end) - start
+    return not bool((named & ((name_len > _ID_NAME_MAX) | (seps[end] - seps[start] + 1 > _ID_TOKENS_MAX))).any())
+
+
+def _ids_fit_the_kernel(id_mode: str, *recs) -> bool:
     """False if an id of the file is beyond what the GPU id coder stages (the host coder, like the reference, has no limits):
-    a cheap pre-scan so that the file falls back to the host coder as a whole instead of failing in mid-file."""
-    for rec in recs:
-        for x in rec.ids:
-            if len(x) > _ID_LINE_MAX or len(x) > 64 and sum(ch in b" :._/-|=#" for ch in x) >= _ID_TOKENS_MAX // 2:
-                return False
-    return True
+    a cheap pre-scan so that the file goes to the host coder as a whole instead of changing over in mid-file.  (What no
+    pre-scan of lines can know, the number of different instrument names a worker meets, is left to that change-over.)"""
+    return all(_id_lines_fit_the_kernel(*hp.id_arrays(rec, np.arange(len(rec))), id_mode) for rec in recs)
 
 
 def compress_records(rec: hp.Records, threads: int, order: str = "s", genome_size_mbp: int = 3100, device: int = 0,
                      lib_path: Optional[str] = None, quality_mode: str = "none", id_mode: str = "none",
-                     quality_thr: int = 20, as_blocks: bool = False, gpu_ids: Optional[bool] = None):
+                     quality_thr: int = 20, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None):
     """`fqs e -s -om <order> -t <threads> -gs <g> -qm <..> -im <..>` on single-end records.  Returns the file's bytes, or
     -- as_blocks -- (header, generator of container blocks) for files too large to hold (hostpipe.fqs_chunks serialises them).
     gpu_ids: the id stream from the GPU kernel (True), from the host coder (False: one thread per worker, no limits on the id
-    lines), or -- None -- the kernel unless an id of the file is beyond its staging limits."""
+    lines), or -- None -- the kernel unless an id of the file is beyond its staging limits.  A file on the kernel that meets
+    more instrument names than a worker's list holds goes on with the host coder from that block (the same bytes).  stats:
+    "gpu_ids" (the choice made), "id_host_fallback" (changed over in mid-file) and what encode_blocks adds."""
     if gpu_ids is None:
-        gpu_ids = id_mode == "none" or _ids_fit_the_kernel(rec)
+        gpu_ids = id_mode == "none" or _ids_fit_the_kernel(id_mode, rec)
+    if stats is not None:
+        stats["gpu_ids"] = gpu_ids
     mode = "se_sorted" if order == "s" else "se_original"
     header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
     sizes = rec.record_sizes()
 
+    def ids_of(idx):
+        return hp.id_arrays(rec, idx)
+
     def arrays(idx):
         bases, off = hp.block_arrays(rec, idx)
-        ids, id_off = hp.id_arrays(rec, idx) if id_mode != "none" else (None, None)
+        ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
         quals = hp.qual_arrays(rec, idx)[0] if quality_mode != "none" else None
         return bases, off, ids, id_off, quals
 
     groups = _gpu_groups(rec, device, lib_path) if mode == "se_sorted" else None
     if as_blocks:
-        return header, encode_blocks(header, hp.form_blocks(rec, mode, groups=groups), arrays, lambda idx: sizes[idx], False, device, lib_path, gpu_ids=gpu_ids)
-    return _encode(header, hp.form_blocks(rec, mode, groups=groups), arrays, lambda idx: sizes[idx], False, device, lib_path, gpu_ids)
+        return header, encode_blocks(header, hp.form_blocks(rec, mode, groups=groups), arrays, lambda idx: sizes[idx], False, device, lib_path, stats=stats,
+                                     gpu_ids=gpu_ids, ids_of=ids_of)
+    return _encode(header, hp.form_blocks(rec, mode, groups=groups), arrays, lambda idx: sizes[idx], False, device, lib_path, gpu_ids, stats, ids_of)
 
 
 def compress_records_pe(rec1: hp.Records, rec2: hp.Records, threads: int, order: str = "s", genome_size_mbp: int = 3100,
@@ -125,14 +206,19 @@ def compress_records_pe(rec1: hp.Records, rec2: hp.Records, threads: int, order:
                         quality_thr: int = 20, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None):
     """`fqs e -p ...` on two mate files (records interleaved mate 1 / mate 2 inside a block).  gpu_ids: see compress_records."""
     if gpu_ids is None:
-        gpu_ids = id_mode == "none" or _ids_fit_the_kernel(rec1, rec2)
+        gpu_ids = id_mode == "none" or _ids_fit_the_kernel(id_mode, rec1, rec2)
+    if stats is not None:
+        stats["gpu_ids"] = gpu_ids
     mode = "pe_sorted" if order == "s" else "pe_original"
     header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
     s1, s2 = rec1.record_sizes(), rec2.record_sizes()
 
+    def ids_of(idx):
+        return hp.id_arrays_pe(rec1, rec2, idx)
+
     def arrays(idx):
         bases, off = hp.block_arrays_pe(rec1, rec2, idx)
-        ids, id_off = hp.id_arrays_pe(rec1, rec2, idx) if id_mode != "none" else (None, None)
+        ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
         quals = hp.qual_arrays_pe(rec1, rec2, idx)[0] if quality_mode != "none" else None
         return bases, off, ids, id_off, quals
 
@@ -143,22 +229,14 @@ def compress_records_pe(rec1: hp.Records, rec2: hp.Records, threads: int, order:
 
     groups = _gpu_groups(rec1, device, lib_path) if mode == "pe_sorted" else None   # mates follow mate 1's order, io.h:541-550
     if as_blocks:
-        return header, encode_blocks(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, stats=stats, gpu_ids=gpu_ids)
-    return _encode(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, gpu_ids)
+        return header, encode_blocks(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, stats=stats,
+                                     gpu_ids=gpu_ids, ids_of=ids_of)
+    return _encode(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, gpu_ids, stats, ids_of)
 
 
-_ID_SEPARATORS = np.zeros(256, dtype=bool)
-_ID_SEPARATORS[list(b" :._/-|=#")] = True
-
-
-def _id_columns_fit_the_kernel(cols: hp.Columns, max_id_line: int) -> bool:
+def _id_columns_fit_the_kernel(cols: hp.Columns, max_id_line: int, id_mode: str) -> bool:
     """_ids_fit_the_kernel on columns: the parser's longest id line (it counts the line feed) and one pass over the id bytes."""
-    if max_id_line - 1 > _ID_LINE_MAX:
-        return False
-    off = cols.id_off.view(np.int64)
-    seps = np.zeros(len(cols.ids) + 1, dtype=np.int64)
-    np.cumsum(_ID_SEPARATORS[cols.ids], out=seps[1:])
-    return not bool(((np.diff(off) - 1 > 64) & (seps[off[1:]] - seps[off[:-1]] >= _ID_TOKENS_MAX // 2)).any())
+    return max_id_line <= _ID_LINE_MAX and _id_lines_fit_the_kernel(cols.ids, cols.id_off.view(np.int64), id_mode)
 
 
 def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: str = "s", genome_size_mbp: int = 3100,
@@ -169,7 +247,8 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
     reference's, params.h:53-78).  The text is parsed on the GPU into columns (codec.parse_fastq), the sort pre-pass runs on the
     base column, and the blocks are cut from the columns with vectorised gathers.  Returns what compress_records* return.
     ValueError: a record whose quality line differs in length from its base line; mate files with different numbers of records.
-    gpu_ids: see compress_records.  stats: "parse" (one dict per input), "gpu_ids" (the choice made) and what encode_blocks adds.
+    gpu_ids: see compress_records.  stats: "parse" (one dict per input), "gpu_ids" (the choice made), "id_host_fallback" (the id coder
+    changed over to the host coder in mid-file) and what encode_blocks adds.
     resident: the base and quality columns stay in device memory (codec.DeviceColumns, one store per input) and the blocks are
     cut there; the same bytes.  Sorted order brings the base column to the host once, for the sort pre-pass; qualities never
     come to the host.  stats then also has "columns" (DeviceColumns.info() per input once the last block is written, with
@@ -214,7 +293,7 @@ def _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, qualit
     if paired and len(cols[0]) != len(cols[1]):
         raise ValueError("the mate files hold different numbers of records: %d and %d" % (len(cols[0]), len(cols[1])))
     if gpu_ids is None:
-        gpu_ids = id_mode == "none" or all(_id_columns_fit_the_kernel(c, st["max_id_line"]) for c, st in zip(cols, parse_stats))
+        gpu_ids = id_mode == "none" or all(_id_columns_fit_the_kernel(c, st["max_id_line"], id_mode) for c, st in zip(cols, parse_stats))
     if stats is not None:
         stats["parse"], stats["gpu_ids"] = parse_stats, gpu_ids
     mode = ("pe_" if paired else "se_") + ("sorted" if order == "s" else "original")
@@ -228,8 +307,11 @@ def _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, qualit
         c2 = cols[1]
         s1, s2 = c1.record_sizes(), c2.record_sizes()
 
+        def ids_of(idx):
+            return c1.ids_of_pe(c2, idx)
+
         def arrays(idx):
-            ids, id_off = c1.ids_of_pe(c2, idx) if id_mode != "none" else (None, None)
+            ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
             if resident:
                 blk = c1.block_pe_dev(c2, idx)
                 return blk, blk.off, ids, id_off, None
@@ -246,8 +328,11 @@ def _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, qualit
     else:
         sizes = c1.record_sizes()
 
+        def ids_of(idx):
+            return c1.ids_of(idx)
+
         def arrays(idx):
-            ids, id_off = c1.ids_of(idx) if id_mode != "none" else (None, None)
+            ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
             if resident:
                 blk = c1.block_dev(idx)
                 return blk, blk.off, ids, id_off, None
@@ -259,7 +344,7 @@ def _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, qualit
             return sizes[idx]
 
         blocks = hp.form_blocks(c1, mode, groups=groups)
-    gen = encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids)
+    gen = encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids, ids_of=ids_of)
     return header, (_closing_columns(gen, cols, stats, profile) if resident else gen)
 
 

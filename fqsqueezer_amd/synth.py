@@ -276,3 +276,98 @@ def fastq_text(ids, seqs, quals, plus_id_every: int = 0, final_eol: bool = True)
 def synth_c25_text() -> bytes:
     """2000 ragged reads, every third separator line carries the id, the text ends without a line feed (tests/golden/c25_*)"""
     return fastq_text(*synth_ragged(2000, 50000, 25), plus_id_every=3, final_eol=False)
+
+
+# ---- c26: ids at the id kernel's staging limits and in the rare branches of the id coders (tests/golden/c26_*, tests/test_id_limits.py) ----
+C26_DELTAS = [1, -1, 2, -2, 123, -123, 124, -124, 0xFFFF, -0xFFFF, 0x10000, -0x10000, 0xFFFFFF, -0xFFFFFF, 0x1000000, -0x1000000,
+              0xFFFFFFFF, -0xFFFFFFFF, 0x100000000, -0x100000000]
+_C26_SEPS = b",;+()~\t"   # separators that are none of " :._/-|=#"
+
+
+def synth_ids_delta_walk(tag: bytes) -> list:
+    """One numeric field that walks through every delta of C26_DELTAS -- both edges of every size class of the id coder's numeric
+    deltas -- then from its value to 0, up to 9999999999 and back to 0 (the largest deltas ten digits allow), beside a field
+    that counts up by one.  The values stay within ten digits and are never negative."""
+    v, out = 5_000_000_000, []
+    for k, d in enumerate([0] + C26_DELTAS + [None, 9_999_999_999, -9_999_999_999, 7]):
+        v = 0 if d is None else v + d
+        assert 0 <= v <= 9_999_999_999
+        out.append(b"@%s.%d %d" % (tag, v, k + 1))
+    return out
+
+
+def synth_ids_at_limits() -> dict:
+    """The ids of c26 that sit on the id kernel's staging limits ("in": the last value the kernel takes) or one beyond ("over")."""
+    def many_tokens(n_sep, k):   # n_sep separators, so n_sep + 1 tokens with the line feed: literal and numeric tokens in turn
+        return b"@t" + b"".join(bytes([_C26_SEPS[i % len(_C26_SEPS)]]) + (b"%d" % (i + k) if i % 2 else b"k%c" % (97 + (i + k) % 26)) for i in range(n_sep))
+
+    def long_id(n, k):
+        body = bytes(97 + (i * 7 + i // 26 + k * (i % 5 == 0)) % 26 for i in range(n - 8))
+        return b"@long." + body + b".%d" % (k % 10)
+
+    ids = {"in": [long_id(1023, 0), long_id(1023, 1), long_id(1023, 1), long_id(1022, 2)] + [many_tokens(127, k) for k in (0, 1, 1, 40)]
+           + [b"@d.1234567890.12345678901", b"@d.1234567891.12345678902", b"@d.234567891.12345678902", b"@", b"@", b"@d.1.00000000002"],
+           "over": [long_id(1024, 3), many_tokens(128, 5), long_id(1100, 4)]}
+    assert [len(x) for x in ids["in"][:4]] == [1023, 1023, 1023, 1022] and [len(x) for x in ids["over"][::2]] == [1024, 1100]
+    return ids
+
+
+def synth_c26(name: str):
+    """(ids, reads) of a single-end c26 input, (ids 1, reads 1, ids 2, reads 2) of the paired one; the reads are 60 bp
+    (tools/make_golden.py --only c26 says how the reference coded each)."""
+    rng = np.random.Generator(np.random.PCG64(0xC26))
+    if name in ("ids_limits", "ids_over"):
+        base, lim = synth_ids_varied(400, 26), synth_ids_at_limits()
+        # (everything special twice: before the middle of the file and after it, so that with two workers each of them sees it)
+        ids = base[:60] + synth_ids_delta_walk(b"walk") + base[60:120] + lim["in"] + base[120:200]
+        ids += base[200:260] + lim["in"][::-1] + base[260:330] + synth_ids_delta_walk(b"w2")
+        if name == "ids_over":
+            ids += base[330:350] + lim["over"][:1] + base[350:360] + lim["over"][1:2] + base[360:380] + lim["over"][2:] + base[380:]
+        else:
+            ids += base[330:]
+        return ids, synth_reads(len(ids), 60, 20000, 26)
+    if name == "names":   # 3000 ids over 300 instrument names, one of them 62 bytes long, every seventh id on one of eight of the names
+        names = [b"@%s%d%s" % ((b"HWI-ST", b"M0", b"NB50", b"A00_x", b"K")[j % 5], 1000 + 37 * j, b"" if j % 4 else b"-r%d" % (j % 7)) for j in range(300)]
+        names[124] = b"@" + b"N62-" + bytes(65 + i % 26 for i in range(57))
+        assert len(names[124]) == 62 and len(set(names)) == 300
+        ids = []
+        for i in range(3000):
+            j = (i * 7919) % 300
+            j = j % 8 if i % 7 == 0 else j
+            ids.append(names[j] + (b".", b" ", b":")[i % 3] + b"%d %d/1" % (i + 1, i + 1))
+        return ids, synth_reads(3000, 60, 20000, 27)
+    if name == "names_over":   # 200 ids whose instrument names are 60 .. 64 bytes long
+        ids = []
+        for i in range(200):
+            n = 60 + (i * 3 + i // 40) % 5
+            nm = b"@" + (b"L%d-" % (i % 23)) + bytes(65 + (i % 23 + k) % 26 for k in range(64))
+            ids.append(nm[:n] + (b":", b".", b" ")[i % 3] + b"%d:%d" % (1 + i // 50, 1000 + 13 * i))
+        return ids, synth_reads(200, 60, 20000, 28)
+    if name == "pe_long":   # 600 pairs, ids of 70 .. 200 bytes
+        base = synth_ids_varied(600, 29)
+        ids1, ids2 = [], []
+        for i, x in enumerate(base):
+            want = int(rng.integers(70, 199))
+            x = x.replace(b" ", b"_") + b":"
+            x = (x + bytes(45 if k % 20 == 19 else b"ACGT"[int(c)] for k, c in enumerate(rng.integers(0, 4, size=200))))[:max(want, 68) - 2]
+            a, b = x + b"/1", x + b"/2"                       # i % 5 == 0: a typical pair
+            if i % 5 == 1:                                     # the mates differ in one byte somewhere in 64 .. na - 3
+                p = int(rng.integers(64, len(a) - 1))
+                b = b[:p] + (b"Q" if b[p:p + 1] != b"Q" else b"R") + b[p + 1:]
+            elif i % 5 == 2:                                   # ... at na - 3, the last byte idk_typical_pe compares
+                b = x + b"_2"
+            elif i % 5 == 3:                                   # the same id twice
+                b = a
+            elif i % 5 == 4:                                   # lengths that differ by one
+                b = x + b"x/2"
+            ids1.append(a)
+            ids2.append(b)
+        assert all(70 <= len(y) <= 200 for y in ids1 + ids2)
+        return ids1, synth_reads(600, 60, 20000, 29), ids2, synth_reads(600, 60, 20000, 30)
+    raise ValueError(name)
+
+
+# name -> (fixture tag, paired, -om, -im, threads, every id within the id kernel's limits)
+C26 = {"ids_limits": ("c26_ids_limits_o_t2", False, "o", "o", 2, True), "ids_over": ("c26_ids_over_o_t2", False, "o", "o", 2, False),
+       "names": ("c26_names_s_i_t3", False, "s", "i", 3, True), "names_over": ("c26_names_over_o_i_t2", False, "o", "i", 2, False),
+       "pe_long": ("c26_pe_long_o_o_t2", True, "o", "o", 2, True)}

@@ -271,8 +271,9 @@ void fqsx_id_destroy(fqsx_id *);
 /* The read-id stream on the GPU: same arguments and the same bytes as fqsx_id_encode_block, coded by one
  * wavefront per worker (csrc/fqsx_idk.h: tokeniser, numeric deltas, move-to-front list of instrument names, adaptive models in
  * per-worker tables in HBM; reference fqs/id.cpp:152-184, 257-495, 734-757).  Staging limits of the kernel: id lines of at most
- * 1024 bytes, 128 tokens, instrument names of 63 bytes, 4096 distinct instrument names per worker (beyond: an error, use the
- * host coder).  id_mode none has no stream. */
+ * 1024 bytes with the line feed, 128 tokens (every byte outside [0-9A-Za-z@] ends one, the line feed included), instrument names
+ * of 62 bytes, 4096 distinct instrument names per worker (beyond: FQSX_E_DEVICE with fqsx_idg_error_kind 5 or 6, use the host
+ * coder: it writes the same bytes, so a file can change over between two blocks).  id_mode none has no stream. */
 typedef struct fqsx_idg fqsx_idg;
 int fqsx_idg_create(const uint8_t *header17, int device, fqsx_idg **out);
 int fqsx_idg_encode_block(fqsx_idg *, const uint8_t *ids, const uint64_t *id_off, uint32_t n_reads, int paired,
@@ -289,7 +290,7 @@ void fqsx_idg_destroy(fqsx_idg *);
  * Errors: a worker with reads to decode and a stream shorter than 8 bytes: FQSX_E_ARG; a malformed or truncated stream (a
  * cumulative frequency at or above its model's total, a move-to-front code beyond the list, bytes wanted beyond the stream's
  * end): FQSX_E_DEVICE -- nothing outside a worker's own output is ever written and the call always returns.  GPU decoder only:
- * a line that would pass 1024 bytes, 128 tokens, an instrument name beyond 63 bytes or more than 4096 names per worker:
+ * a line that would pass 1024 bytes, 128 tokens, an instrument name beyond 62 bytes or more than 4096 names per worker:
  * FQSX_E_DEVICE ("staging sizes" in fqsx_last_error(); decode the file with fqsx_id_decode_block, which has no such limits).
  * The GPU decoder cannot size its model tables and its output from its input: it snapshots them before a block and, when one
  * runs out, restores the snapshot, doubles that capacity and runs the block again ("Reading a file back").
@@ -311,9 +312,10 @@ int fqsx_idg_stats(fqsx_idg *, uint64_t out[8]);
 /* out[4 * w + 0 / 1 / 2] = models in worker w's small table, in its big table, names in its move-to-front list after the last
  * block (an encoder and a decoder that have seen the same blocks agree on them) */
 int fqsx_idg_state(fqsx_idg *, uint32_t *out);
-/* What the kernel reported in the last fqsx_idg_decode_block: 0 nothing, 5 = a line over 1024 bytes, over 128 tokens or an
- * instrument name over 63 bytes, 6 = more than 4096 instrument names in a worker (5 and 6: the file is for fqsx_id_decode_block),
- * 7 = malformed or truncated stream, 3 / 4 = an output / model table that a valid stream could not have filled */
+/* What the kernel reported in the last fqsx_idg_encode_block / fqsx_idg_decode_block: 0 nothing, 5 = a line over 1024 bytes, over
+ * 128 tokens or an instrument name over 62 bytes, 6 = more than 4096 instrument names in a worker (5 and 6: the file is for
+ * fqsx_id_encode_block / fqsx_id_decode_block), 7 = malformed or truncated stream, 3 / 4 = an output / model table that a valid
+ * stream could not have filled; the encoder also: 1 = a byte >= 128, 2 = no instrument name */
 int fqsx_idg_error_kind(fqsx_idg *);
 /* Kernel timing of the id coder, as fqsx_qual_set_profiling / fqsx_qual_kernel_times: out[0] = milliseconds, out[1] = launches */
 int fqsx_idg_set_profiling(fqsx_idg *, int enable);

@@ -50,6 +50,11 @@ Fixtures (data only -- inputs are re-generated deterministically by fqsqueezer_a
                             (c10_full_o_t3.fqs) and c24_c4_ragged_o_t3.json (c4_ragged_o_t3.fqs: -im n -qm n)
   c25_plus_nolf_o_t3.fqs + .json, c25_plus_nolf_s_t2.json   `fqs e -qm o -im o` on synth_c25_text(): ragged reads, `+id` separator
                             lines on every third record, the last record without its line feed (--only c25)
+  c26_*.fqs + .json         ids at and beyond the id kernel's staging limits and in the id coders' rare branches (--only c26; inputs:
+                            synth.synth_c26, modes: synth.C26), all 60 bp, -gs 1, -qm n; the JSON as c24's: c26_ids_limits_o_t2 (-s -om o
+                            -im o, T=2), c26_ids_over_o_t2 (the same with three ids beyond the limits), c26_names_s_i_t3 (-s -om s -im i,
+                            T=3: 300 instrument names), c26_names_over_o_i_t2 (-om o -im i, T=2: names of 60..64 bytes),
+                            c26_pe_long_o_o_t2 (-p -om o -im o, T=2: mate ids of 70..200 bytes)
 Usage: python tools/make_golden.py [--work /tmp/w] [--only c1|c2|c3]
 """
 import argparse, hashlib, json, os, subprocess, sys
@@ -258,6 +263,8 @@ def main():
         c24(a)
     if a.only in ("", "c25"):
         c25(a)
+    if a.only in ("", "c26"):
+        c26(a)
     if a.only in ("", "c3"):
         fq = os.path.join(a.work, "c3.fq")
         if not os.path.exists(fq):
@@ -448,28 +455,34 @@ def c23(a):
                "decoded_quality_sha256": s1, "decoded_quality_sha256_mate2": s2}, open(os.path.join(GOLD, "c23_c5_pe_qo_t3.json"), "w"), indent=1)
 
 
+def fq_digest(path):
+    text = open(path, "rb").read()
+    lines = text.split(b"\n")[0::4]
+    lines = lines[:-1] if lines and lines[-1] == b"" else lines
+    return {"reads": len(lines), "fastq_sha256": hashlib.sha256(text).hexdigest(), "fastq_bytes": len(text),
+            "id_lines_sha256": hashlib.sha256(b"".join(x + b"\n" for x in lines)).hexdigest()}, lines
+
+
+def c24_decode(a, fqs, tag, paired, meta, keep_lines=False):
+    """tests/golden/<tag>.json: the digests of what `fqs d` writes for the file (per mate file: the text and its id lines)"""
+    d1, d2 = os.path.join(a.work, tag + "_d1.fq"), os.path.join(a.work, tag + "_d2.fq")
+    subprocess.check_call([REF, "d", "-out", d1] + (["-out2", d2] if paired else []) + [fqs], stdout=subprocess.DEVNULL)
+    m1, lines = fq_digest(d1)
+    d = dict(meta, fqs=os.path.basename(fqs), paired=paired, mate1=m1)
+    if paired:
+        d["mate2"] = fq_digest(d2)[0]
+    if keep_lines:
+        d["id_lines"] = [x.decode("latin-1") for x in lines]
+    json.dump(d, open(os.path.join(GOLD, tag + ".json"), "w"), indent=1)
+    return lines
+
+
 def c24(a):
     """Files for the id decoder and the FASTQ writer: what `fqs d` writes for each (the whole text and its id lines)."""
     from fqsqueezer_amd.synth import synth_ids_varied, synth_ids_zeros, synth_pairs, synth_quals
 
-    def fq_digest(path):
-        text = open(path, "rb").read()
-        lines = text.split(b"\n")[0::4]
-        lines = lines[:-1] if lines and lines[-1] == b"" else lines
-        return {"reads": len(lines), "fastq_sha256": hashlib.sha256(text).hexdigest(), "fastq_bytes": len(text),
-                "id_lines_sha256": hashlib.sha256(b"".join(x + b"\n" for x in lines)).hexdigest()}, lines
-
     def decode(fqs, tag, paired, meta, keep_lines=False):
-        d1, d2 = os.path.join(a.work, tag + "_d1.fq"), os.path.join(a.work, tag + "_d2.fq")
-        subprocess.check_call([REF, "d", "-out", d1] + (["-out2", d2] if paired else []) + [fqs], stdout=subprocess.DEVNULL)
-        m1, lines = fq_digest(d1)
-        d = dict(meta, fqs=os.path.basename(fqs), paired=paired, mate1=m1)
-        if paired:
-            d["mate2"] = fq_digest(d2)[0]
-        if keep_lines:
-            d["id_lines"] = [x.decode("latin-1") for x in lines]
-        json.dump(d, open(os.path.join(GOLD, tag + ".json"), "w"), indent=1)
-        return lines
+        return c24_decode(a, fqs, tag, paired, meta, keep_lines)
 
     def encode(out, inputs, paired, om, im, t):
         subprocess.check_call([REF, "e", "-p" if paired else "-s", "-om", om, "-t", str(t), "-gs", "1", "-qm", "n", "-im", im, "-v", "0",
@@ -522,6 +535,26 @@ def c25(a):
                 "om": om, "qm": "o", "im": "o", "threads": t}
         json.dump(fdigest(out, meta), open(os.path.join(GOLD, tag + ".json"), "w"))
         assert os.path.getsize(out) < 1 << 20
+
+
+def c26(a):
+    """Ids at the id kernel's staging limits, beyond them, and in the rare branches of the id coders (synth.synth_c26, synth.C26):
+    the reference's file for each input and the digests of what `fqs d` writes for it, as c24 has them.  All 60 bp, -gs 1, -qm n."""
+    from fqsqueezer_amd.synth import C26, synth_c26, synth_quals
+    for name, (tag, paired, om, im, t, inside) in C26.items():
+        got = synth_c26(name)
+        inputs = []
+        for m in range(2 if paired else 1):
+            ids, reads = got[2 * m], got[2 * m + 1]
+            inputs.append(os.path.join(a.work, "%s_%d.fq" % (tag, m + 1)))
+            write_fq_ids(inputs[-1], ids, reads, synth_quals(len(ids), 60, 26 + m))
+        out = os.path.join(GOLD, tag + ".fqs")
+        subprocess.check_call([REF, "e", "-p" if paired else "-s", "-om", om, "-t", str(t), "-gs", "1", "-qm", "n", "-im", im, "-v", "0",
+                               "-tmp", os.path.join(a.work, "tmp26_"), "-out", out] + inputs, stdout=subprocess.DEVNULL)
+        meta = {"input": "synth_c26(%r): %d %s x 60bp" % (name, len(got[0]), "pairs" if paired else "reads"), "om": om, "qm": "n", "im": im,
+                "threads": t, "within_kernel_limits": inside}
+        c24_decode(a, out, tag, paired, meta)
+        assert os.path.getsize(out) < 1 << 16, tag
 
 
 def c4_ref_decode(a, fq):
