@@ -24,6 +24,83 @@ class FqsxError(RuntimeError):
     pass
 
 
+_P, _INT, _U32, _U64, _HDR = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_char_p
+_OUT, _U64S, _MS, _IN = C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_char_p)
+_ID_ENCODE = [_P, _P, _P, _U32, _INT, _OUT, _U64S]
+_ID_DECODE = [_P, _IN, _P, _U32, _INT, _OUT, _OUT]
+
+# Every function of include/fqsx.h this module calls: name -> (restype, argtypes).  _OUT: a handle or a pointer the library
+# hands back; _IN with the _P behind it: T input streams and their lengths (_pack); _OUT, _U64S at the end of an encoder's
+# list: its T output streams (_Handle._collect).  (sharded.py binds the fqsx_shard_* / fqsx_rccl_* calls it makes itself.)
+_ABI = {
+    "fqsx_dna_create": (_INT, [_HDR, _INT, _OUT]),
+    "fqsx_dna_create_on_partition": (_INT, [_HDR, _INT, _U32, _U32, _OUT]),
+    "fqsx_dna_destroy": (None, [_P]),
+    "fqsx_dna_use_chunked_tables": (_INT, [_P]),
+    "fqsx_dna_encode_block": (_INT, [_P, _P, _P, _U32, _U32, _OUT, _U64S]),
+    "fqsx_dna_encode_block_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _OUT, _U64S]),
+    "fqsx_dna_decode_block": (_INT, [_P, _IN, _P, _P, _U32, _U32, _P]),
+    "fqsx_dna_decode_block_dev": (_INT, [_P, _IN, _P, _P, _U32, _U32, _OUT]),
+    "fqsx_dna_stats": (_INT, [_P, _U64S]),
+    "fqsx_dna_capacity": (_INT, [_P, _U64S]),
+    "fqsx_dna_set_profiling": (_INT, [_P, _INT]),
+    "fqsx_dna_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_qual_create": (_INT, [_HDR, _INT, _OUT]),
+    "fqsx_qual_destroy": (None, [_P]),
+    "fqsx_qual_encode_block": (_INT, [_P, _P, _P, _U32, _OUT, _U64S]),
+    "fqsx_qual_encode_block_dev": (_INT, [_P, _P, _P, _P, _U32, _OUT, _U64S]),
+    "fqsx_qual_decode_block": (_INT, [_P, _IN, _P, _P, _U32, _P]),
+    "fqsx_qual_decode_block_dev": (_INT, [_P, _IN, _P, _P, _U32, _OUT]),
+    "fqsx_qual_contexts": (_INT, [_P, _P]),
+    "fqsx_qual_set_profiling": (_INT, [_P, _INT]),
+    "fqsx_qual_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_meta_create": (_INT, [_U32, _OUT]),
+    "fqsx_meta_destroy": (None, [_P]),
+    "fqsx_meta_encode_block_pe": (_INT, [_P, _P, _U32, _INT, _OUT, _U64S]),
+    "fqsx_meta_decode_block": (_INT, [_P, _IN, _P, _U32, _INT, _P]),
+    "fqsx_id_create": (_INT, [_HDR, _OUT]),
+    "fqsx_id_destroy": (None, [_P]),
+    "fqsx_id_encode_block": (_INT, _ID_ENCODE),
+    "fqsx_id_decode_block": (_INT, _ID_DECODE),
+    "fqsx_idg_create": (_INT, [_HDR, _INT, _OUT]),
+    "fqsx_idg_destroy": (None, [_P]),
+    "fqsx_idg_encode_block": (_INT, _ID_ENCODE),
+    "fqsx_idg_decode_block": (_INT, _ID_DECODE),
+    "fqsx_idg_decode_block_dev": (_INT, [_P, _IN, _P, _U32, _INT, _OUT, _OUT, _U64S]),
+    "fqsx_idg_error_kind": (_INT, [_P]),
+    "fqsx_idg_stats": (_INT, [_P, _U64S]),
+    "fqsx_idg_state": (_INT, [_P, _P]),
+    "fqsx_idg_set_profiling": (_INT, [_P, _INT]),
+    "fqsx_idg_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_sort_order": (_INT, [_P, _P, _U32, _INT, _P, _P]),
+    "fqsx_sort_order_batched": (_INT, [_P, _P, _U32, _INT, _U64, _P, _P, C.POINTER(_U32)]),
+    "fqsx_fastq_create": (_INT, [_INT, _U64, _OUT]),
+    "fqsx_fastq_destroy": (None, [_P]),
+    "fqsx_fastq_max_chunk": (_U64, [_P]),
+    "fqsx_fastq_index": (_INT, [_P, _P, _U64, _U64S]),
+    "fqsx_fastq_columns": (_INT, [_P] * 8),
+    "fqsx_fastq_columns_into": (_INT, [_P] * 6),
+    "fqsx_fastq_set_profiling": (_INT, [_P, _INT]),
+    "fqsx_fastq_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_cols_create": (_INT, [_INT, _OUT]),
+    "fqsx_cols_destroy": (None, [_P]),
+    "fqsx_cols_info": (_INT, [_P, _U64S]),
+    "fqsx_cols_gather": (_INT, [_P, _P, _P, _U32, _P, _OUT, _OUT, _OUT]),
+    "fqsx_cols_bases": (_INT, [_P, _P]),
+    "fqsx_cols_download": (_INT, [_P, _P, _P, _U64]),
+    "fqsx_cols_set_profiling": (_INT, [_P, _INT]),
+    "fqsx_cols_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_fqtext_create": (_INT, [_INT, _OUT]),
+    "fqsx_fqtext_destroy": (None, [_P]),
+    "fqsx_fqtext_block": (_INT, [_P, _U32, _INT, _P, _P, _INT, _U64, _P, _P, _INT, _P, _U64S]),
+    "fqsx_fqtext_download": (_INT, [_P, _INT, _P]),
+    "fqsx_fqtext_set_profiling": (_INT, [_P, _INT]),
+    "fqsx_fqtext_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_last_error": (C.c_char_p, []),
+    "fqsx_version": (C.c_char_p, []),
+}
+
+
 def _load(path: str):
     if not os.path.exists(path):
         raise FqsxError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -33,68 +110,10 @@ def _load(path: str):
     except ImportError:
         pass
     lib = C.CDLL(path)
-    lib.fqsx_dna_create.restype = C.c_int
-    lib.fqsx_dna_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
-    if hasattr(lib, "fqsx_dna_create_on_partition"):   # (tools/ab_bench.py also loads builds that predate these entry points)
-        lib.fqsx_dna_create_on_partition.restype = C.c_int
-        lib.fqsx_dna_create_on_partition.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.fqsx_dna_destroy.argtypes = [C.c_void_p]
-    lib.fqsx_dna_encode_block.restype = C.c_int
-    lib.fqsx_dna_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                          C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    lib.fqsx_dna_encode_block_dev.restype = C.c_int
-    lib.fqsx_dna_encode_block_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                              C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    lib.fqsx_dna_decode_block.restype = C.c_int
-    lib.fqsx_dna_decode_block.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-    lib.fqsx_dna_stats.restype = C.c_int
-    lib.fqsx_dna_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    if hasattr(lib, "fqsx_dna_capacity"):
-        lib.fqsx_dna_capacity.restype = C.c_int
-        lib.fqsx_dna_capacity.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.fqsx_dna_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    lib.fqsx_dna_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.fqsx_qual_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
-    lib.fqsx_qual_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    lib.fqsx_qual_destroy.argtypes = [C.c_void_p]
-    if hasattr(lib, "fqsx_qual_decode_block"):   # (as above: builds that predate the decoders)
-        lib.fqsx_qual_decode_block.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        lib.fqsx_qual_decode_block_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
-        lib.fqsx_qual_contexts.argtypes = [C.c_void_p, C.c_void_p]
-        lib.fqsx_meta_decode_block.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
-    lib.fqsx_meta_create.argtypes = [C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.fqsx_meta_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    lib.fqsx_meta_destroy.argtypes = [C.c_void_p]
-    lib.fqsx_meta_encode_block_pe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    lib.fqsx_id_create.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-    lib.fqsx_id_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    lib.fqsx_id_destroy.argtypes = [C.c_void_p]
-    lib.fqsx_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-    if hasattr(lib, "fqsx_cols_create"):   # (as above: builds that predate the device-resident columns)
-        lib.fqsx_cols_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        lib.fqsx_cols_destroy.argtypes = [C.c_void_p]
-        lib.fqsx_cols_destroy.restype = None
-        lib.fqsx_cols_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        lib.fqsx_fastq_columns_into.argtypes = [C.c_void_p] * 6
-        lib.fqsx_cols_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
-        lib.fqsx_cols_bases.argtypes = [C.c_void_p, C.c_void_p]
-        lib.fqsx_cols_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
-        lib.fqsx_cols_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        lib.fqsx_cols_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    if hasattr(lib, "fqsx_fqtext_create"):   # (as above: builds that predate the text assembler)
-        lib.fqsx_dna_decode_block_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-        lib.fqsx_idg_decode_block_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p),
-                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        lib.fqsx_fqtext_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        lib.fqsx_fqtext_destroy.argtypes = [C.c_void_p]
-        lib.fqsx_fqtext_destroy.restype = None
-        lib.fqsx_fqtext_block.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
-                                          C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
-        lib.fqsx_fqtext_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        lib.fqsx_fqtext_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        lib.fqsx_fqtext_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.fqsx_last_error.restype = C.c_char_p
-    lib.fqsx_version.restype = C.c_char_p
+    for name, (restype, argtypes) in _ABI.items():
+        f = getattr(lib, name, None)   # (tools/ab_bench.py also loads builds that predate the newer entry points)
+        if f is not None:
+            f.restype, f.argtypes = restype, argtypes
     return lib
 
 
@@ -108,7 +127,61 @@ def load_library(path: Optional[str] = None):
     return _libs[path]
 
 
-class DnaCodec:
+def _error(lib, name: str, rc: int, text: Optional[str] = None, fmt: str = "{name}: {rc}: {text}") -> FqsxError:
+    """text: the library's (fqsx_last_error) unless the caller has its own; `.code` is the return code"""
+    e = FqsxError(fmt.format(name=name, rc=rc, text=lib.fqsx_last_error().decode() if text is None else text))
+    e.code = rc
+    return e
+
+
+def _pack(streams, T: int):
+    """T input streams as the decode entry points take them: (array of T pointers, their uint64 lengths)"""
+    return (C.c_char_p * T)(*[bytes(x) for x in streams]), np.array([len(x) for x in streams], dtype=np.uint64)
+
+
+class _Handle:
+    """An object of the library behind its opaque pointer: made by one fqsx_*_create, released once by its fqsx_*_destroy."""
+    _lib = _h = None
+
+    def _open(self, lib_path: Optional[str], create: str, destroy: str, *args, **error) -> None:
+        self._lib = load_library(lib_path)
+        self._h, self._destroy = C.c_void_p(), destroy
+        self._call(create, *args, C.byref(self._h), **error)
+
+    def _call(self, name: str, *args, text=None, fmt: str = "{name}: {rc}: {text}") -> None:
+        """text: None (the library's), the caller's own, or a function of the return code that gives it"""
+        rc = getattr(self._lib, name)(*args)
+        if rc:
+            raise self._error(name, rc, text(rc) if callable(text) else text, fmt)
+
+    def _error(self, name: str, rc: int, text: Optional[str], fmt: str) -> FqsxError:
+        return _error(self._lib, name, rc, text, fmt)
+
+    def _outputs(self, T: int) -> None:
+        """the T output streams of an encoder's block, owned by the library until the next call"""
+        self.T = T
+        self._streams = (C.c_void_p * T)()
+        self._lens = (C.c_uint64 * T)()
+
+    def _collect(self) -> List[bytes]:
+        return [C.string_at(self._streams[w], self._lens[w]) if self._lens[w] else b"" for w in range(self.T)]
+
+    def _stream_bytes(self) -> int:
+        return sum(self._lens[w] for w in range(self.T))
+
+    def close(self) -> None:
+        if self._h:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DnaCodec(_Handle):
     """One .fqs file's DNA-stream encoder state on one GPU (fqsx_dna_*)."""
 
     def __init__(self, header: bytes, device: int = 0, lib_path: Optional[str] = None, partition: Optional[tuple] = None,
@@ -117,77 +190,52 @@ class DnaCodec:
         chunked_tables: the capacity mode (fqsx_dna_use_chunked_tables): a growth never holds the old and the new table side by side."""
         if len(header) != 17:
             raise ValueError("header must be the 17 .fqs parameter bytes")
-        self._lib = load_library(lib_path)
-        self.T = header[4]
-        self._h = C.c_void_p()
         if partition is None:
-            rc = self._lib.fqsx_dna_create(bytes(header), device, C.byref(self._h))
+            self._open(lib_path, "fqsx_dna_create", "fqsx_dna_destroy", bytes(header), device)
         else:
-            rc = self._lib.fqsx_dna_create_on_partition(bytes(header), device, partition[0], partition[1], C.byref(self._h))
-        if rc:
-            raise FqsxError(f"fqsx_dna_create: {rc}: {self._lib.fqsx_last_error().decode()}")
+            self._open(lib_path, "fqsx_dna_create_on_partition", "fqsx_dna_destroy", bytes(header), device, partition[0], partition[1])
         if chunked_tables:
-            self._lib.fqsx_dna_use_chunked_tables.argtypes = [C.c_void_p]
-            if self._lib.fqsx_dna_use_chunked_tables(self._h):
-                raise FqsxError(f"fqsx_dna_use_chunked_tables: {self._lib.fqsx_last_error().decode()}")
-        self._streams = (C.c_void_p * self.T)()
-        self._lens = (C.c_uint64 * self.T)()
-
-    def _collect(self) -> List[bytes]:
-        return [C.string_at(self._streams[w], self._lens[w]) if self._lens[w] else b"" for w in range(self.T)]
+            self._call("fqsx_dna_use_chunked_tables", self._h, fmt="{name}: {text}")
+        self._outputs(header[4])
 
     def encode_block(self, bases: np.ndarray, read_off: np.ndarray, generation: int) -> List[bytes]:
         """Host-buffer entry point: returns the T per-worker DNA streams of the block."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        rc = self._lib.fqsx_dna_encode_block(self._h, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
-                                             generation, self._streams, self._lens)
-        if rc:
-            raise FqsxError(f"fqsx_dna_encode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_dna_encode_block", self._h, bases.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
+                   generation, self._streams, self._lens)
         return self._collect()
 
     def encode_block_dev(self, d_bases_ptr: int, d_off_ptr: int, read_off: np.ndarray, generation: int,
                          collect: bool = True):
         """Device-resident entry point (inputs already in HBM)."""
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        rc = self._lib.fqsx_dna_encode_block_dev(self._h, d_bases_ptr, d_off_ptr, read_off.ctypes.data,
-                                                 len(read_off) - 1, generation, self._streams, self._lens)
-        if rc:
-            raise FqsxError(f"fqsx_dna_encode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
-        if collect:
-            return self._collect()
-        return sum(self._lens[w] for w in range(self.T))
+        self._call("fqsx_dna_encode_block_dev", self._h, d_bases_ptr, d_off_ptr, read_off.ctypes.data,
+                   len(read_off) - 1, generation, self._streams, self._lens)
+        return self._collect() if collect else self._stream_bytes()
 
     def decode_block(self, streams, read_off: np.ndarray, generation: int) -> np.ndarray:
         """Inverse of encode_block: the T DNA streams of a block + read offsets -> concatenated base bytes."""
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
-        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        arr, lens = _pack(streams, self.T)
         out = np.zeros(max(1, int(read_off[-1])), dtype=np.uint8)
-        rc = self._lib.fqsx_dna_decode_block(self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
-                                             generation, out.ctypes.data)
-        if rc:
-            raise FqsxError(f"fqsx_dna_decode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_dna_decode_block", self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
+                   generation, out.ctypes.data)
         return out[:int(read_off[-1])]
 
     def decode_block_dev(self, streams, read_off: np.ndarray, generation: int) -> int:
         """The same, leaving the block in device memory: returns the device pointer (the codec's output buffer, valid until
         the next call on this codec)."""
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
-        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        arr, lens = _pack(streams, self.T)
         d_out = C.c_void_p()
-        rc = self._lib.fqsx_dna_decode_block_dev(self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
-                                                 generation, C.byref(d_out))
-        if rc:
-            raise FqsxError(f"fqsx_dna_decode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_dna_decode_block_dev", self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
+                   generation, C.byref(d_out))
         return d_out.value or 0
 
     def stats(self) -> dict:
         a = (C.c_uint64 * 64)()
-        rc = self._lib.fqsx_dna_stats(self._h, a)
-        if rc:
-            raise FqsxError(f"fqsx_dna_stats: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_dna_stats", self._h, a)
         d = dict(zip(STAT_NAMES, list(a)))
         d["timers"] = list(a)[16:64]
         return d
@@ -195,9 +243,7 @@ class DnaCodec:
     def capacity(self) -> dict:
         """Table occupancy and device memory (fqsx_dna_capacity)."""
         a = (C.c_uint64 * 16)()
-        rc = self._lib.fqsx_dna_capacity(self._h, a)
-        if rc:
-            raise FqsxError(f"fqsx_dna_capacity: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_dna_capacity", self._h, a)
         d = {"smers": a[0], "bmers": a[1], "smer_slots": a[2], "bmer_slots": a[3], "siv_bytes": a[4], "ctx_slots": a[5],
              "contexts": a[6], "device_bytes": a[7], "device_bytes_peak": a[8], "growths": a[9], "pairs": a[10], "pair_slots": a[11],
              "table_bytes_held": a[13], "pair_bytes_held": a[14], "siv_bytes_held": a[15]}
@@ -214,57 +260,28 @@ class DnaCodec:
         return {"encode_ms": a[0], "insert_ms": a[1], "other_ms": a[2],
                 "encode_launches": int(a[3]), "insert_launches": int(a[4]), "other_launches": int(a[5])}
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fqsx_dna_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class MetaCodec:
-    """Host-side read-length stream of the container (fqsx_meta_*)."""
+class MetaCodec(_Handle):
+    """Host-side read-length stream of the container (fqsx_meta_*).  (The host coders never set the library's error text.)"""
 
     def __init__(self, threads: int, lib_path: Optional[str] = None):
-        self._lib = load_library(lib_path)
-        self.T = threads
-        self._h = C.c_void_p()
-        if self._lib.fqsx_meta_create(threads, C.byref(self._h)):
-            raise FqsxError("fqsx_meta_create failed")
-        self._streams = (C.c_void_p * threads)()
-        self._lens = (C.c_uint64 * threads)()
+        self._open(lib_path, "fqsx_meta_create", "fqsx_meta_destroy", threads, fmt="{name} failed")
+        self._outputs(threads)
 
     def encode_block(self, read_len: np.ndarray, paired: bool = False) -> List[bytes]:
         read_len = np.ascontiguousarray(read_len, dtype=np.uint32)
-        if self._lib.fqsx_meta_encode_block_pe(self._h, read_len.ctypes.data, len(read_len), int(paired), self._streams, self._lens):
-            raise FqsxError("fqsx_meta_encode_block failed")
-        return [C.string_at(self._streams[w], self._lens[w]) for w in range(self.T)]
+        self._call("fqsx_meta_encode_block_pe", self._h, read_len.ctypes.data, len(read_len), int(paired), self._streams, self._lens,
+                   fmt="fqsx_meta_encode_block failed")
+        return self._collect()
 
     def decode_block(self, streams, n_reads: int, paired: bool = False) -> np.ndarray:
         """Inverse of encode_block: the T meta streams of a block -> its n_reads read lengths (an instance encodes or decodes a
         file, never both)."""
-        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
-        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        arr, lens = _pack(streams, self.T)
         out = np.zeros(max(1, n_reads), dtype=np.uint32)
-        rc = self._lib.fqsx_meta_decode_block(self._h, arr, lens.ctypes.data, n_reads, int(paired), out.ctypes.data)
-        if rc:
-            raise FqsxError(f"fqsx_meta_decode_block: {rc}: malformed or truncated meta stream")
+        self._call("fqsx_meta_decode_block", self._h, arr, lens.ctypes.data, n_reads, int(paired), out.ctypes.data,
+                   text="malformed or truncated meta stream")
         return out[:n_reads]
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fqsx_meta_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def sort_order(bases: np.ndarray, read_off: np.ndarray, device: int = 0, lib_path: Optional[str] = None,
@@ -279,102 +296,77 @@ def sort_order(bases: np.ndarray, read_off: np.ndarray, device: int = 0, lib_pat
     order = np.empty(max(n, 1), dtype=np.uint32)
     bins = np.zeros(257, dtype=np.uint32)
     nb = C.c_uint32(0)
-    lib.fqsx_sort_order_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     rc = lib.fqsx_sort_order_batched(bases.ctypes.data, read_off.ctypes.data, n, device, max_batch_bases, order.ctypes.data, bins.ctypes.data, C.byref(nb))
     if rc:
-        raise FqsxError(f"fqsx_sort_order: {rc}: {lib.fqsx_last_error().decode()}")
+        raise _error(lib, "fqsx_sort_order", rc)
     if stats is not None:
         stats["batches"] = nb.value
     return [order[bins[b]:bins[b + 1]].astype(np.int64) for b in range(256) if bins[b + 1] > bins[b]]
 
 
-class IdCodec:
+class IdCodec(_Handle):
     """Read-id stream of the container (header byte 7 = id mode).  device = None: the host coder (fqsx_id_*, one host thread per
     worker); device = ordinal: the GPU coder (fqsx_idg_*, one wavefront per worker) -- the same bytes.  Both flavours decode too."""
 
     def __init__(self, header: bytes, lib_path: Optional[str] = None, device: Optional[int] = None):
-        self._lib = load_library(lib_path)
-        self.T = header[4]
         self._mode = header[7]   # 0 lossless, 1 instrument
-        self._h = C.c_void_p()
         self._gpu = device is not None
-        L = self._lib
         if self._gpu:
-            L.fqsx_idg_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
-            L.fqsx_idg_encode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-            L.fqsx_idg_destroy.argtypes = [C.c_void_p]
-            L.fqsx_idg_destroy.restype = None
-            rc = L.fqsx_idg_create(bytes(header), device, C.byref(self._h))
-            if rc:
-                raise FqsxError(f"fqsx_idg_create: {rc}: {L.fqsx_last_error().decode()}")
-        elif L.fqsx_id_create(bytes(header), C.byref(self._h)):
-            raise FqsxError("fqsx_id_create failed")
-        self._streams = (C.c_void_p * self.T)()
-        self._lens = (C.c_uint64 * self.T)()
+            self._open(lib_path, "fqsx_idg_create", "fqsx_idg_destroy", bytes(header), device)
+        else:
+            self._open(lib_path, "fqsx_id_create", "fqsx_id_destroy", bytes(header), fmt="{name} failed")
+        self._outputs(header[4])
+
+    def _error(self, name: str, rc: int, text: Optional[str], fmt: str) -> FqsxError:
+        """A block's error has `staging`.  GPU flavour: True if the kernel met an id beyond its staging sizes or its list of
+        instrument names (fqsx_idg_error_kind 5 and 6); its models have moved by then, so the file goes on with the host
+        flavour (IdFallback)."""
+        e = super()._error(name, rc, text, fmt)
+        if "_block" in name:
+            e.staging = self._gpu and rc == -5 and self._lib.fqsx_idg_error_kind(self._h) in (5, 6)
+        return e
 
     def encode_block(self, ids: np.ndarray, id_off: np.ndarray, paired: bool = False) -> List[bytes]:
         ids = np.ascontiguousarray(ids, dtype=np.uint8)
         id_off = np.ascontiguousarray(id_off, dtype=np.uint64)
-        f = self._lib.fqsx_idg_encode_block if self._gpu else self._lib.fqsx_id_encode_block
-        rc = f(self._h, ids.ctypes.data, id_off.ctypes.data, len(id_off) - 1, int(paired), self._streams, self._lens)
-        if rc:
-            raise self._encode_error(rc, ids, id_off, paired)
-        return [C.string_at(self._streams[w], self._lens[w]) for w in range(self.T)]
+        self._call("fqsx_idg_encode_block" if self._gpu else "fqsx_id_encode_block", self._h, ids.ctypes.data, id_off.ctypes.data,
+                   len(id_off) - 1, int(paired), self._streams, self._lens,
+                   text=None if self._gpu else lambda rc: self._host_refusal(ids, id_off, paired))
+        return self._collect()
 
-    def _encode_error(self, rc: int, ids: np.ndarray, id_off: np.ndarray, paired: bool) -> FqsxError:
-        """GPU flavour: `staging` is True if the kernel met an id beyond its staging sizes or its list of instrument names (kinds
-        5 and 6); its models have moved by then, so the file goes on with the host flavour (fqsfile.encode_blocks).  The host
-        flavour never sets the library's error text: its one return code gets its message here."""
-        L = self._lib
-        e = FqsxError()
-        e.staging = False
-        if self._gpu:
-            L.fqsx_idg_error_kind.argtypes = [C.c_void_p]
-            e.staging = rc == -5 and L.fqsx_idg_error_kind(self._h) in (5, 6)
-            msg = L.fqsx_last_error().decode()
-        elif paired and (len(id_off) - 1) & 1:
-            msg = "a paired block with an odd number of reads"
-        else:   # (the two reasons for which the host coder refuses an id, fqsx_host.cpp id_lossless / id_instrument)
-            ends = np.zeros(len(ids) + 1, dtype=np.int64)
-            np.cumsum((ids == 0x2E) | (ids == 0x20) | (ids == 0x3A), out=ends[1:])
-            off = id_off.astype(np.int64)
-            if self._mode == 1 and bool((ends[off[1:]] == ends[off[:-1]]).any()):
-                msg = "no instrument name: an id line without '.', ' ' or ':'"
-            elif len(ids) and int(ids.max()) >= 128:
-                msg = "byte outside the 128-symbol alphabet in an id line"
-            else:
-                msg = "bad argument"
-        e.args = (f"fqsx_id{'g' if self._gpu else ''}_encode_block: {rc}: {msg}",)
-        return e
+    def _host_refusal(self, ids: np.ndarray, id_off: np.ndarray, paired: bool) -> str:
+        """The host flavour never sets the library's error text: its one return code gets its message here."""
+        if paired and (len(id_off) - 1) & 1:
+            return "a paired block with an odd number of reads"
+        # (the two reasons for which the host coder refuses an id, fqsx_host.cpp id_lossless / id_instrument)
+        ends = np.zeros(len(ids) + 1, dtype=np.int64)
+        np.cumsum((ids == 0x2E) | (ids == 0x20) | (ids == 0x3A), out=ends[1:])
+        off = id_off.astype(np.int64)
+        if self._mode == 1 and bool((ends[off[1:]] == ends[off[:-1]]).any()):
+            return "no instrument name: an id line without '.', ' ' or ':'"
+        if len(ids) and int(ids.max()) >= 128:
+            return "byte outside the 128-symbol alphabet in an id line"
+        return "bad argument"
+
+    @staticmethod
+    def _host_stream_error(rc: int) -> str:
+        return "a worker's stream is shorter than 8 bytes or a bad argument" if rc == -1 else "malformed or truncated id stream"
+
+    def _decode(self, name: str, streams, n_reads: int, paired: bool, *out) -> None:
+        arr, lens = _pack(streams, self.T)
+        self._call(name, self._h, arr, lens.ctypes.data, n_reads, int(paired), *[C.byref(x) for x in out],
+                   text=None if self._gpu else self._host_stream_error)
 
     def decode_block(self, streams, n_reads: int, paired: bool = False):
         """Inverse of encode_block: the T id streams of a block -> (ids uint8[], id_off uint64[n_reads + 1]), the id lines the
         reference's decoder writes, each with its line feed, in block order (an instance encodes or decodes a file, never both).
         GPU flavour: FqsxError whose `staging` is True if a line is beyond what the kernel stages (the host flavour has no limits)."""
-        L = self._lib
-        name = "fqsx_idg_decode_block" if self._gpu else "fqsx_id_decode_block"
-        f = getattr(L, name)
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
-        lens = np.array([len(x) for x in streams], dtype=np.uint64)
         ids, off = C.c_void_p(), C.c_void_p()
-        rc = f(self._h, arr, lens.ctypes.data, n_reads, int(paired), C.byref(ids), C.byref(off))
-        if rc:
-            raise self._decode_error(name, rc)
+        self._decode("fqsx_idg_decode_block" if self._gpu else "fqsx_id_decode_block", streams, n_reads, paired, ids, off)
         id_off = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(n_reads + 1,)).copy()
         n = int(id_off[-1])
         out = np.ctypeslib.as_array(C.cast(ids, C.POINTER(C.c_uint8)), shape=(max(n, 1),))[:n].copy()
         return out, id_off
-
-    def _decode_error(self, name: str, rc: int) -> FqsxError:
-        L = self._lib
-        msg = L.fqsx_last_error().decode() if self._gpu else ("a worker's stream is shorter than 8 bytes or a bad argument" if rc == -1 else "malformed or truncated id stream")
-        e = FqsxError(f"{name}: {rc}: {msg}")
-        e.staging = False
-        if self._gpu:   # what the kernel reported: 5 / 6 = beyond its staging sizes / its list of instrument names
-            L.fqsx_idg_error_kind.argtypes = [C.c_void_p]
-            e.staging = rc == -5 and L.fqsx_idg_error_kind(self._h) in (5, 6)
-        return e
 
     def decode_block_dev(self, streams, n_reads: int, paired: bool = False):
         """GPU flavour only: decode_block leaving the block in device memory.  Returns (d_ids, d_id_len, id_bytes): the device
@@ -382,171 +374,140 @@ class IdCodec:
         and the bytes of the lines.  Errors as decode_block's, `staging` included."""
         if not self._gpu:
             raise FqsxError("decode_block_dev: the host id decoder has no device output")
-        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
-        lens = np.array([len(x) for x in streams], dtype=np.uint64)
         ids, idl, nb = C.c_void_p(), C.c_void_p(), C.c_uint64()
-        rc = self._lib.fqsx_idg_decode_block_dev(self._h, arr, lens.ctypes.data, n_reads, int(paired), C.byref(ids), C.byref(idl), C.byref(nb))
-        if rc:
-            raise self._decode_error("fqsx_idg_decode_block_dev", rc)
+        self._decode("fqsx_idg_decode_block_dev", streams, n_reads, paired, ids, idl, nb)
         return ids.value or 0, idl.value or 0, int(nb.value)
 
     def error_kind(self) -> int:
         """GPU flavour: what the kernel reported in the last block (fqsx_idg_error_kind; 0 = nothing)"""
-        self._lib.fqsx_idg_error_kind.argtypes = [C.c_void_p]
         return int(self._lib.fqsx_idg_error_kind(self._h)) if self._gpu else 0
+
+    def _kernel_coder(self, name: str, *args) -> None:
+        if not self._gpu:
+            raise FqsxError(f"{name} failed")
+        self._call(name, self._h, *args, fmt="{name} failed")
 
     def stats(self) -> dict:
         """GPU flavour: how often the decoder had to grow (fqsx_idg_stats) and its capacities."""
         a = (C.c_uint64 * 8)()
-        self._lib.fqsx_idg_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        if not self._gpu or self._lib.fqsx_idg_stats(self._h, a):
-            raise FqsxError("fqsx_idg_stats failed")
+        self._kernel_coder("fqsx_idg_stats", a)
         return dict(zip(["retries", "grow_small", "grow_big", "grow_out", "small_slots", "big_slots", "out_bytes"], [int(x) for x in a]))
 
     def state(self) -> np.ndarray:
         """GPU flavour: (T, 3) models in the small table, in the big table and move-to-front names per worker after the last block."""
         a = np.zeros(4 * self.T, dtype=np.uint32)
-        self._lib.fqsx_idg_state.argtypes = [C.c_void_p, C.c_void_p]
-        if not self._gpu or self._lib.fqsx_idg_state(self._h, a.ctypes.data):
-            raise FqsxError("fqsx_idg_state failed")
+        self._kernel_coder("fqsx_idg_state", a.ctypes.data)
         return a.reshape(self.T, 4)[:, :3].copy()
 
     def set_profiling(self, on: bool) -> None:
-        self._lib.fqsx_idg_set_profiling.argtypes = [C.c_void_p, C.c_int]
         self._lib.fqsx_idg_set_profiling(self._h, int(on))
 
     def kernel_times(self) -> dict:
         a = (C.c_double * 2)()
-        self._lib.fqsx_idg_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self._lib.fqsx_idg_kernel_times(self._h, a)
         return {"ms": a[0], "launches": int(a[1])}
 
+
+class IdFallback:
+    """The id coder of one file: the GPU kernel, or -- once the kernel reports `staging` (IdCodec._error) -- the host coder,
+    brought to the same state by coding again, in order, the blocks the kernel has coded.  The blocks already done stay as they
+    are: both coders write and read the same bytes.  The user says what coding a block means: code(codec, what, held), where
+    `what` is all that is kept of a block to code it again and `held`, given on its first run only, what the caller has at hand
+    then.  fqsfile keeps a block's index array and cuts its id columns again; fqsread keeps its streams."""
+
+    def __init__(self, header: bytes, device: int, lib_path: Optional[str], gpu_ids: bool, code):
+        self._header, self._lib_path, self._code = header, lib_path, code
+        self.codec = IdCodec(header, lib_path=lib_path, device=device if gpu_ids else None)   # the live one (stats())
+        self.on_gpu, self.fell_back = gpu_ids, False
+        self._seen = []   # `what` of the blocks coded on the GPU so far
+
+    def run(self, what, held=None):
+        if self.on_gpu:
+            try:
+                out = self._code(self.codec, what, held)
+                self._seen.append(what)
+                return out
+            except FqsxError as e:
+                if not getattr(e, "staging", False):
+                    raise
+            self.codec.close()
+            self.codec = IdCodec(self._header, lib_path=self._lib_path)
+            self.on_gpu, self.fell_back = False, True
+            for w in self._seen:
+                self._code(self.codec, w, None)
+            self._seen = []
+        return self._code(self.codec, what, held)
+
     def close(self) -> None:
-        if getattr(self, "_h", None):
-            (self._lib.fqsx_idg_destroy if self._gpu else self._lib.fqsx_id_destroy)(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.codec.close()
 
 
-class QualCodec:
+class QualCodec(_Handle):
     """Quality-stream coder on the GPU (fqsx_qual_*): one instance encodes or decodes a file, never both."""
 
     def __init__(self, header: bytes, device: int = 0, lib_path: Optional[str] = None):
-        self._lib = load_library(lib_path)
-        self.T = header[4]
-        self._h = C.c_void_p()
-        rc = self._lib.fqsx_qual_create(bytes(header), device, C.byref(self._h))
-        if rc:
-            raise FqsxError(f"fqsx_qual_create: {rc}: {self._lib.fqsx_last_error().decode()}")
-        self._streams = (C.c_void_p * self.T)()
-        self._lens = (C.c_uint64 * self.T)()
+        self._open(lib_path, "fqsx_qual_create", "fqsx_qual_destroy", bytes(header), device)
+        self._outputs(header[4])
 
     def encode_block(self, quals: np.ndarray, read_off: np.ndarray) -> List[bytes]:
         quals = np.ascontiguousarray(quals, dtype=np.uint8)
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        rc = self._lib.fqsx_qual_encode_block(self._h, quals.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
-                                              self._streams, self._lens)
-        if rc:
-            raise FqsxError(f"fqsx_qual_encode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
-        return [C.string_at(self._streams[w], self._lens[w]) if self._lens[w] else b"" for w in range(self.T)]
+        self._call("fqsx_qual_encode_block", self._h, quals.ctypes.data, read_off.ctypes.data, len(read_off) - 1,
+                   self._streams, self._lens)
+        return self._collect()
 
     def encode_block_dev(self, d_quals_ptr: int, d_off_ptr: int, read_off: np.ndarray, collect: bool = False):
         """Device-resident entry point; returns the total stream bytes of the block or -- collect -- its T streams."""
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        self._lib.fqsx_qual_encode_block_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        rc = self._lib.fqsx_qual_encode_block_dev(self._h, d_quals_ptr, d_off_ptr, read_off.ctypes.data, len(read_off) - 1, self._streams, self._lens)
-        if rc:
-            raise FqsxError(f"fqsx_qual_encode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
-        if collect:
-            return [C.string_at(self._streams[w], self._lens[w]) if self._lens[w] else b"" for w in range(self.T)]
-        return sum(self._lens[w] for w in range(self.T))
+        self._call("fqsx_qual_encode_block_dev", self._h, d_quals_ptr, d_off_ptr, read_off.ctypes.data, len(read_off) - 1,
+                   self._streams, self._lens)
+        return self._collect() if collect else self._stream_bytes()
 
     def decode_block(self, streams, read_off: np.ndarray) -> np.ndarray:
         """Inverse of encode_block: the T quality streams of a block + read offsets -> concatenated quality bytes (ASCII)."""
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
-        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        arr, lens = _pack(streams, self.T)
         out = np.zeros(max(1, int(read_off[-1])), dtype=np.uint8)
-        rc = self._lib.fqsx_qual_decode_block(self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1, out.ctypes.data)
-        if rc:
-            raise FqsxError(f"fqsx_qual_decode_block: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_qual_decode_block", self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1, out.ctypes.data)
         return out[:int(read_off[-1])]
 
     def decode_block_dev(self, streams, read_off: np.ndarray) -> int:
         """The same, leaving the block in device memory: returns the device pointer (valid until the next call)."""
         read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
-        arr = (C.c_char_p * self.T)(*[bytes(x) for x in streams])
-        lens = np.array([len(x) for x in streams], dtype=np.uint64)
+        arr, lens = _pack(streams, self.T)
         d_out = C.c_void_p()
-        rc = self._lib.fqsx_qual_decode_block_dev(self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1, C.byref(d_out))
-        if rc:
-            raise FqsxError(f"fqsx_qual_decode_block_dev: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_qual_decode_block_dev", self._h, arr, lens.ctypes.data, read_off.ctypes.data, len(read_off) - 1, C.byref(d_out))
         return d_out.value or 0
 
     def contexts(self) -> dict:
         """Contexts stored per worker and the slots per worker of the context table (fqsx_qual_contexts)."""
         a = np.zeros(self.T + 1, dtype=np.uint64)
-        rc = self._lib.fqsx_qual_contexts(self._h, a.ctypes.data)
-        if rc:
-            raise FqsxError(f"fqsx_qual_contexts: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_qual_contexts", self._h, a.ctypes.data)
         return {"per_worker": [int(x) for x in a[:self.T]], "slots_per_worker": int(a[self.T])}
 
     def set_profiling(self, on: bool) -> None:
-        self._lib.fqsx_qual_set_profiling.argtypes = [C.c_void_p, C.c_int]
         self._lib.fqsx_qual_set_profiling(self._h, int(on))
 
     def kernel_times(self) -> dict:
         a = (C.c_double * 2)()
-        self._lib.fqsx_qual_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self._lib.fqsx_qual_kernel_times(self._h, a)
         return {"encode_ms": a[0], "encode_launches": int(a[1])}   # (of a decoding instance: its decode launches)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fqsx_qual_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 FASTQ_PASSES = ["count", "scan_tiles", "index", "lengths", "scan_rtiles", "offsets", "gather"]
 
 
-class FastqParser:
+class FastqParser(_Handle):
     """FASTQ text to columns on the GPU (fqsx_fastq_*): one chunk of text per call."""
 
     def __init__(self, device: int = 0, lib_path: Optional[str] = None, max_chunk_bytes: int = 0):
-        L = self._lib = load_library(lib_path)
-        L.fqsx_fastq_create.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.fqsx_fastq_destroy.argtypes = [C.c_void_p]
-        L.fqsx_fastq_destroy.restype = None
-        L.fqsx_fastq_max_chunk.argtypes = [C.c_void_p]
-        L.fqsx_fastq_max_chunk.restype = C.c_uint64
-        L.fqsx_fastq_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-        L.fqsx_fastq_columns.argtypes = [C.c_void_p] + [C.c_void_p] * 7
-        L.fqsx_fastq_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        L.fqsx_fastq_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        self._h = C.c_void_p()
-        rc = L.fqsx_fastq_create(device, max_chunk_bytes, C.byref(self._h))
-        if rc:
-            raise FqsxError(f"fqsx_fastq_create: {rc}: {L.fqsx_last_error().decode()}")
-        self.max_chunk_bytes = int(L.fqsx_fastq_max_chunk(self._h))
+        self._open(lib_path, "fqsx_fastq_create", "fqsx_fastq_destroy", device, max_chunk_bytes)
+        self.max_chunk_bytes = int(self._lib.fqsx_fastq_max_chunk(self._h))
 
     def index(self, text: np.ndarray) -> dict:
         """Upload a chunk (uint8 array) and find its records: sizes for columns()."""
         a = (C.c_uint64 * 8)()
-        rc = self._lib.fqsx_fastq_index(self._h, text.ctypes.data if len(text) else None, len(text), a)
-        if rc:
-            raise FqsxError(f"fqsx_fastq_index: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_fastq_index", self._h, text.ctypes.data if len(text) else None, len(text), a)
         return {"records": int(a[0]), "consumed": int(a[1]), "id_bytes": int(a[2]), "bases": int(a[3]), "quals": int(a[4]),
                 "max_id_line": int(a[5]), "length_mismatch": bool(a[6]), "line_feeds": int(a[7])}
 
@@ -556,10 +517,8 @@ class FastqParser:
         ids, bases, quals = (np.empty(info[k], dtype=np.uint8) for k in ("id_bytes", "bases", "quals"))
         id_off, read_off, qual_off = (np.zeros(n + 1, dtype=np.uint64) for _ in range(3))
         plus_len = np.empty(n, dtype=np.uint32)
-        rc = self._lib.fqsx_fastq_columns(self._h, ids.ctypes.data, id_off.ctypes.data, bases.ctypes.data, read_off.ctypes.data,
-                                          quals.ctypes.data, qual_off.ctypes.data, plus_len.ctypes.data)
-        if rc:
-            raise FqsxError(f"fqsx_fastq_columns: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_fastq_columns", self._h, ids.ctypes.data, id_off.ctypes.data, bases.ctypes.data, read_off.ctypes.data,
+                   quals.ctypes.data, qual_off.ctypes.data, plus_len.ctypes.data)
         return ids, id_off, bases, read_off, quals, qual_off, plus_len
 
     def columns_into(self, info: dict, store: "DeviceColumns"):
@@ -569,9 +528,7 @@ class FastqParser:
         ids = np.empty(info["id_bytes"], dtype=np.uint8)
         id_off, read_off = (np.zeros(n + 1, dtype=np.uint64) for _ in range(2))
         plus_len = np.empty(n, dtype=np.uint32)
-        rc = self._lib.fqsx_fastq_columns_into(self._h, store._h, ids.ctypes.data, id_off.ctypes.data, read_off.ctypes.data, plus_len.ctypes.data)
-        if rc:
-            raise FqsxError(f"fqsx_fastq_columns_into: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_fastq_columns_into", self._h, store._h, ids.ctypes.data, id_off.ctypes.data, read_off.ctypes.data, plus_len.ctypes.data)
         return ids, id_off, read_off, plus_len
 
     def set_profiling(self, on: bool) -> None:
@@ -582,30 +539,15 @@ class FastqParser:
         self._lib.fqsx_fastq_kernel_times(self._h, a)
         return {name: {"ms": a[k], "launches": int(a[7 + k])} for k, name in enumerate(FASTQ_PASSES)}
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fqsx_fastq_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 FQTEXT_PASSES = ["sizes", "scan_tiles", "offsets", "scatter"]
 
 
-class FastqText:
+class FastqText(_Handle):
     """Columns to FASTQ text on the GPU (fqsx_fqtext_*): one container block per call, the text `fqs d` writes for it."""
 
     def __init__(self, device: int = 0, lib_path: Optional[str] = None):
-        L = self._lib = load_library(lib_path)
-        self._h = C.c_void_p()
-        rc = L.fqsx_fqtext_create(device, C.byref(self._h))
-        if rc:
-            raise FqsxError(f"fqsx_fqtext_create: {rc}: {L.fqsx_last_error().decode()}")
+        self._open(lib_path, "fqsx_fqtext_create", "fqsx_fqtext_destroy", device)
         self.text_bytes = (0, 0)
 
     def block(self, read_off: np.ndarray, d_bases: int, d_quals: Optional[int] = None, ids=None, id_len=None, id_bytes: Optional[int] = None,
@@ -629,21 +571,15 @@ class FastqText:
         else:
             p_ids, p_len, nb, on_device = int(ids), int(id_len), int(id_bytes), 1
         out = (C.c_uint64 * 2)()
-        rc = self._lib.fqsx_fqtext_block(self._h, n, int(paired), p_ids, p_len, on_device, nb, d_bases or None, d_quals or None,
-                                         int(qual_fill), read_off.ctypes.data, out)
-        if rc:
-            e = FqsxError(f"fqsx_fqtext_block: {rc}: {self._lib.fqsx_last_error().decode()}")
-            e.code = rc
-            raise e
+        self._call("fqsx_fqtext_block", self._h, n, int(paired), p_ids, p_len, on_device, nb, d_bases or None, d_quals or None,
+                   int(qual_fill), read_off.ctypes.data, out)
         self.text_bytes = (int(out[0]), int(out[1]))
         return self.text_bytes
 
     def download(self, mate: int = 0) -> np.ndarray:
         """Output `mate` of the block assembled last (uint8[])."""
         out = np.empty(self.text_bytes[mate], dtype=np.uint8)
-        rc = self._lib.fqsx_fqtext_download(self._h, mate, out.ctypes.data if len(out) else None)
-        if rc:
-            raise FqsxError(f"fqsx_fqtext_download: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_fqtext_download", self._h, mate, out.ctypes.data if len(out) else None)
         return out
 
     def set_profiling(self, on: bool) -> None:
@@ -653,17 +589,6 @@ class FastqText:
         a = (C.c_double * 8)()
         self._lib.fqsx_fqtext_kernel_times(self._h, a)
         return {name: {"ms": a[k], "launches": int(a[4 + k])} for k, name in enumerate(FQTEXT_PASSES)}
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fqsx_fqtext_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DeviceBlock:
@@ -675,7 +600,7 @@ class DeviceBlock:
         self.bases, self.quals, self.d_off, self.off = bases, quals, d_off, off
 
 
-class DeviceColumns:
+class DeviceColumns(_Handle):
     """The records of a FASTQ file with the base and the quality column resident in device memory (fqsx_cols_*), filled chunk by
     chunk by FastqParser.columns_into.  ids, id_off, read_off and plus_len are host arrays as in hostpipe.Columns, so that
     record_sizes(), ids_of / ids_of_pe and the block formation work as they do there; block_dev / block_pe_dev cut a block on
@@ -683,11 +608,7 @@ class DeviceColumns:
 
     def __init__(self, device: int = 0, lib_path: Optional[str] = None):
         from . import hostpipe as hp
-        self._lib = load_library(lib_path)
-        self._h = C.c_void_p()
-        rc = self._lib.fqsx_cols_create(device, C.byref(self._h))
-        if rc:
-            raise FqsxError(f"fqsx_cols_create: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._open(lib_path, "fqsx_cols_create", "fqsx_cols_destroy", device)
         self._set_host(hp.Columns.from_chunks([]))
 
     def _set_host(self, host) -> None:
@@ -714,8 +635,7 @@ class DeviceColumns:
 
     def info(self) -> dict:
         a = (C.c_uint64 * 4)()
-        if self._lib.fqsx_cols_info(self._h, a):
-            raise FqsxError(f"fqsx_cols_info: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_cols_info", self._h, a, fmt="{name}: {text}")
         return {"records": int(a[0]), "bases": int(a[1]), "device_bytes": int(a[2]), "device_bytes_peak": int(a[3])}
 
     def gather(self, idx, off: np.ndarray, mate2: Optional["DeviceColumns"] = None) -> DeviceBlock:
@@ -728,10 +648,8 @@ class DeviceColumns:
         if len(off) != len(idx) * (2 if mate2 is not None else 1) + 1:
             raise ValueError("a block of n reads has n + 1 offsets")
         out = [C.c_void_p() for _ in range(3)]
-        rc = self._lib.fqsx_cols_gather(self._h, mate2._h if mate2 is not None else None, idx.ctypes.data if len(idx) else None, len(idx),
-                                        off.ctypes.data, *[C.byref(p) for p in out])
-        if rc:
-            raise FqsxError(f"fqsx_cols_gather: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_cols_gather", self._h, mate2._h if mate2 is not None else None, idx.ctypes.data if len(idx) else None, len(idx),
+                   off.ctypes.data, *[C.byref(p) for p in out])
         return DeviceBlock(out[0].value, out[1].value, out[2].value, off)
 
     def block_dev(self, idx) -> DeviceBlock:
@@ -753,17 +671,13 @@ class DeviceColumns:
     def download(self, d_ptr: int, n_bytes: int) -> np.ndarray:
         """n_bytes of the store's device memory (a DeviceBlock's buffers) as a host array"""
         out = np.empty(n_bytes, dtype=np.uint8)
-        rc = self._lib.fqsx_cols_download(self._h, d_ptr, out.ctypes.data, n_bytes)
-        if rc:
-            raise FqsxError(f"fqsx_cols_download: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_cols_download", self._h, d_ptr, out.ctypes.data, n_bytes)
         return out
 
     def bases_to_host(self) -> np.ndarray:
         """the whole base column (the sort pre-pass bins on the host)"""
         out = np.empty(int(self.read_off[-1]), dtype=np.uint8)
-        rc = self._lib.fqsx_cols_bases(self._h, out.ctypes.data)
-        if rc:
-            raise FqsxError(f"fqsx_cols_bases: {rc}: {self._lib.fqsx_last_error().decode()}")
+        self._call("fqsx_cols_bases", self._h, out.ctypes.data)
         return out
 
     def set_profiling(self, on: bool) -> None:
@@ -773,17 +687,6 @@ class DeviceColumns:
         a = (C.c_double * 4)()
         self._lib.fqsx_cols_kernel_times(self._h, a)
         return {"gather_ms": a[0], "gather_launches": int(a[1]), "check_ms": a[2], "check_launches": int(a[3])}
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.fqsx_cols_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _chunk_source(src):

@@ -9,47 +9,17 @@ from typing import Optional
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DeviceBlock, DnaCodec, FqsxError, IdCodec, MetaCodec, QualCodec, parse_fastq, sort_order
+from .codec import DeviceBlock, DeviceColumns, DnaCodec, IdFallback, MetaCodec, QualCodec, parse_fastq, sort_order
 
 
-def _gpu_groups(rec: hp.Records, device: int, lib_path: Optional[str]):
-    """Sorted-mode read order from the GPU pre-pass (bins + per-bin order incl. the reference's order of equal reads)."""
-    bases, off = hp.block_arrays(rec, np.arange(len(rec), dtype=np.int64))
+def _gpu_groups(rec, device: int, lib_path: Optional[str]):
+    """Sorted-mode read order from the GPU pre-pass (bins + per-bin order incl. the reference's order of equal reads) on the base
+    column of rec: hostpipe.Records, hostpipe.Columns or codec.DeviceColumns (which brings the column to the host for it)."""
+    if isinstance(rec, hp.Records):
+        bases, off = rec.block(np.arange(len(rec), dtype=np.int64))
+    else:
+        bases, off = (rec.bases_to_host() if isinstance(rec, DeviceColumns) else rec.bases), rec.read_off
     return sort_order(bases, off, device=device, lib_path=lib_path)
-
-
-class _Ids:
-    """The id coder of one file: the GPU kernel, or -- once the kernel reports an id beyond its staging limits or its list of
-    instrument names (IdCodec.encode_block, `staging`) -- the host coder, brought to the same state by coding again the id
-    columns of the blocks written so far (of which only the index arrays are kept; ids_of(idx) cuts the columns again).  The
-    blocks already written stay as they are: both coders write the same bytes.  The encoder's twin of fqsread._Ids."""
-
-    def __init__(self, header: bytes, device: int, lib_path: Optional[str], gpu_ids: bool, paired: bool, ids_of):
-        self.header, self.lib_path, self.paired, self.ids_of = header, lib_path, paired, ids_of
-        self.enc = IdCodec(header, lib_path=lib_path, device=device if gpu_ids else None)
-        self.on_gpu = gpu_ids
-        self.seen = []   # the index arrays of the blocks coded on the GPU so far
-        self.fell_back = False
-
-    def encode(self, idx, ids, id_off):
-        if self.on_gpu:
-            try:
-                out = self.enc.encode_block(ids, id_off, self.paired)
-                self.seen.append(idx)
-                return out
-            except FqsxError as e:
-                if not getattr(e, "staging", False):
-                    raise
-            self.enc.close()
-            self.enc = IdCodec(self.header, lib_path=self.lib_path)
-            self.on_gpu, self.fell_back = False, True
-            for j in self.seen:
-                self.enc.encode_block(*self.ids_of(j), self.paired)
-            self.seen = []
-        return self.enc.encode_block(ids, id_off, self.paired)
-
-    def close(self):
-        self.enc.close()
 
 
 def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device: int, lib_path: Optional[str], stats: Optional[dict] = None,
@@ -59,7 +29,7 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
     and the id kernel on their own HIP streams (host threads inside the C ABI, which releases the GIL), the meta coder on a host
     thread meanwhile.  arrays(idx) may hand back the bases as a codec.DeviceBlock (a block cut on the device, its qualities with
     it): the DNA and quality coders then read it where it lies.  ids_of(idx): the id columns of a block alone (default: from
-    arrays), for the id coder's change-over to the host coder in mid-file (_Ids); stats then has "id_host_fallback" True."""
+    arrays), for the id coder's change-over to the host coder in mid-file (codec.IdFallback); stats then has "id_host_fallback" True."""
     from concurrent.futures import ThreadPoolExecutor
     threads = header[4]
     stored = hp.stored_streams(header)
@@ -67,7 +37,11 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
     meta = MetaCodec(threads, lib_path=lib_path)
     # (the id stream comes from the GPU coder too: fqsx_idg_*, one wavefront per worker on a stream of its own; gpu_ids = False:
     # the host coder, one host thread per worker -- the same bytes)
-    idc = _Ids(header, device, lib_path, gpu_ids, paired, ids_of or (lambda idx: arrays(idx)[2:4])) if hp.STREAM_ID in stored else None
+    # of a block coded on the kernel only the index array is kept: a change-over to the host coder in mid-file (codec.IdFallback)
+    # cuts its id columns again; a block's first run takes the columns arrays(idx) has cut already
+    ids_of = ids_of or (lambda idx: arrays(idx)[2:4])
+    idc = IdFallback(header, device, lib_path, gpu_ids, lambda enc, idx, held: enc.encode_block(*(held or ids_of(idx)), paired)) \
+        if hp.STREAM_ID in stored else None
     qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
     pool = ThreadPoolExecutor(max_workers=3)
     try:
@@ -83,7 +57,7 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
                 if qual is not None:
                     jobs[hp.STREAM_QUALITY] = pool.submit(qual.encode_block, quals, off)
             if idc is not None:
-                jobs[hp.STREAM_ID] = pool.submit(idc.encode, idx, ids, id_off)
+                jobs[hp.STREAM_ID] = pool.submit(idc.run, idx, (ids, id_off))
             st = {hp.STREAM_META: meta.encode_block(np.diff(off.astype(np.int64)).astype(np.uint32), paired)}
             for k, f in jobs.items():
                 st[k] = f.result()
@@ -111,11 +85,6 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
             idc.close()
         if qual is not None:
             qual.close()
-
-
-def _encode(header: bytes, blocks, arrays, sizes_of, paired: bool, device: int, lib_path: Optional[str], gpu_ids: bool = True,
-            stats: Optional[dict] = None, ids_of=None) -> bytes:
-    return hp.write_fqs(header, encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids, ids_of=ids_of))
 
 
 # What the id kernel stages of an id line in LDS, the one place on this side that states csrc/fqsx_idk.h's IDK_MAX_ID, IDK_MAX_TOK
@@ -168,6 +137,54 @@ def _ids_fit_the_kernel(id_mode: str, *recs) -> bool:
     return all(_id_lines_fit_the_kernel(*hp.id_arrays(rec, np.arange(len(rec))), id_mode) for rec in recs)
 
 
+def _compress(inputs, ids_fit, threads: int, order: str, genome_size_mbp: int, quality_mode: str, id_mode: str, quality_thr: int, device: int,
+              lib_path: Optional[str], as_blocks: bool, gpu_ids: Optional[bool], stats: Optional[dict], resident: bool = False,
+              profile: bool = False):
+    """The file of one input (`fqs e -s`) or of two mate inputs (`fqs e -p`), each a hostpipe.Records, a hostpipe.Columns or
+    -- resident -- a codec.DeviceColumns, which all cut a block's columns under the same names: block, ids_of, quals_of, with a
+    mate block_pe, ids_of_pe, quals_of_pe (DeviceColumns: block_dev / block_pe_dev, the block cut on the device with its
+    qualities).  ids_fit(): the caller's pre-scan of the id lines, asked if gpu_ids is None.  Returns the file's bytes or
+    -- as_blocks -- (header, generator of container blocks); resident columns are released behind the last block."""
+    paired, c1, mates = len(inputs) == 2, inputs[0], inputs[1:]
+    if gpu_ids is None:
+        gpu_ids = id_mode == "none" or ids_fit()
+    if stats is not None:
+        stats["gpu_ids"] = gpu_ids
+    mode = ("pe_" if paired else "se_") + ("sorted" if order == "s" else "original")
+    header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
+    groups = _gpu_groups(c1, device, lib_path) if order == "s" else None   # mates follow mate 1's order, io.h:541-550
+    if resident and profile:
+        c1.set_profiling(True)
+    sizes = [c.record_sizes() for c in inputs]
+
+    def cutter(name: str, dev: str = ""):
+        """mate 1's method `name` on one input, its _pe form with the mate on two"""
+        name += ("_pe" if paired else "") + dev
+        return lambda idx: getattr(c1, name)(*mates, idx)
+    block, ids_of, quals_of = cutter("block", "_dev" if resident else ""), cutter("ids_of"), cutter("quals_of")
+
+    def arrays(idx):
+        ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
+        if resident:
+            blk = block(idx)
+            return blk, blk.off, ids, id_off, None
+        bases, off = block(idx)
+        return bases, off, ids, id_off, quals_of(idx)[0] if quality_mode != "none" else None
+
+    def sizes_of(idx):
+        if not paired:
+            return sizes[0][idx]
+        z = np.empty(2 * len(idx), dtype=np.int64)
+        z[0::2], z[1::2] = sizes[0][idx], sizes[1][idx]
+        return z
+
+    blocks = hp.form_blocks_pe(c1, *mates, mode, groups=groups) if paired else hp.form_blocks(c1, mode, groups=groups)
+    gen = encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids, ids_of=ids_of)
+    if resident:
+        gen = _closing_columns(gen, inputs, stats, profile)
+    return (header, gen) if as_blocks else hp.write_fqs(header, gen)
+
+
 def compress_records(rec: hp.Records, threads: int, order: str = "s", genome_size_mbp: int = 3100, device: int = 0,
                      lib_path: Optional[str] = None, quality_mode: str = "none", id_mode: str = "none",
                      quality_thr: int = 20, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None):
@@ -177,61 +194,16 @@ def compress_records(rec: hp.Records, threads: int, order: str = "s", genome_siz
     lines), or -- None -- the kernel unless an id of the file is beyond its staging limits.  A file on the kernel that meets
     more instrument names than a worker's list holds goes on with the host coder from that block (the same bytes).  stats:
     "gpu_ids" (the choice made), "id_host_fallback" (changed over in mid-file) and what encode_blocks adds."""
-    if gpu_ids is None:
-        gpu_ids = id_mode == "none" or _ids_fit_the_kernel(id_mode, rec)
-    if stats is not None:
-        stats["gpu_ids"] = gpu_ids
-    mode = "se_sorted" if order == "s" else "se_original"
-    header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
-    sizes = rec.record_sizes()
-
-    def ids_of(idx):
-        return hp.id_arrays(rec, idx)
-
-    def arrays(idx):
-        bases, off = hp.block_arrays(rec, idx)
-        ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
-        quals = hp.qual_arrays(rec, idx)[0] if quality_mode != "none" else None
-        return bases, off, ids, id_off, quals
-
-    groups = _gpu_groups(rec, device, lib_path) if mode == "se_sorted" else None
-    if as_blocks:
-        return header, encode_blocks(header, hp.form_blocks(rec, mode, groups=groups), arrays, lambda idx: sizes[idx], False, device, lib_path, stats=stats,
-                                     gpu_ids=gpu_ids, ids_of=ids_of)
-    return _encode(header, hp.form_blocks(rec, mode, groups=groups), arrays, lambda idx: sizes[idx], False, device, lib_path, gpu_ids, stats, ids_of)
+    return _compress([rec], lambda: _ids_fit_the_kernel(id_mode, rec), threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr,
+                     device, lib_path, as_blocks, gpu_ids, stats)
 
 
 def compress_records_pe(rec1: hp.Records, rec2: hp.Records, threads: int, order: str = "s", genome_size_mbp: int = 3100,
                         device: int = 0, lib_path: Optional[str] = None, quality_mode: str = "none", id_mode: str = "none",
                         quality_thr: int = 20, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None):
     """`fqs e -p ...` on two mate files (records interleaved mate 1 / mate 2 inside a block).  gpu_ids: see compress_records."""
-    if gpu_ids is None:
-        gpu_ids = id_mode == "none" or _ids_fit_the_kernel(id_mode, rec1, rec2)
-    if stats is not None:
-        stats["gpu_ids"] = gpu_ids
-    mode = "pe_sorted" if order == "s" else "pe_original"
-    header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
-    s1, s2 = rec1.record_sizes(), rec2.record_sizes()
-
-    def ids_of(idx):
-        return hp.id_arrays_pe(rec1, rec2, idx)
-
-    def arrays(idx):
-        bases, off = hp.block_arrays_pe(rec1, rec2, idx)
-        ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
-        quals = hp.qual_arrays_pe(rec1, rec2, idx)[0] if quality_mode != "none" else None
-        return bases, off, ids, id_off, quals
-
-    def sizes_of(idx):
-        z = np.empty(2 * len(idx), dtype=np.int64)
-        z[0::2], z[1::2] = s1[idx], s2[idx]
-        return z
-
-    groups = _gpu_groups(rec1, device, lib_path) if mode == "pe_sorted" else None   # mates follow mate 1's order, io.h:541-550
-    if as_blocks:
-        return header, encode_blocks(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, stats=stats,
-                                     gpu_ids=gpu_ids, ids_of=ids_of)
-    return _encode(header, hp.form_blocks_pe(rec1, rec2, mode, groups=groups), arrays, sizes_of, True, device, lib_path, gpu_ids, stats, ids_of)
+    return _compress([rec1, rec2], lambda: _ids_fit_the_kernel(id_mode, rec1, rec2), threads, order, genome_size_mbp, quality_mode, id_mode,
+                     quality_thr, device, lib_path, as_blocks, gpu_ids, stats)
 
 
 def _id_columns_fit_the_kernel(cols: hp.Columns, max_id_line: int, id_mode: str) -> bool:
@@ -265,14 +237,18 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
             parse_stats.append(st)
             if st["length_mismatch"]:
                 raise ValueError("a record's quality line differs in length from its base line (input %d)" % len(parse_stats))
-        out = _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr, device, lib_path, gpu_ids,
-                                stats, resident, profile)
+        if paired and len(cols[0]) != len(cols[1]):
+            raise ValueError("the mate files hold different numbers of records: %d and %d" % (len(cols[0]), len(cols[1])))
+        if stats is not None:
+            stats["parse"] = parse_stats
+        return _compress(cols, lambda: all(_id_columns_fit_the_kernel(c, st["max_id_line"], id_mode) for c, st in zip(cols, parse_stats)),
+                         threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr, device, lib_path, as_blocks, gpu_ids, stats,
+                         resident, profile)
     except BaseException:
         if resident:
             for c in cols:
                 c.close()
         raise
-    return out if as_blocks else hp.write_fqs(*out)
 
 
 def _closing_columns(gen, cols, stats: Optional[dict], profile: bool):
@@ -284,68 +260,6 @@ def _closing_columns(gen, cols, stats: Optional[dict], profile: bool):
     finally:
         for c in cols:
             c.close()
-
-
-def _compress_columns(cols, parse_stats, threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr, device, lib_path, gpu_ids,
-                      stats, resident, profile):
-    """(header, generator of container blocks) from the parsed columns of compress_fastq's one or two inputs"""
-    paired = len(cols) == 2
-    if paired and len(cols[0]) != len(cols[1]):
-        raise ValueError("the mate files hold different numbers of records: %d and %d" % (len(cols[0]), len(cols[1])))
-    if gpu_ids is None:
-        gpu_ids = id_mode == "none" or all(_id_columns_fit_the_kernel(c, st["max_id_line"], id_mode) for c, st in zip(cols, parse_stats))
-    if stats is not None:
-        stats["parse"], stats["gpu_ids"] = parse_stats, gpu_ids
-    mode = ("pe_" if paired else "se_") + ("sorted" if order == "s" else "original")
-    header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
-    c1 = cols[0]
-    # mates follow mate 1's order
-    groups = sort_order(c1.bases_to_host() if resident else c1.bases, c1.read_off, device=device, lib_path=lib_path) if order == "s" else None
-    if resident and profile:
-        c1.set_profiling(True)
-    if paired:
-        c2 = cols[1]
-        s1, s2 = c1.record_sizes(), c2.record_sizes()
-
-        def ids_of(idx):
-            return c1.ids_of_pe(c2, idx)
-
-        def arrays(idx):
-            ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
-            if resident:
-                blk = c1.block_pe_dev(c2, idx)
-                return blk, blk.off, ids, id_off, None
-            bases, off = c1.block_pe(c2, idx)
-            quals = c1.quals_of_pe(c2, idx)[0] if quality_mode != "none" else None
-            return bases, off, ids, id_off, quals
-
-        def sizes_of(idx):
-            z = np.empty(2 * len(idx), dtype=np.int64)
-            z[0::2], z[1::2] = s1[idx], s2[idx]
-            return z
-
-        blocks = hp.form_blocks_pe(c1, c2, mode, groups=groups)
-    else:
-        sizes = c1.record_sizes()
-
-        def ids_of(idx):
-            return c1.ids_of(idx)
-
-        def arrays(idx):
-            ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
-            if resident:
-                blk = c1.block_dev(idx)
-                return blk, blk.off, ids, id_off, None
-            bases, off = c1.block(idx)
-            quals = c1.quals_of(idx)[0] if quality_mode != "none" else None
-            return bases, off, ids, id_off, quals
-
-        def sizes_of(idx):
-            return sizes[idx]
-
-        blocks = hp.form_blocks(c1, mode, groups=groups)
-    gen = encode_blocks(header, blocks, arrays, sizes_of, paired, device, lib_path, stats=stats, gpu_ids=gpu_ids, ids_of=ids_of)
-    return header, (_closing_columns(gen, cols, stats, profile) if resident else gen)
 
 
 _QM = {"o": "lossless", "8": "illumina_8", "4": "illumina_4", "2": "binary", "n": "none"}   # fqsqueezer.cpp:157-191

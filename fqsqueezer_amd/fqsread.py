@@ -10,80 +10,97 @@ by block (hostpipe.iter_fqs), the decoders leave their columns on the device, th
 from __future__ import annotations
 
 import os
-from typing import Iterator, List, Optional, Tuple, Union
+from contextlib import closing
+from typing import Iterator, Optional, Tuple, Union
 
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DnaCodec, FastqText, FqsxError, IdCodec, MetaCodec, QualCodec
+from .codec import DnaCodec, FastqText, IdFallback, MetaCodec, QualCodec
+
+
+def _qual_fill(header: bytes) -> int:
+    """quality_mode none: every quality is 33 + quality_thr (quality.cpp:177-183)"""
+    return 33 + header[8]
+
+
+def _decode_blocks(header: bytes, blocks, device: int, lib_path: Optional[str], with_ids: bool, dev: bool, gpu_ids: bool = True,
+                   stats: Optional[dict] = None):
+    """The one per-block decode loop: a generator over the container blocks `blocks` (hostpipe.FqsBlock, in file order) of the
+    file with this header, each item (read_len uint32[n], off uint64[n + 1], bases, quals, ids).  Per block the id decoder
+    starts on its own HIP stream, the meta stream gives the read offsets on the calling thread, then the DNA kernels and the
+    quality kernel decode side by side on their own HIP streams, as fqsfile.encode_blocks runs the encoders.
+    dev False: bases and quals are uint8 arrays, the reads back to back (quality_mode none: the constant fill), and ids is
+    (ids uint8[], id_off uint64[n + 1]) (id_mode none: every id line is '@', id.cpp:486-492).
+    dev True: the columns stay in device memory for codec.FastqText.block -- bases and quals are device pointers (quals None:
+    the assembler fills in _qual_fill) and ids is (d_ids, d_id_len, id_bytes), or the same as host arrays once the host id
+    decoder has taken over (codec.IdFallback), or (None, None, None): the assembler's constant id line.  The pointers are the
+    decoders' own buffers, valid until this generator is resumed.
+    with_ids False: no id decoder is opened and ids is None.  stats: receives 'id_host_fallback' and the id decoder's growth
+    counters when the generator ends or is closed."""
+    from concurrent.futures import ThreadPoolExecutor
+    threads, paired = header[4], header[5] >= 2
+    stored = hp.stored_streams(header)
+
+    def decode_ids(dec, block, _):
+        if dev and idd.on_gpu:   # (what the assembler takes: device pointers from the id kernel, host arrays with their lengths from the host decoder)
+            return dec.decode_block_dev(*block, paired)
+        ids, id_off = dec.decode_block(*block, paired)
+        return (ids, np.diff(id_off).astype(np.uint32), len(ids)) if dev else (ids, id_off)
+
+    opened = []   # every codec opened so far: closed again also if a later constructor raises
+
+    def opening(codec):
+        opened.append(codec)
+        return codec
+    idd = None
+    pool = ThreadPoolExecutor(max_workers=3)
+    try:
+        dna = opening(DnaCodec(header, device=device, lib_path=lib_path))
+        meta = opening(MetaCodec(threads, lib_path=lib_path))
+        qual = opening(QualCodec(header, device=device, lib_path=lib_path)) if hp.STREAM_QUALITY in stored else None
+        if with_ids and hp.STREAM_ID in stored:
+            idd = opening(IdFallback(header, device, lib_path, gpu_ids, decode_ids))
+        for g, blk in enumerate(blocks):
+            st = lambda sid: [blk.streams[w][sid] for w in range(threads)]   # noqa: E731
+            n = blk.n_reads
+            ji = pool.submit(idd.run, (st(hp.STREAM_ID), n)) if idd is not None else None
+            read_len = meta.decode_block(st(hp.STREAM_META), n, paired)
+            off = np.zeros(n + 1, dtype=np.uint64)
+            off[1:] = np.cumsum(read_len, dtype=np.uint64)
+            jd = pool.submit(dna.decode_block_dev if dev else dna.decode_block, st(hp.STREAM_DNA), off, g)
+            if qual is not None:
+                quals = pool.submit(qual.decode_block_dev if dev else qual.decode_block, st(hp.STREAM_QUALITY), off).result()
+            else:
+                quals = None if dev else np.full(int(off[-1]), _qual_fill(header), dtype=np.uint8)
+            bases = jd.result()
+            if ji is not None:
+                ids = ji.result()
+            elif not with_ids:
+                ids = None
+            elif dev:
+                ids = (None, None, None)
+            else:
+                ids = (np.tile(np.frombuffer(b"@\n", dtype=np.uint8), n), np.arange(n + 1, dtype=np.uint64) * np.uint64(2))
+            yield read_len, off, bases, quals, ids
+    finally:
+        pool.shutdown(wait=True)
+        if stats is not None and idd is not None:   # (here, so that a caller that stops after the last block has them too)
+            stats["id_host_fallback"] = idd.fell_back
+            if idd.on_gpu:
+                stats["id_decoder"] = idd.codec.stats()
+        for c in opened:
+            c.close()
 
 
 def decompress_reads(data: bytes, device: int = 0, lib_path: Optional[str] = None) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
     """Generator over the container blocks of a .fqs file, in file order: (read_len uint32[n], bases uint8, quals uint8), the
-    reads of a block back to back (mates interleaved mate 1 / mate 2 in paired files).  Per block the meta stream gives the
-    read offsets, then the DNA kernels and the quality kernel decode side by side on their own HIP streams, as
-    fqsfile.encode_blocks runs the encoders.  quality_mode none: every quality is 33 + quality_thr (quality.cpp:177-183)."""
-    from concurrent.futures import ThreadPoolExecutor
+    reads of a block back to back (mates interleaved mate 1 / mate 2 in paired files), decoded by _decode_blocks.
+    quality_mode none: every quality is 33 + quality_thr (quality.cpp:177-183)."""
     header, blocks = hp.parse_fqs(data)
-    threads, paired = header[4], header[5] >= 2
-    stored = hp.stored_streams(header)
-    dna = DnaCodec(header, device=device, lib_path=lib_path)
-    meta = MetaCodec(threads, lib_path=lib_path)
-    qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
-    pool = ThreadPoolExecutor(max_workers=2)
-    try:
-        for g, blk in enumerate(blocks):
-            st = lambda sid: [blk.streams[w][sid] for w in range(threads)]   # noqa: E731
-            read_len = meta.decode_block(st(hp.STREAM_META), blk.n_reads, paired)
-            off = np.zeros(blk.n_reads + 1, dtype=np.uint64)
-            off[1:] = np.cumsum(read_len, dtype=np.uint64)
-            jd = pool.submit(dna.decode_block, st(hp.STREAM_DNA), off, g)
-            if qual is not None:
-                quals = pool.submit(qual.decode_block, st(hp.STREAM_QUALITY), off).result()
-            else:
-                quals = np.full(int(off[-1]), 33 + header[8], dtype=np.uint8)
-            yield read_len, jd.result(), quals
-    finally:
-        pool.shutdown(wait=True)
-        dna.close()
-        meta.close()
-        if qual is not None:
-            qual.close()
-
-
-class _Ids:
-    """The id decoder of one file: the GPU kernel, or -- once the kernel reports a line beyond its staging limits -- the host
-    decoder, brought to the same point by replaying the id streams of the blocks read so far."""
-
-    def __init__(self, header: bytes, device: int, lib_path: Optional[str], gpu_ids: bool = True):
-        self.header, self.lib_path, self.paired = header, lib_path, header[5] >= 2
-        self.dec = IdCodec(header, lib_path=lib_path, device=device if gpu_ids else None)
-        self.on_gpu = gpu_ids
-        self.seen: List[tuple] = []   # (streams, n_reads) of the blocks decoded on the GPU so far
-        self.fell_back = False
-
-    def decode(self, streams, n_reads: int, dev: bool = False):
-        """(ids, id_off) of the block; dev: (d_ids, d_id_len, id_bytes) in device memory while the kernel decodes the file and
-        (ids, id_len uint32[], id_bytes) as host arrays once the host decoder has taken over."""
-        if self.on_gpu:
-            try:
-                out = (self.dec.decode_block_dev if dev else self.dec.decode_block)(streams, n_reads, self.paired)
-                self.seen.append((streams, n_reads))
-                return out
-            except FqsxError as e:
-                if not getattr(e, "staging", False):
-                    raise
-            self.dec.close()
-            self.dec = IdCodec(self.header, lib_path=self.lib_path)
-            self.on_gpu, self.fell_back = False, True
-            for st, n in self.seen:
-                self.dec.decode_block(st, n, self.paired)
-            self.seen = []
-        ids, id_off = self.dec.decode_block(streams, n_reads, self.paired)
-        return (ids, np.diff(id_off).astype(np.uint32), len(ids)) if dev else (ids, id_off)
-
-    def close(self):
-        self.dec.close()
+    with closing(_decode_blocks(header, blocks, device, lib_path, with_ids=False, dev=False)) as decoded:
+        for read_len, _, bases, quals, _ in decoded:
+            yield read_len, bases, quals
 
 
 def decompress_records(data: bytes, device: int = 0, lib_path: Optional[str] = None, stats: Optional[dict] = None,
@@ -92,43 +109,10 @@ def decompress_records(data: bytes, device: int = 0, lib_path: Optional[str] = N
     id lines each with its line feed, as the reference's decoder writes them (numeric fields without leading zeros, instrument
     mode: the instrument name only).  The id decoder runs on its own HIP stream beside the DNA and the quality decoder.
     id_mode none: every id is '@' (id.cpp:486-492).  stats: receives 'id_host_fallback' and the id decoder's growth counters."""
-    from concurrent.futures import ThreadPoolExecutor
     header, blocks = hp.parse_fqs(data)
-    threads, paired = header[4], header[5] >= 2
-    stored = hp.stored_streams(header)
-    dna = DnaCodec(header, device=device, lib_path=lib_path)
-    meta = MetaCodec(threads, lib_path=lib_path)
-    qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
-    idd = _Ids(header, device, lib_path, gpu_ids) if hp.STREAM_ID in stored else None
-    pool = ThreadPoolExecutor(max_workers=3)
-    try:
-        for g, blk in enumerate(blocks):
-            st = lambda sid: [blk.streams[w][sid] for w in range(threads)]   # noqa: E731
-            ji = pool.submit(idd.decode, st(hp.STREAM_ID), blk.n_reads) if idd is not None else None
-            read_len = meta.decode_block(st(hp.STREAM_META), blk.n_reads, paired)
-            off = np.zeros(blk.n_reads + 1, dtype=np.uint64)
-            off[1:] = np.cumsum(read_len, dtype=np.uint64)
-            jd = pool.submit(dna.decode_block, st(hp.STREAM_DNA), off, g)
-            jq = pool.submit(qual.decode_block, st(hp.STREAM_QUALITY), off) if qual is not None else None
-            quals = jq.result() if jq is not None else np.full(int(off[-1]), 33 + header[8], dtype=np.uint8)
-            if ji is not None:
-                ids, id_off = ji.result()
-            else:
-                ids = np.tile(np.frombuffer(b"@\n", dtype=np.uint8), blk.n_reads)
-                id_off = np.arange(blk.n_reads + 1, dtype=np.uint64) * np.uint64(2)
-            yield read_len, jd.result(), quals, ids, id_off
-    finally:
-        pool.shutdown(wait=True)
-        if stats is not None and idd is not None:   # (here, so that a caller that stops after the last block has them too)
-            stats["id_host_fallback"] = idd.fell_back
-            if idd.on_gpu:
-                stats["id_decoder"] = idd.dec.stats()
-        dna.close()
-        meta.close()
-        if qual is not None:
-            qual.close()
-        if idd is not None:
-            idd.close()
+    with closing(_decode_blocks(header, blocks, device, lib_path, with_ids=True, dev=False, gpu_ids=gpu_ids, stats=stats)) as decoded:
+        for read_len, _, bases, quals, (ids, id_off) in decoded:
+            yield read_len, bases, quals, ids, id_off
 
 
 def _scatter(dst: np.ndarray, at: np.ndarray, src: np.ndarray, off: np.ndarray) -> None:
@@ -201,29 +185,24 @@ def decompress_fastq_chunks(src, device: int = 0, lib_path: Optional[str] = None
     the DNA, quality and id decoders run side by side and leave their columns in device memory, codec.FastqText assembles
     the text there, and its download runs on a worker thread while the next block decodes: a run holds one block of streams
     and two blocks of text.  quality_mode none: the assembler fills in 33 + quality_thr; id_mode none: its constant id line.
-    After a staging-limit fallback of the id decoder (_Ids) the ids reach the assembler as host arrays.  gpu_text=False: the
+    After a staging-limit fallback of the id decoder (codec.IdFallback) the ids reach the assembler as host arrays.  gpu_text=False: the
     same chunks through the decoders' host entry points and fastq_text / _take.  stats: as decompress_records, plus 'text':
     {'gpu_text', 'bytes': [mate 1, mate 2], 'blocks'} and -- stats['profile_text'] set by the caller -- 'kernels'."""
     import io
     from concurrent.futures import ThreadPoolExecutor
     own = isinstance(src, (bytes, bytearray, memoryview, str, os.PathLike))
     f = io.BytesIO(src) if isinstance(src, (bytes, bytearray, memoryview)) else open(src, "rb") if own else src
-    dna = meta = qual = idd = text = None
-    pool = ThreadPoolExecutor(max_workers=4)
+    decoded = text = None
+    loader = ThreadPoolExecutor(max_workers=1)   # downloads the text of the block assembled last
     written, n_blocks = [0, 0], 0
     try:
         blocks = hp.iter_fqs(f)
         header = next(blocks)
-        threads, paired = header[4], header[5] >= 2
-        stored = hp.stored_streams(header)
-        fill = 33 + header[8]
-        dna = DnaCodec(header, device=device, lib_path=lib_path)
-        meta = MetaCodec(threads, lib_path=lib_path)
-        qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
-        idd = _Ids(header, device, lib_path, gpu_ids) if hp.STREAM_ID in stored else None
+        paired = header[5] >= 2
         if gpu_text:
             text = FastqText(device=device, lib_path=lib_path)
             text.set_profiling(bool(stats and stats.get("profile_text")))
+        decoded = _decode_blocks(header, blocks, device, lib_path, with_ids=True, dev=bool(gpu_text), gpu_ids=gpu_ids, stats=stats)
 
         def download():
             return (text.download(0).tobytes(), text.download(1).tobytes()) if paired else text.download(0).tobytes()
@@ -236,50 +215,28 @@ def decompress_fastq_chunks(src, device: int = 0, lib_path: Optional[str] = None
             return chunk
 
         pending = None   # the download of the block assembled last
-        for g, blk in enumerate(blocks):
-            st = lambda sid: [blk.streams[w][sid] for w in range(threads)]   # noqa: E731
-            # (dev: what the assembler takes -- device pointers from the id kernel, host arrays with their lengths from the host decoder)
-            ji = pool.submit(idd.decode, st(hp.STREAM_ID), blk.n_reads, bool(gpu_text)) if idd is not None else None
-            read_len = meta.decode_block(st(hp.STREAM_META), blk.n_reads, paired)
-            off = np.zeros(blk.n_reads + 1, dtype=np.uint64)
-            off[1:] = np.cumsum(read_len, dtype=np.uint64)
+        for read_len, off, bases, quals, ids in decoded:
             if not gpu_text:
-                jd = pool.submit(dna.decode_block, st(hp.STREAM_DNA), off, g)
-                jq = pool.submit(qual.decode_block, st(hp.STREAM_QUALITY), off) if qual is not None else None
-                quals = jq.result() if jq is not None else np.full(int(off[-1]), fill, dtype=np.uint8)
-                if ji is not None:
-                    ids, id_off = ji.result()
-                else:
-                    ids = np.tile(np.frombuffer(b"@\n", dtype=np.uint8), blk.n_reads)
-                    id_off = np.arange(blk.n_reads + 1, dtype=np.uint64) * np.uint64(2)
-                yield count(_mates(*fastq_text(read_len, jd.result(), quals, ids, id_off), paired))
+                yield count(_mates(*fastq_text(read_len, bases, quals, *ids), paired))
                 continue
-            jd = pool.submit(dna.decode_block_dev, st(hp.STREAM_DNA), off, g)
-            jq = pool.submit(qual.decode_block_dev, st(hp.STREAM_QUALITY), off) if qual is not None else None
-            d_quals = jq.result() if jq is not None else None
-            d_bases = jd.result()
-            ids, id_len, id_bytes = ji.result() if ji is not None else (None, None, None)
             done = pending.result() if pending is not None else None   # (one call at a time on the assembler's handle)
-            text.block(off, d_bases, d_quals, ids=ids, id_len=id_len, id_bytes=id_bytes, paired=paired, qual_fill=fill)
-            pending = pool.submit(download)
+            text.block(off, bases, quals, ids=ids[0], id_len=ids[1], id_bytes=ids[2], paired=paired, qual_fill=_qual_fill(header))
+            pending = loader.submit(download)
             if done is not None:
                 yield count(done)
         if pending is not None:
             done, pending = pending.result(), None
             yield count(done)
     finally:
-        pool.shutdown(wait=True)
+        loader.shutdown(wait=True)
         if stats is not None:
             stats["text"] = {"gpu_text": bool(gpu_text), "bytes": list(written), "blocks": n_blocks}
             if text is not None and stats.get("profile_text"):
                 stats["text"]["kernels"] = text.kernel_times()
-            if idd is not None:
-                stats["id_host_fallback"] = idd.fell_back
-                if idd.on_gpu:
-                    stats["id_decoder"] = idd.dec.stats()
-        for c in (dna, meta, qual, idd, text):
-            if c is not None:
-                c.close()
+        if decoded is not None:
+            decoded.close()   # (fills in the id decoder's part of stats and closes the decoders)
+        if text is not None:
+            text.close()
         if own:
             f.close()
 

@@ -82,6 +82,25 @@ class Records:
         pl = len(self.plus) if self.plus_len is None else np.asarray(self.plus_len, dtype=np.int64)
         return idl + 1 + sl + 1 + pl + 1 + sl + 1
 
+    # the block cutters under the names Columns has them (block_arrays / id_arrays / qual_arrays and their _pe forms, below)
+    def block(self, idx):
+        return block_arrays(self, idx)
+
+    def ids_of(self, idx):
+        return id_arrays(self, idx)
+
+    def quals_of(self, idx):
+        return qual_arrays(self, idx)
+
+    def block_pe(self, mate2: "Records", idx):
+        return block_arrays_pe(self, mate2, idx)
+
+    def ids_of_pe(self, mate2: "Records", idx):
+        return id_arrays_pe(self, mate2, idx)
+
+    def quals_of_pe(self, mate2: "Records", idx):
+        return qual_arrays_pe(self, mate2, idx)
+
 
 def read_fastq(path: str) -> Records:
     with open(path, "rb") as f:

@@ -25,6 +25,33 @@ def test_exports_every_declared_symbol(libpath):
         assert hasattr(lib, name), f"{name} declared in include/fqsx.h but not exported"
 
 
+def test_codec_binds_every_function_it_calls_when_the_library_is_loaded(built):
+    """codec.py has one table of signatures, applied by load_library: every fqsx_* function the module calls -- as an
+    attribute of the library or by its name, given to a call helper -- is a key of it, every key is declared in
+    include/fqsx.h, and a loaded library (the emulation build) has each of them bound."""
+    import ast
+    from conftest import EMU_LIB
+    from fqsqueezer_amd import codec
+    tree = ast.parse(open(os.path.join(ROOT, "fqsqueezer_amd", "codec.py")).read())
+    table = next(n for n in tree.body if isinstance(n, ast.Assign) and any(isinstance(t, ast.Name) and t.id == "_ABI" for t in n.targets))
+    in_table = {id(n) for n in ast.walk(table)}
+    called = set()
+    for n in ast.walk(tree):
+        if id(n) in in_table:
+            continue
+        if isinstance(n, ast.Attribute) and n.attr.startswith("fqsx_"):
+            called.add(n.attr)
+        elif isinstance(n, ast.Constant) and isinstance(n.value, str) and re.fullmatch(r"fqsx_[a-z0-9_]+", n.value):
+            called.add(n.value)
+    assert {"fqsx_dna_encode_block", "fqsx_idg_decode_block_dev", "fqsx_fqtext_block", "fqsx_cols_gather", "fqsx_last_error"} <= called
+    assert called <= set(codec._ABI), sorted(called - set(codec._ABI))
+    declared = set(re.findall(r"\b(fqsx_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "fqsx.h")).read()))
+    assert set(codec._ABI) <= declared, sorted(set(codec._ABI) - declared)
+    lib = codec.load_library(EMU_LIB)
+    for name in codec._ABI:
+        assert getattr(lib, name).argtypes is not None, f"{name} is not bound by load_library"
+
+
 def test_contains_gfx950_code_object(libpath):
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-S", libpath], capture_output=True, text=True).stdout
     assert ".hip_fatbin" in out
