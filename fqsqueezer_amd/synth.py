@@ -371,3 +371,72 @@ def synth_c26(name: str):
 C26 = {"ids_limits": ("c26_ids_limits_o_t2", False, "o", "o", 2, True), "ids_over": ("c26_ids_over_o_t2", False, "o", "o", 2, False),
        "names": ("c26_names_s_i_t3", False, "s", "i", 3, True), "names_over": ("c26_names_over_o_i_t2", False, "o", "i", 2, False),
        "pe_long": ("c26_pe_long_o_o_t2", True, "o", "o", 2, True)}
+
+
+# ---- c27: the quality encoder at its edges (tests/golden/c27_*, tests/test_quality.py, tests/test_fqs_file.py) ----
+C27_WINDOW_LENS = [4031, 4032, 4033, 4095, 4096, 4097, 8063, 8064, 8065, 20, 63, 64, 65, 12100]
+
+
+def _geometric(rng, n: int, k_max: int = 45) -> np.ndarray:
+    """n draws of a geometric variable (p = 1/4, values 1 .. k_max + 1) from 32-bit integer draws: P(G > k) = (3/4)^k, the
+    thresholds floor(2^32 (1 - (3/4)^k)) in integer arithmetic, so the values depend on no library's logarithm"""
+    thr = np.array([(4 ** k - 3 ** k << 32) // 4 ** k for k in range(1, k_max + 1)], dtype=np.int64)
+    return 1 + np.searchsorted(thr, rng.integers(0, 1 << 32, size=n, dtype=np.int64), side="right")
+
+
+def _low_skewed_quals(rng, n: int) -> np.ndarray:
+    """qualities 33 + min(G + 1, 41): 2 .. 41, the low ones frequent"""
+    return (33 + np.minimum(_geometric(rng, n) + 1, 41)).astype(np.uint8)
+
+
+def _split(flat: np.ndarray, lens) -> list:
+    at = np.zeros(len(lens) + 1, dtype=np.int64)
+    at[1:] = np.cumsum(lens)
+    return [flat[at[i]:at[i + 1]].tobytes() for i in range(len(lens))]
+
+
+def synth_c27(name: str):
+    """(ids, seqs, quals), lists of bytes, of a c27 input (tools/make_golden.py --only c27 says how the reference coded each):
+    "halving": 40 000 reads x 30 bp, low-skewed qualities -- coded by one worker, position 0's model passes 2^15;
+    "windows": reads of C27_WINDOW_LENS x 3 -- both sides of the quality kernel's staging windows (4032 positions) and of its
+               64-symbol chunks;
+    "alphabet": 1200 reads of 20 .. 199 bp, quality symbols 0 .. 93 skewed to the top;
+    "tiny_1" / "tiny_2" (40 reads) and "one_1" / "one_2" (1 read) of 20 .. 119 bp with synth_ids_varied ids: mate files of
+               whole-file fixtures with far fewer reads than workers."""
+    seed = {"halving": 271, "windows": 272, "alphabet": 273, "tiny_1": 274, "tiny_2": 275, "one_1": 276, "one_2": 277}[name]
+    rng = np.random.Generator(np.random.PCG64(seed))
+    if name == "halving":
+        lens = [30] * 40000
+    elif name == "windows":
+        lens = C27_WINDOW_LENS * 3
+    elif name == "alphabet":
+        lens = rng.integers(20, 200, size=1200).tolist()
+    else:
+        lens = rng.integers(20, 120, size=40 if name.startswith("tiny") else 1).tolist()
+    total = int(sum(lens))
+    seqs = _split(_ACGT[rng.integers(0, 4, size=total, dtype=np.uint8)], lens)
+    if name == "alphabet":
+        u = rng.integers(0, 100, size=total)
+        sym = np.where(u < 15, rng.integers(0, 94, size=total), 93 - np.minimum(_geometric(rng, total) - 1, 93))
+        assert sym.min() == 0 and sym.max() == 93
+        quals = _split((33 + sym).astype(np.uint8), lens)
+    else:
+        quals = _split(_low_skewed_quals(rng, total), lens)
+    if name[:-2] in ("tiny", "one"):
+        ids = synth_ids_varied(len(lens), 27, int(name[-1]))   # (the mates of a pair share everything but the mate suffix)
+    else:
+        ids = [b"@c27.%d" % (i + 1) for i in range(len(lens))]
+    return ids, seqs, quals
+
+
+# quality-stream fixture -> (input, -qm, threads); all -s -om o -gs 1 -im n -qt 20
+C27 = {}
+for _qm in "o842":
+    C27["c27_halving_%s_t1" % _qm] = ("halving", _qm, 1)
+    C27["c27_alphabet_%s_t5" % _qm] = ("alphabet", _qm, 5)
+for _qm in "o82":
+    for _t in (1, 3):
+        C27["c27_windows_%s_t%d" % (_qm, _t)] = ("windows", _qm, _t)
+# whole-file fixture -> its inputs; all -om o -qm o -im o -gs 1 -t 64
+C27_FILES = {"c27_tiny_se_o_oo_t64": ("tiny_1",), "c27_tiny_pe_o_oo_t64": ("tiny_1", "tiny_2"),
+             "c27_one_se_o_oo_t64": ("one_1",), "c27_one_pe_o_oo_t64": ("one_1", "one_2")}

@@ -112,3 +112,35 @@ def test_gpu_sorted_order_of_1M_reads_is_the_reference_order():
     name = "c16_1M150_s_ids_t8.json"
     d = json.load(open(os.path.join(GOLD, name)))
     check_full_file_digest(compress_records(digest_records(d), d["threads"], "s", d["gs"], quality_mode="none", id_mode="lossless"), name)
+
+
+# ---- far fewer reads than workers: 40 reads / pairs and one read / pair at -t 64 (tools/make_golden.py c27) -------------------------
+def _check_tiny_file(tag, lib_path):
+    """compress_records* writes the reference's file byte for byte -- every stream of the 64 workers, most of which have no
+    read -- and fqsread decodes that file to the input text"""
+    from fqsqueezer_amd.fqsread import decompress_fastq
+    from fqsqueezer_amd.synth import C27_FILES, fastq_text, synth_c27
+    inputs = [synth_c27(n) for n in C27_FILES[tag]]
+    recs = [hp.Records(*x) for x in inputs]
+    want = open(os.path.join(GOLD, tag + ".fqs"), "rb").read()
+    header, blocks = hp.parse_fqs(want)
+    assert header[4] == 64 and sum(b.n_reads for b in blocks) == len(recs) * len(recs[0]) < 2 * 64
+    compress = compress_records_pe if len(recs) == 2 else compress_records
+    data = compress(*recs, 64, "o", 1, lib_path=lib_path, quality_mode="lossless", id_mode="lossless")
+    assert data == want
+    text = decompress_fastq(want, lib_path=lib_path)
+    assert (list(text) if len(recs) == 2 else [text]) == [fastq_text(*x) for x in inputs]
+
+
+TINY_FILES = ["c27_tiny_se_o_oo_t64", "c27_tiny_pe_o_oo_t64", "c27_one_se_o_oo_t64", "c27_one_pe_o_oo_t64"]
+
+
+@pytest.mark.parametrize("tag", TINY_FILES)
+def test_files_with_fewer_reads_than_workers_identical_to_reference(built, tag):
+    _check_tiny_file(tag, EMU_LIB)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", TINY_FILES)
+def test_gpu_files_with_fewer_reads_than_workers_identical_to_reference(tag):
+    _check_tiny_file(tag, None)

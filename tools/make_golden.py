@@ -55,6 +55,11 @@ Fixtures (data only -- inputs are re-generated deterministically by fqsqueezer_a
                             -im o, T=2), c26_ids_over_o_t2 (the same with three ids beyond the limits), c26_names_s_i_t3 (-s -om s -im i,
                             T=3: 300 instrument names), c26_names_over_o_i_t2 (-om o -im i, T=2: names of 60..64 bytes),
                             c26_pe_long_o_o_t2 (-p -om o -im o, T=2: mate ids of 70..200 bytes)
+  c27_*.json, c27_*.fqs     the quality encoder at its edges (--only c27; inputs: synth.synth_c27, modes: synth.C27 / C27_FILES).  JSON: per-block
+                            SHA-256 of the QUALITY streams as c8's, from `e -s -om o -gs 1 -im n -qt 20`: c27_halving_{o,8,4,2}_t1 (40 000 x 30 bp,
+                            T = 1: position 0's model passes 2^15 in every slot layout), c27_windows_{o,8,2}_t{1,3} (read lengths on both sides of
+                            the 4032-position staging windows and the 64-symbol chunks), c27_alphabet_{o,8,4,2}_t5 (symbols 0..93).  Files:
+                            c27_{tiny,one}_{se,pe}_o_oo_t64.fqs, 40 reads / pairs and one read / pair at -om o -qm o -im o -t 64 (most workers idle)
 Usage: python tools/make_golden.py [--work /tmp/w] [--only c1|c2|c3]
 """
 import argparse, hashlib, json, os, subprocess, sys
@@ -265,6 +270,8 @@ def main():
         c25(a)
     if a.only in ("", "c26"):
         c26(a)
+    if a.only in ("", "c27"):
+        c27(a)
     if a.only in ("", "c3"):
         fq = os.path.join(a.work, "c3.fq")
         if not os.path.exists(fq):
@@ -555,6 +562,44 @@ def c26(a):
                 "threads": t, "within_kernel_limits": inside}
         c24_decode(a, out, tag, paired, meta)
         assert os.path.getsize(out) < 1 << 16, tag
+
+
+def qdigest(path, meta):
+    """per-block SHA-256 and size of the quality streams (the format of c8_qual_*.json)"""
+    header, blocks = hp.parse_fqs(open(path, "rb").read())
+    d = dict(meta, header=header.hex(), n_blocks=len(blocks), blocks=[])
+    for b in blocks:
+        h = hashlib.sha256()
+        n = 0
+        for st in b.streams:
+            h.update(st[hp.STREAM_QUALITY])
+            n += len(st[hp.STREAM_QUALITY])
+        d["blocks"].append({"n_reads": b.n_reads, "sha256": h.hexdigest(), "bytes": n})
+    return d
+
+
+def c27(a):
+    """The quality encoder at its edges (synth.synth_c27): digests of the reference's quality streams per synth.C27, and the
+    reference's whole files for inputs with far fewer reads than workers per synth.C27_FILES."""
+    from fqsqueezer_amd.synth import C27, C27_FILES, fastq_text, synth_c27
+    fqs = {}
+
+    def fq_of(name):
+        if name not in fqs:
+            fqs[name] = os.path.join(a.work, "c27_%s.fq" % name)
+            open(fqs[name], "wb").write(fastq_text(*synth_c27(name)))
+        return fqs[name]
+
+    for tag, (name, qm, t) in C27.items():
+        out = os.path.join(a.work, tag + ".fqs")
+        subprocess.check_call([REF, "e", "-s", "-om", "o", "-t", str(t), "-gs", "1", "-qm", qm, "-qt", "20", "-im", "n", "-v", "0",
+                               "-tmp", os.path.join(a.work, "tmp27_"), "-out", out, fq_of(name)], stdout=subprocess.DEVNULL)
+        json.dump(qdigest(out, {"input": name, "qm": qm, "om": "o", "threads": t}), open(os.path.join(GOLD, tag + ".json"), "w"))
+    for tag, names in C27_FILES.items():
+        out = os.path.join(GOLD, tag + ".fqs")
+        subprocess.check_call([REF, "e", "-p" if len(names) == 2 else "-s", "-om", "o", "-t", "64", "-gs", "1", "-qm", "o", "-im", "o", "-v", "0",
+                               "-tmp", os.path.join(a.work, "tmp27_"), "-out", out] + [fq_of(n) for n in names], stdout=subprocess.DEVNULL)
+        assert os.path.getsize(out) < 1 << 14, tag
 
 
 def c4_ref_decode(a, fq):
