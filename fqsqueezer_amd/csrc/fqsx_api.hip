@@ -4,7 +4,7 @@
 // sizes the per-block buffers, and drives the kernel schedule of one reads block:
 //
 //   for seg in 0..S:  k_encode_segment  (T workgroups, one wavefront = one worker)
-//                     k_insert_phase    (3 T workgroups: (owner, mailbox kind); an inserting and a prefetching wave each)
+//                     k_insert_phase    (3 T workgroups: (owner, mailbox kind), eight waves each: the keys go in window by window)
 //                     clear local tables
 //   k_finish_block
 //
@@ -50,31 +50,29 @@ extern "C" const char *fqsx_version(void) {
 // queue -- the inserts of that phase included -- does nothing.  The host finds the word with the end-of-block transfer,
 // grows the tables and takes the block up again at that phase's inserts (block_recover).  err[0]: device error word.
 FQ_DEV bool phase_skip(const DevCfg &cfg) { return (cfg.err[0] | cfg.err[1]) != 0; }
-#define FQSX_INS_THREADS 128   /* k_insert_phase: the inserting wave and the prefetching wave */
-// grid = 3 * T: (owner, mailbox kind), plus -- single-end encoding -- workgroups that clear the workers' local tables
-// (ClearKmersToHT, dna.cpp:2475-2488: the insert phase does not touch them), which saves that launch
-// 128 threads: wave 0 inserts, wave 1 touches the buckets of the batches ahead (insert_prefetch_body)
-FQ_KERNEL128 void k_insert_phase(DevCfg cfg, u64 nb_slots, u64 ns_slots) {
-  FQ_SHARED InsShared sm;
-  if (phase_skip(cfg)) return;
+// grid = 3 * T: (owner, mailbox kind), FQSX_INS_THREADS threads each, plus -- single-end encoding -- workgroups that clear the
+// workers' local tables (ClearKmersToHT, dna.cpp:2475-2488: the insert phase does not touch them), which saves that launch
+// win: keys of a window of the s- / b-mer inserts (0: everything in order); maxmult: occurrences of one k-mer a window may hold
+FQ_KERNEL_NW(FQSX_INS_THREADS, FQSX_INS_WG_PER_CU * FQSX_INS_WAVES / 4) void k_insert_phase(DevCfg cfg, u64 nb_slots, u64 ns_slots, u32 win, u32 maxmult) {
+  FQ_SHARED InsWgShared sm;
 #ifndef FQSX_EMU
-  if (threadIdx.x == 0) { sm.pf_done = 0; sm.pf_on = blockDim.x > 64 ? 1u : 0u; }
+  // (another workgroup of this launch may post an error meanwhile: one thread looks, so that the waves of a workgroup agree)
+  if (FQ_TID == 0) sm.err = phase_skip(cfg) ? 1u : 0u;
   __syncthreads();
-  if (FQ_WAVE_ID == 1) {
-    if (FQ_BLOCK < 3 * cfg.T) insert_prefetch_body(cfg, &sm, FQ_BLOCK / 3, FQ_BLOCK % 3);
-    return;
-  }
+  const bool skip = sm.err != 0;
+  __syncthreads();
+  if (skip) return;
 #else
-  sm.pf_done = 0; sm.pf_on = 0;
+  if (phase_skip(cfg)) return;
 #endif
   if (FQ_BLOCK >= 3 * cfg.T) {
-    const u64 stride = (u64)(FQ_NBLOCKS - 3 * cfg.T) * FQ_WAVE, first = (u64)(FQ_BLOCK - 3 * cfg.T) * FQ_WAVE + FQ_LANE;
+    const u64 stride = (u64)(FQ_NBLOCKS - 3 * cfg.T) * FQ_NTHREADS, first = (u64)(FQ_BLOCK - 3 * cfg.T) * FQ_NTHREADS + FQ_TID;
     for (u64 i = first; i < nb_slots; i += stride) cfg.l_b.slots[i] = 0;
     for (u64 i = first; i < ns_slots; i += stride) cfg.l_s.slots[i] = 0;
     for (u64 i = first; i < 2ull * cfg.T; i += stride) cfg.l_s.filled[i] = 0;   // l_s.filled and l_b.filled are adjacent
     return;
   }
-  insert_phase_body(cfg, &sm, FQ_BLOCK / 3, FQ_BLOCK % 3);
+  insert_phase_body(cfg, &sm, FQ_BLOCK / 3, FQ_BLOCK % 3, win, maxmult);
   // partitioned tables: this owner's slots are read by other GPUs in the next launch -- out of this XCD's L2 into HBM
   // before the kernel ends (the phase's collective then orders the end of this kernel before anybody's next look-up)
   if (cfg.sys_scope) fq_release_system();
@@ -640,7 +638,8 @@ struct fqsx_dna : DevCtx {   // (a new fqsx_dna() starts with every field zero u
     bool live = false;
   } vm_s, vm_b, vm_pk, vm_pv, vm_siv; // s-mer and b-mer table; the pair table's key and value arrays; the p-mer vector (4096 chunks)
   u32 *d_plog_n;                      // counter of the p-mer transition log (DevCfg.p_log_n)
-  u32 ins_threads;                    // k_insert_phase: 128 = inserting wave + prefetching wave (FQSX_INS_PREFETCH=0: 64, the inserting wave alone)
+  u32 ins_win, ins_maxmult;           // k_insert_phase: keys per window of the s- / b-mer inserts (FQSX_INS_WINDOW; 0 = all in order, FQSX_INS_PARALLEL=0)
+                                      // and the occurrences of one k-mer a window may hold before it goes in order (FQSX_INS_MAXMULT)
   u64 vm_own_bytes;   // physical table memory held by this rank
 };
 
@@ -1158,8 +1157,9 @@ int clear_local_tables(fqsx_dna *c) {
 // insert phase and ClearKmersToHT in one launch (single-end encoding)
 int insert_and_clear(fqsx_dna *c) {
   const u64 words = (c->cur_need_lb + c->cur_need_ls) * c->T;
-  const u32 cgrid = (u32)std::min<u64>(2048, (words + 4095) / 4096 + 1);
-  LAUNCH(c, 1, k_insert_phase, 3 * c->T + cgrid, c->ins_threads, c->cfg, c->cur_need_lb * c->T, c->cur_need_ls * c->T);
+  const u64 per = 64ull * FQSX_INS_THREADS;   // words a clearing workgroup takes
+  const u32 cgrid = (u32)std::min<u64>(2048, (words + per - 1) / per + 1);
+  LAUNCH(c, 1, k_insert_phase, 3 * c->T + cgrid, FQSX_INS_THREADS, c->cfg, c->cur_need_lb * c->T, c->cur_need_ls * c->T, c->ins_win, c->ins_maxmult);
   return FQSX_OK;
 }
 // growth decision from the demand words (k_part_dstoff): a sub-table is at most half full after the coming inserts
@@ -1259,7 +1259,7 @@ int block_segment(fqsx_dna *c, u32 seg) {
       if (need * 2 > c->gpe_cap && (rc = grow_gpe(c, pow2_at_least(need * 2 + 2)))) return rc;
       if ((rc = pe_insert_and_clear(c))) return rc;
     }
-    LAUNCH(c, 1, k_insert_phase, 3 * T, c->ins_threads, cfg, (u64)0, (u64)0);
+    LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult);
     if ((rc = clear_local_tables(c))) return rc;
   }
   return FQSX_OK;
@@ -1354,7 +1354,13 @@ int create_impl(fqsx_dna *c, const u8 *h) {
   c->tab_small_pct = 40;
   if (const char *e = getenv("FQSX_TAB_AFTER_PCT")) c->tab_small_pct = c->tab_after_pct = (u32)std::min<u64>(c->tab_load_pct - 5, std::max<u64>(10, strtoull(e, nullptr, 10)));
   cfg.tab_load_pct = c->tab_load_pct;
-  c->ins_threads = (getenv("FQSX_INS_PREFETCH") && atoi(getenv("FQSX_INS_PREFETCH")) == 0) ? 64u : FQSX_INS_THREADS;
+  c->ins_win = FQSX_WIN_MAX; c->ins_maxmult = 16;
+  if (const char *e = getenv("FQSX_INS_WINDOW")) c->ins_win = (u32)std::min<u64>(FQSX_WIN_MAX, std::max<u64>(1, strtoull(e, nullptr, 10)));
+  if (const char *e = getenv("FQSX_INS_MAXMULT")) c->ins_maxmult = (u32)std::min<u64>(FQSX_WIN_MULT_MAX, std::max<u64>(1, strtoull(e, nullptr, 10)));
+  if (const char *e = getenv("FQSX_INS_PARALLEL")) if (atoi(e) == 0) c->ins_win = 0;
+#ifdef FQSX_EMU
+  c->ins_win = 0;   // (one lane: the in-order routine)
+#endif
   if (const char *e = getenv("FQSX_WHATIF")) { u32 r = 0, u = 0; if (sscanf(e, "%u,%u", &r, &u) == 2) cfg.whatif = (r << 16) | (u & 0xffffu); }
   c->gs_cap = c->gb_cap = pow2_at_least(std::max<u64>(1024, (1ull << 22) / T));
   if (const char *e = getenv("FQSX_GTAB_INIT")) c->gs_cap = c->gb_cap = pow2_at_least(std::max<u64>(64, strtoull(e, nullptr, 10)));   // (tests: growth from tiny tables)
@@ -1681,7 +1687,7 @@ int fqsx_shard_insert(fqsx_dna *c, uint64_t need_s, uint64_t need_b, uint64_t *c
   if (tab_over(c, need_s, c->gs_cap) && (rc = grow_global(c, cfg.g_s, c->gs_cap, tab_new_cap(c, need_s)))) return rc;
   if (tab_over(c, need_b, c->gb_cap) && (rc = grow_global(c, cfg.g_b, c->gb_cap, tab_new_cap(c, need_b)))) return rc;
   if ((rc = d2h_sync(c, c->siv_before, cfg.siv_stats, 2 * sizeof(u64)))) return rc;
-  LAUNCH(c, 1, k_insert_phase, 3 * T, c->ins_threads, cfg, (u64)0, (u64)0);
+  LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult);
   u64 after[2];
   if ((rc = d2h_sync(c, after, cfg.siv_stats, 2 * sizeof(u64)))) return rc;
   siv_delta[0] = after[0] - c->siv_before[0];
@@ -1840,7 +1846,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
     if (M[MAIL_P]) LAUNCH(c, 2, k_zero_words, (u32)std::min<u64>(REHASH_GRID, (M[MAIL_P] + 255) / 256), 256, cfg.p_log, M[MAIL_P], 0u);
     if ((rc = dzero(c, c->d_plog_n, sizeof(u32)))) return rc;
   }
-  LAUNCH(c, 1, k_insert_phase, 3 * T, c->ins_threads, cfg, (u64)0, (u64)0);
+  LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult);
   // ---- one all-gather
   for (u32 k = 0; k < 3; ++k)
     if (n_items[(u64)k * G + me] && !(k == MAIL_P && cfg.siv_part)) LAUNCH(c, 2, k_shard_collect, REHASH_GRID, 256, cfg, k, c->d_items + off_k[k]);

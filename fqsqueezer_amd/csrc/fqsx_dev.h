@@ -6,6 +6,7 @@
 #pragma once
 #include "fqsx_layout.h"
 #include "fqsx_rc.h"
+#include "fqsx_insplan.h"
 
 // ---------------------------------------------------------------------------------------
 // workgroup-shared (LDS) state of one worker
@@ -148,11 +149,10 @@ struct WgShared {
 #ifndef FQSX_EMU
 static_assert(sizeof(WgShared) <= 160u * 1024u, "WgShared must fit the 160 KB of LDS of a gfx950 CU");
 #endif
-// LDS of the insert-phase kernels (k_insert_phase, k_pe_insert): one RNG stream at a time and the batch scratch
+// LDS of the paired-end insert-phase kernels (k_pe_insert*): one RNG stream at a time and the batch scratch
 struct InsShared {
   u32 mt[4][624];
   u32 mt_idx[4];
-  u32 pf_done, pf_on;   // batches the inserting wave has applied / a prefetching wave runs beside it (k_insert_phase)
   u64 ib_pos[64];
   u64 ib_hash[256];
   u64 bk_key[64];
@@ -508,6 +508,20 @@ FQ_DEV void tab_load_bucket(const u64 *s, u32 bk, u64 it[FQSX_BKT]) {   // one 3
 // the per-slot work is kept to a dozen instructions: one masked 64-bit compare decides "same sibling group" for either
 // orientation, the matching slot's count is added into a packed accumulator (4 x 16 bits: a sibling is stored once and a count
 // has at most 12 bits), free slots need no test of their own (their count bits are zero).
+// The same bucket as it is NOW in L2 (agent-scope loads), never from a line this CU cached before another wave's claim went to
+// L2 as an atomic: the look-ups of the window-parallel insert phase (insert_windows)
+FQ_DEV void tab_load_bucket_live(const u64 *s, u32 bk, u64 it[FQSX_BKT]) {
+#ifndef FQSX_EMU
+#pragma unroll
+  for (u32 j = 0; j < FQSX_BKT; ++j) it[j] = __hip_atomic_load((u64 *)s + (u64)bk * FQSX_BKT + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  tab_load_bucket(s, bk, it);
+#endif
+}
+template <bool LIVE>
+FQ_DEV void tab_load_bucket_as(const u64 *s, u32 bk, u64 it[FQSX_BKT]) {
+  if constexpr (LIVE) tab_load_bucket_live(s, bk, it); else tab_load_bucket(s, bk, it);
+}
 struct TabQ { u64 mask, want; u32 sh, flip, cm; };
 FQ_DEV TabQ tab_query(const KTab &t, u64 kmer_norm, bool is_dir) {
   const u32 k2 = 2 * t.k;
@@ -628,18 +642,20 @@ FQ_DEV u64 tab_pick(const u64 it[FQSX_BKT], u32 j) {   // it[j] without dynamic 
 // (A function of its own, everything in and out BY VALUE: inlined at its dozen call sites the decode kernels took ten minutes to
 // compile, and the encode / insert kernels ran 2 % slower; a reference parameter of a real function is a scratch round trip.)
 struct TabLoc { u64 pos, item; u32 ns; };
-FQ_DEVN TabLoc tab_locate(const KTab t, const u64 *s, u64 v) {
+// (LIVE: every bucket through tab_load_bucket_live -- one body, so that the two probe orders cannot drift apart)
+template <bool LIVE>
+FQ_DEV TabLoc tab_locate_as(const KTab &t, const u64 *s, u64 v) {
   TabLoc R;
   R.pos = ~0ull; R.item = 0; R.ns = 0;
   u64 nsl = 0;
   const TabHome h = tab_home(t, v);
   u64 ia[FQSX_BKT];
-  tab_load_bucket(s, h.a, ia);
+  tab_load_bucket_as<LIVE>(s, h.a, ia);
   u32 fa, oa;
   bool chain = false;
   if (t.two) {
     u64 ib[FQSX_BKT];
-    tab_load_bucket(s, h.b, ib);
+    tab_load_bucket_as<LIVE>(s, h.b, ib);
     u32 fb, ob;
     tab_bucket_find(t, ia, v, fa, oa, nsl);
     tab_bucket_find(t, ib, v, fb, ob, nsl);
@@ -658,7 +674,7 @@ FQ_DEVN TabLoc tab_locate(const KTab t, const u64 *s, u64 v) {
     for (u64 n = 0; n <= t.nb; ++n) {
       p = t.two ? tab_next(t, h.a, p) : ((u64)p + 1 == t.nb ? 0u : p + 1u);
       u64 it[FQSX_BKT];
-      tab_load_bucket(s, p, it);
+      tab_load_bucket_as<LIVE>(s, p, it);
       u32 fj, oc;
       tab_bucket_find(t, it, v, fj, oc, nsl);
       if (fj != FQSX_BKT) { R.item = tab_pick(it, fj); R.pos = (u64)p * FQSX_BKT + fj; break; }
@@ -668,6 +684,8 @@ FQ_DEVN TabLoc tab_locate(const KTab t, const u64 *s, u64 v) {
   R.ns = (u32)nsl;
   return R;   // (pos == ~0: cannot happen, the tables are never full)
 }
+FQ_DEVN TabLoc tab_locate(const KTab t, const u64 *s, u64 v) { return tab_locate_as<false>(t, s, v); }
+FQ_DEVN TabLoc tab_locate_live(const KTab t, const u64 *s, u64 v) { return tab_locate_as<true>(t, s, v); }
 // the same for a one-sequence (local) table, inlined: the inserter wave of a worker runs it for every batch of local inserts, and
 // the wave that resolves the reads waits for that wave whenever a look-up could be changed by an insert still on its way
 FQ_DEV TabLoc tab_locate1(const KTab &t, const u64 *s, u64 v) {
@@ -790,23 +808,10 @@ FQ_DEV void insert_batch(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, cons
 template <class SM>
 FQ_DEV void insert_batch_k(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, u64 mykey, u32 n, u32 rng, const Cinc &ci,
                            u64 &nslots, u32 &err);
-// EXT_PF (the insert-phase kernel): a second wave of the workgroup touches the home buckets of the batches ahead (insert_prefetch_body),
-// so this wave sends for nothing itself -- a touch issued in front of a batch's probe walk holds that walk's loads back until the touch
-// (an HBM round trip) is home, because a wave's vector-memory operations retire in issue order -- and reports its progress instead.
-template <class SM, bool EXT_PF = false>
+template <class SM>
 FQ_DEV void insert_keys(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, const u64 *keys, u32 n, u32 rng, const Cinc &ci,
                         u64 &nslots, u32 &err) {
 #if FQ_WAVE > 1
-  if constexpr (EXT_PF) {
-    u64 nextk = FQ_LANE < n ? keys[FQ_LANE] : 0;
-    for (u32 o = 0; o < n && !err; o += FQ_WAVE) {
-      const u64 k = nextk;
-      if (o + FQ_WAVE + FQ_LANE < n) nextk = keys[o + FQ_WAVE + FQ_LANE];
-      insert_batch_k(cfg, sm, t, sub, k, n - o < FQ_WAVE ? n - o : FQ_WAVE, rng, ci, nslots, err);
-      lds_store_rel(&sm->pf_done, o / FQ_WAVE + 1);
-    }
-    return;
-  }
   // the keys of the next batch are fetched while the current one is applied (the list is read-only here)
   // ... and the home slots of the next batch are touched one batch ahead, so that the ordered walk of a batch finds
   // its cache lines (and address translations) in L2 instead of paying the HBM round trip inside the serial chain
@@ -4773,46 +4778,230 @@ FQ_DEV void siv_idx_move(const DevCfg &cfg, u64 idx, u32 from, u32 to) {
   e[to] += 1;
 #endif
 }
+// ---- insert phase ---------------------------------------------------------------------------
 // owner `tid` applies its group of mailbox `kind` (InsertKmersToHT, dna.cpp:2393-2472).  The three
 // mailboxes touch disjoint state (p-mer vector / ht_smer + cinc_s / ht_bmer + cinc_b), so they run as
-// three independent workgroups per owner.
-#ifndef FQSX_PF_AHEAD
-#define FQSX_PF_AHEAD 4
+// three independent workgroups per owner, FQSX_INS_WAVES waves each.
+//
+// s- and b-mers: the order of an owner's keys matters in two ways only -- the draws of the owner's MT19937 stream are
+// numbered in key order, and occurrences of one k-mer see each other's increments.  Where a new key is placed (which of
+// its two buckets, which slot) matters to no look-up: they all search both buckets and the chain.  So the group is
+// applied a WINDOW of keys at a time (insert_windows below), every key of the window on a thread of its own:
+//   locate   read-only: the key's slot and counter c0 before the window, or "absent"
+//   rank     r = earlier occurrences of the same k-mer in the window (LDS hash keyed by the k-mer, rounds of atomicMin
+//            over the key index: the winner of round q has rank q)
+//   decide   fqsx_insplan.h: whether an occurrence draws follows from (c0, r) alone, unless the counter may have reached
+//            its maximum inside the window -- then, or when a k-mer occurs more often than the cap on the rank rounds,
+//            nothing has been written yet and wave 0 applies the window with the in-order routine (insert_keys)
+//   draws    exclusive scan of the draw flags in key order = every occurrence's place in the stream; wave 0 produces
+//            that many numbers into LDS and leaves the generator where that many sequential draws leave it
+//   claim    the first occurrence of every absent key takes a slot (tab_find_or_claim, count 1)
+//   commit   rank round by rank round, a barrier between rounds: the occurrence applies insplan_adds to the counter it
+//            meets (rank 0: c0; later ranks reload it)
+// All waves reach every barrier: trip counts of loops with a barrier in them are read from LDS behind a barrier, nothing
+// waits for another wave in any other way, and every probe loop is bounded.
+#ifndef FQSX_INS_WAVES
+#define FQSX_INS_WAVES 8u
 #endif
-// The prefetching wave of an insert-phase workgroup: walks the owner's group a few batches ahead of the inserting wave and touches
-// every key's two home buckets, so that the inserting wave's ordered probe walks find them in L2.  It only reads.
-#if FQ_WAVE > 1
-template <class SM>
-FQ_DEV void insert_prefetch_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind) {
-  if (kind == MAIL_P) return;
-  const Mail &m = cfg.mail[kind];
-  const u32 lo = m.dst_off[tid], hi = m.dst_off[tid + 1], n = hi - lo;
-  const KTab &t = kind == MAIL_S ? cfg.g_s : cfg.g_b;
-  const u64 *s = t.slots + (u64)tid * t.stride, *keys = m.sorted + lo;
-  u64 acc = 0;
-  for (u32 o = 0; o < n; o += FQ_WAVE) {
-    u32 spins = 0;
-    while ((i32)(o / FQ_WAVE - lds_load_acq(&sm->pf_done)) > (i32)FQSX_PF_AHEAD) {   // a few batches ahead (their lines stay in L2 that long)
-      fq_sleep();
-      if (++spins > (1u << 18)) { keep_live(acc); return; }          // (the inserting wave gave up, or is far slower than ever seen: just stop)
-    }
-    if (o + FQ_LANE < n) {
-      const TabHome th = tab_home(t, keys[o + FQ_LANE] >> (64 - 2 * t.k));
-      acc ^= touch_load(&s[(u64)th.a * FQSX_BKT]) ^ touch_load(&s[(u64)th.b * FQSX_BKT]);
-    }
-  }
-  keep_live(acc);
+#ifndef FQSX_WIN_PER
+#define FQSX_WIN_PER 2u                                      /* keys of a window per thread */
+#endif
+#define FQSX_INS_WG_PER_CU 2u                                /* workgroups the register budget leaves room for on a CU (launch bound) */
+#define FQSX_INS_THREADS (FQSX_INS_WAVES * 64u)
+#define FQSX_WIN_MAX (FQSX_WIN_PER * FQSX_INS_THREADS)      /* keys of a window (FQSX_INS_WINDOW: fewer) */
+#define FQSX_WIN_HASH (2u * FQSX_WIN_MAX)
+#define FQSX_WIN_MULT_MAX 32u                                /* upper limit of the multiplicity cap (FQSX_INS_MAXMULT) */
+// LDS of k_insert_phase: 36 KB at 1 024 keys a window; with the registers the launch bound leaves (FQSX_INS_WG_PER_CU) two
+// workgroups share a CU, so that four files on CU partitions (192 workgroups on 64 CUs) do not take turns
+struct InsWgShared {
+  u32 mt[2][624];                  // the owner's stream of this kind (RNG_B / RNG_S)
+  u32 mt_idx[2];
+  u64 ib_pos[64];                  // scratch of the in-order routine (insert_batch_k)
+  u64 ib_hash[256];
+  u64 h_tag[FQSX_WIN_HASH];        // rank hash: the k-mer (~0: free); after the rank rounds: the slot its first occurrence claimed
+  u32 h_min[FQSX_WIN_HASH];        // ... ((63 - round) << 16 | smallest key index still unranked)
+  u32 rnd[FQSX_WIN_MAX];           // the window's draws in stream order
+  u32 more[FQSX_WIN_MULT_MAX + 1]; // rank round q left keys unranked
+  u32 n_draw[FQSX_WIN_PER][FQSX_INS_WAVES], n_new[FQSX_WIN_PER][FQSX_INS_WAVES];   // per wave and key row: draws, new keys
+  u32 in_order;                    // the window goes through the in-order routine
+  u32 filled;                      // occupied slots of the sub-table
+  u32 err;
+  u64 acc[2];                      // p-mers: fields filled / updated, summed over the waves
+};
+static_assert(RNG_B == 0 && RNG_S == 1, "InsWgShared.mt holds the streams of the global tables only");
+#ifndef FQSX_EMU
+static_assert(sizeof(InsWgShared) * FQSX_INS_WG_PER_CU <= 128u * 1024u, "FQSX_INS_WG_PER_CU insert-phase workgroups must fit one CU's LDS with room to spare");
+
+// the slot (relative to s) new key v has claimed with count 1 (a function of its own for the reason given at tab_locate);
+// ~0: no room, or the key was there after all -- neither can happen to a key the window's look-up found absent
+FQ_DEVN u64 tab_claim_new(const KTab t, u64 *s, u64 v) {
+  bool claimed = false;
+  const u64 *p = tab_find_or_claim(t, s, v, (v << t.cbits) | 1ull, claimed);
+  return p && claimed ? (u64)(p - s) : ~0ull;
 }
-#endif
+
+// keys[0 .. n) of sub-table `sub`, window by window (see above).  Called by every thread of the workgroup; err, n_par and
+// n_fb (windows applied in parallel / in order) come out workgroup-uniform, nslots is this thread's own count.
+FQ_DEV void insert_windows(const DevCfg &cfg, InsWgShared *sm, const KTab &t, u32 sub, const u64 *keys, u32 n, u32 rng, const Cinc &ci,
+                           u32 win, u32 maxmult, u64 &nslots, u32 &err, u32 &n_par, u32 &n_fb) {
+  u64 *s = t.slots + (u64)sub * t.stride;
+  const u32 cm = (1u << t.cbits) - 1u;
+  const u32 tx = FQ_TID, lane = FQ_LANE, wave = FQ_WAVE_ID;
+  const u64 below = (1ull << lane) - 1ull;
+  win = win < FQSX_WIN_MAX ? win : FQSX_WIN_MAX;   // (the LDS arrays are sized for these)
+  maxmult = maxmult < 1 ? 1 : maxmult < FQSX_WIN_MULT_MAX ? maxmult : FQSX_WIN_MULT_MAX;
+  if (tx == 0) sm->filled = t.filled[sub];
+  for (u32 wo = 0; wo < n; wo += win) {
+    const u32 wn = n - wo < win ? n - wo : win;
+    u32 hs = 128;
+    while (hs < 2 * wn) hs <<= 1;
+    for (u32 i = tx; i < hs; i += FQSX_INS_THREADS) { sm->h_tag[i] = ~0ull; sm->h_min[i] = ~0u; }
+    if (tx <= FQSX_WIN_MULT_MAX) sm->more[tx] = 0;
+    if (tx == 0) sm->in_order = 0;
+    __syncthreads();
+    // locate, and a place in the rank hash
+    u64 v[FQSX_WIN_PER], pos[FQSX_WIN_PER], item[FQSX_WIN_PER];
+    u32 he[FQSX_WIN_PER], rk[FQSX_WIN_PER];
+    bool act[FQSX_WIN_PER], drw[FQSX_WIN_PER];
+#pragma unroll
+    for (u32 j = 0; j < FQSX_WIN_PER; ++j) {
+      const u32 i = j * FQSX_INS_THREADS + tx;
+      act[j] = i < wn;
+      v[j] = 0; pos[j] = ~0ull; item[j] = 0; he[j] = 0; rk[j] = ~0u; drw[j] = false;
+      if (act[j]) {
+        v[j] = keys[wo + i] >> (64 - 2 * t.k);
+        const TabLoc L = tab_locate_live(t, s, v[j]);   // (absent: item == 0; where the key goes is the claim's business)
+        pos[j] = L.pos; item[j] = L.item; nslots += L.ns;
+        u32 h = (u32)((v[j] * 0x9E3779B97F4A7C15ull) >> 40) & (hs - 1);
+        for (u32 pr = 0; pr < hs; ++pr) {   // (at most half of the entries are ever taken)
+          const u64 old = (u64)atomicCAS((unsigned long long *)&sm->h_tag[h], ~0ull, (unsigned long long)v[j]);
+          if (old == ~0ull || old == v[j]) break;
+          h = (h + 1) & (hs - 1);
+        }
+        he[j] = h;
+      }
+    }
+    __syncthreads();
+    // rank rounds: q ends as the largest rank of the window (over: some k-mer occurs more than maxmult times)
+    u32 q = 0;
+    bool over = false;
+    for (;;) {
+#pragma unroll
+      for (u32 j = 0; j < FQSX_WIN_PER; ++j)
+        if (act[j] && rk[j] == ~0u) atomicMin(&sm->h_min[he[j]], ((63u - q) << 16) | (j * FQSX_INS_THREADS + tx));
+      __syncthreads();
+      bool left = false;
+#pragma unroll
+      for (u32 j = 0; j < FQSX_WIN_PER; ++j)
+        if (act[j] && rk[j] == ~0u) {
+          if ((sm->h_min[he[j]] & 0xffffu) == j * FQSX_INS_THREADS + tx) rk[j] = q; else left = true;
+        }
+      if (left) sm->more[q] = 1;
+      __syncthreads();
+      if (!sm->more[q]) break;
+      if (++q >= maxmult) { over = true; break; }
+    }
+    // decide: who draws, who is new; is any of it undecidable?
+    bool amb = false;
+#pragma unroll
+    for (u32 j = 0; j < FQSX_WIN_PER; ++j) {
+      const u32 c0 = (u32)item[j] & cm;
+      if (act[j] && !over) {
+        amb |= insplan_ambiguous(c0, rk[j], ci.thr, ci.maxv);
+        drw[j] = insplan_draws(c0, rk[j], ci.thr, ci.maxv);
+      }
+      const u64 dm = wave_ballot(drw[j]), nm = wave_ballot(act[j] && !over && item[j] == 0 && rk[j] == 0);
+      if (lane == 0) { sm->n_draw[j][wave] = popc64(dm); sm->n_new[j][wave] = popc64(nm); }
+    }
+    if (amb) sm->in_order = 1;
+    __syncthreads();
+    if (over || sm->in_order) {   // nothing of the window has been written: the in-order routine, exact by construction
+      if (wave == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // (its look-ups read through this CU's L1: drop lines older than the claims)
+        u32 e1 = 0;
+        insert_keys(cfg, sm, t, sub, keys + wo, wn, rng, ci, nslots, e1);
+        FQ_SYNC_MEM();
+        if (lane == 0) { sm->filled = t.filled[sub]; if (e1) sm->err = e1; }
+      }
+      ++n_fb;
+      __syncthreads();
+      if (sm->err) { err = sm->err; break; }
+      continue;
+    }
+    // draw numbers: exclusive scan of the flags in key order (row j before row j + 1, wave by wave inside a row)
+    u32 D = 0, n_new = 0, base[FQSX_WIN_PER];
+#pragma unroll
+    for (u32 j = 0; j < FQSX_WIN_PER; ++j) base[j] = 0;
+#pragma unroll
+    for (u32 jj = 0; jj < FQSX_WIN_PER; ++jj)
+      for (u32 ww = 0; ww < FQSX_INS_WAVES; ++ww) {
+        const u32 c = sm->n_draw[jj][ww];
+#pragma unroll
+        for (u32 j = 0; j < FQSX_WIN_PER; ++j) base[j] += (jj < j || (jj == j && ww < wave)) ? c : 0u;
+        D += c;
+        n_new += sm->n_new[jj][ww];
+      }
+#pragma unroll
+    for (u32 j = 0; j < FQSX_WIN_PER; ++j) base[j] += popc64(wave_ballot(drw[j]) & below);   // = this key's draw, if it makes one
+    const u32 filled = sm->filled;
+    if ((u64)(filled + n_new) * 10 >= t.nb * FQSX_BKT * 9) { err = FQSX_ERR_GTAB_FULL; break; }   // (uniform: all of it read from LDS)
+    if (wave == 0 && D) {   // the next D outputs of the stream; an index of 624 with the twist still pending is a valid state to leave
+      u32 idx = sm->mt_idx[rng];
+      for (u32 out = 0; out < D;) {
+        if (idx >= 624) { mt_twist(sm->mt[rng]); idx = 0; }
+        const u32 take = 624 - idx < D - out ? 624 - idx : D - out;
+        for (u32 x = lane; x < take; x += FQ_WAVE) sm->rnd[out + x] = mt_temper(sm->mt[rng][idx + x]);
+        FQ_SYNC();
+        idx += take; out += take;
+      }
+      if (lane == 0) sm->mt_idx[rng] = idx;
+    }
+    // claim: the first occurrence of an absent key takes its slot and leaves it in the hash record for the later ones
+    bool lost = false;
+#pragma unroll
+    for (u32 j = 0; j < FQSX_WIN_PER; ++j)
+      if (act[j] && item[j] == 0 && rk[j] == 0) {
+        pos[j] = tab_claim_new(t, s, v[j]);
+        sm->h_tag[he[j]] = pos[j];
+        lost |= pos[j] == ~0ull;
+      }
+    if (lost) sm->err = FQSX_ERR_GTAB_FULL;
+    if (tx == 0) t.filled[sub] = filled + n_new;
+    // (No wait for vector memory in front of this barrier, unlike the one behind the commit rounds: every claim is a compare-and-swap
+    // whose result its thread has used, so L2 has acknowledged it; a claim made with a plain store would need FQ_SYNC_MEM here.)
+    __syncthreads();
+    if (tx == 0) sm->filled = filled + n_new;
+    if (sm->err) { err = sm->err; break; }
+    // commit, rank round by rank round
+    for (u32 r = 0; r <= q; ++r) {
+#pragma unroll
+      for (u32 j = 0; j < FQSX_WIN_PER; ++j)
+        if (act[j] && rk[j] == r && !(item[j] == 0 && r == 0)) {   // (a claim stored its 1 already)
+          u64 *sp = s + (item[j] ? pos[j] : sm->h_tag[he[j]]);
+          const u64 cur = r == 0 ? item[j] : __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (insplan_adds((u32)cur & cm, drw[j], drw[j] ? sm->rnd[base[j]] : 0u, ci.thr, ci.mult, cm)) *sp = cur + 1;
+        }
+      // Every storing wave waits for its stores to be acknowledged by L2 before the barrier: the reloads of the next round and
+      // the look-ups of the next window are served by L2, and a workgroup-scope barrier alone orders accesses only as far as
+      // this CU's L1 -- a store still on its way would be overtaken.
+      // (After the last round too: the next window clears the hash records this round still reads slots from.)
+      FQ_SYNC_MEM();
+      __syncthreads();
+    }
+    ++n_par;
+  }
+}
+#endif   // !FQSX_EMU
+
 template <class SM>
-FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind) {
+FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind, u32 win, u32 maxmult) {
   WState *ws = cfg.ws + tid;
   const Mail &m = cfg.mail[kind];
   const u32 lo = m.dst_off[tid], hi = m.dst_off[tid + 1];
   if (kind == MAIL_P) {
-    // p-mers: saturating 2-bit increments; order-free, so lanes update concurrently with CAS
+    // p-mers: saturating 2-bit increments; order-free, so all threads update concurrently with CAS
     u64 nf = 0, nu = 0;
-    for (u32 e = lo + FQ_LANE; e < hi; e += FQ_WAVE) {
+    for (u32 e = lo + FQ_TID; e < hi; e += FQ_NTHREADS) {
       u64 idx = m.sorted[e];
       u64 *wp = cfg.siv + (idx >> 5);
       u32 sh = 2 * (u32)(idx & 31);
@@ -4840,7 +5029,14 @@ FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind) {
     }
     nf = wave_sum64(nf);
     nu = wave_sum64(nu);
-    if (FQ_LANE == 0) {  // update_no_filled / update_no_updates, dna.cpp:2416-2418 (atomics, bit_vec.h:25-26)
+#ifndef FQSX_EMU
+    if (FQ_TID == 0) sm->acc[0] = sm->acc[1] = 0;
+    FQ_WG_BARRIER();
+    if (FQ_LANE == 0) { atomicAdd((unsigned long long *)&sm->acc[0], (unsigned long long)nf); atomicAdd((unsigned long long *)&sm->acc[1], (unsigned long long)nu); }
+    FQ_WG_BARRIER();
+    nf = sm->acc[0]; nu = sm->acc[1];
+#endif
+    if (FQ_TID == 0) {  // update_no_filled / update_no_updates, dna.cpp:2416-2418 (atomics, bit_vec.h:25-26)
 #ifndef FQSX_EMU
       atomicAdd((unsigned long long *)&cfg.siv_stats[1], (unsigned long long)nf);
       atomicAdd((unsigned long long *)&cfg.siv_stats[0], (unsigned long long)(nu + ws->hidden_updates));
@@ -4856,28 +5052,38 @@ FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind) {
   const KTab &t = kind == MAIL_S ? cfg.g_s : cfg.g_b;
   const u32 rng = kind == MAIL_S ? RNG_S : RNG_B;
   const Cinc ci = kind == MAIL_S ? CINC_S : CINC_B;
-  u32 err = 0;
+  u32 err = 0, n_par = 0, n_fb = 0;
   u64 n_slots = 0;
-  FQ_SYNC();
-  for (u32 i = FQ_LANE; i < 624; i += FQ_WAVE) sm->mt[rng][i] = ws->mt[rng][i];
-  if (FQ_LANE == 0) sm->mt_idx[rng] = ws->mt_idx[rng];
-  FQ_SYNC();
-  if (sm->pf_on) insert_keys<SM, true>(cfg, sm, t, tid, m.sorted + lo, hi - lo, rng, ci, n_slots, err);
-  else insert_keys(cfg, sm, t, tid, m.sorted + lo, hi - lo, rng, ci, n_slots, err);
-  FQ_SYNC();
-  for (u32 i = FQ_LANE; i < 624; i += FQ_WAVE) ws->mt[rng][i] = sm->mt[rng][i];
+  for (u32 i = FQ_TID; i < 624; i += FQ_NTHREADS) sm->mt[rng][i] = ws->mt[rng][i];
+  if (FQ_TID == 0) { sm->mt_idx[rng] = ws->mt_idx[rng]; sm->err = 0; }
+  FQ_WG_BARRIER();
+#ifndef FQSX_EMU
+  if (win && t.two) insert_windows(cfg, sm, t, tid, m.sorted + lo, hi - lo, rng, ci, win, maxmult, n_slots, err, n_par, n_fb);
+  else
+#endif
+  if (FQ_WAVE_ID == 0) insert_keys(cfg, sm, t, tid, m.sorted + lo, hi - lo, rng, ci, n_slots, err);   // everything in order: one wave
+  (void)win; (void)maxmult;
+  FQ_WG_BARRIER();
+  for (u32 i = FQ_TID; i < 624; i += FQ_NTHREADS) ws->mt[rng][i] = sm->mt[rng][i];
   n_slots = wave_sum64(n_slots);
   if (FQ_LANE == 0) {
+#ifndef FQSX_EMU
+    if (n_slots) atomicAdd((unsigned long long *)&ws->stat[ST_GINS_SLOT], (unsigned long long)n_slots);
+#else
+    ws->stat[ST_GINS_SLOT] += n_slots;
+#endif
+    if (err) *cfg.err = err;
+  }
+  if (FQ_TID == 0) {
     ws->mt_idx[rng] = sm->mt_idx[rng];
 #ifndef FQSX_EMU
     atomicAdd((unsigned long long *)&ws->stat[ST_GINS], (unsigned long long)(hi - lo));
-    atomicAdd((unsigned long long *)&ws->stat[ST_GINS_SLOT], (unsigned long long)n_slots);
+    if (n_par) atomicAdd((unsigned long long *)&ws->stat[ST_INS_WIN], (unsigned long long)n_par);
+    if (n_fb) atomicAdd((unsigned long long *)&ws->stat[ST_INS_WIN_ORDER], (unsigned long long)n_fb);
 #else
     ws->stat[ST_GINS] += hi - lo;
-    ws->stat[ST_GINS_SLOT] += n_slots;
 #endif
   }
-  if (err) *cfg.err = err;
 }
 
 // End() of the block's range coder: 8 flush bytes (sub_rc.h:79-86, application.cpp:664-665); the stream

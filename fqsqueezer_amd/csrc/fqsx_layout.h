@@ -144,8 +144,11 @@ enum {
                    // algorithmic figure of SURVEY 8d
   ST_DEC_REFETCH,  // decoder: b-mer look-ups whose buckets, requested a position ahead, were dropped and looked up again (fqsx_dec.h: suffix_dec);
                    // counted as ST_GPROBE is (the wave-uniform count one lane holds), so figures of different builds compare only in kind
-  ST_N
+  ST_N,            // (the counters a worker keeps in registers during an encode / decode launch end here)
+  ST_INS_WIN = 14,       // insert phase: windows of s- / b-mer keys applied in parallel (fqsx_dev.h: insert_windows) ...
+  ST_INS_WIN_ORDER = 15  // ... and windows that went through the in-order routine instead
 };
+static_assert(ST_N <= ST_INS_WIN, "WState.stat[14..15] belong to the insert phase, [16..63] to the timing builds");
 // section timers (only maintained by -DFQSX_TIMING builds)
 enum { TM_TOTAL = 0, TM_SPEC, TM_FAST, TM_SLOW, TM_POST, TM_READ_HEAD, TM_LQ, TM_ROUGH, TM_REPM, TM_FINDC,
        CN_FAST, CN_SLOW, CN_CHUNK, CN_DIRTY, CN_ROUGH, CN_REPM,

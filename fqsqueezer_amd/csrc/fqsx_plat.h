@@ -35,6 +35,7 @@ typedef int32_t i32;
 #define FQ_KERNEL192 extern "C" __global__ __launch_bounds__(192)
 #define FQ_KERNEL256 extern "C" __global__ __launch_bounds__(256)
 #define FQ_KERNEL512 extern "C" __global__ __launch_bounds__(512)
+#define FQ_KERNEL_NW(n, w) extern "C" __global__ __launch_bounds__(n, w)   /* n threads; registers for at least w waves per SIMD */
 #define FQ_WAVE 64
 #define FQ_LANE ((u32)(threadIdx.x & 63u))
 #define FQ_BLOCK ((u32)blockIdx.x)
@@ -56,6 +57,9 @@ typedef int32_t i32;
 // The one barrier of the two-wave encode kernel (after the LDS queue indices are initialised)
 #define FQ_WG_BARRIER() __syncthreads()
 #define FQ_WAVE_ID ((u32)(threadIdx.x >> 6))
+// thread of the workgroup / threads per workgroup (kernels whose workgroup is more than one wave walk lists with these)
+#define FQ_TID ((u32)threadIdx.x)
+#define FQ_NTHREADS ((u32)blockDim.x)
 // LDS hand-off words between the two waves of a workgroup (release: everything this wave wrote before is
 // visible to a wave that acquires the value)
 FQ_DEV u32 lds_load_acq(const u32 *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -169,6 +173,7 @@ FQ_DEV double ema_update(double avg, double level) { return __dadd_rn(__dmul_rn(
 #define FQ_KERNEL192 static
 #define FQ_KERNEL256 static
 #define FQ_KERNEL512 static
+#define FQ_KERNEL_NW(n, w) static
 #define FQ_WAVE 1
 #define FQ_LANE 0u
 #define FQ_BLOCK (fq_emu_block)
@@ -181,6 +186,8 @@ FQ_DEV double ema_update(double avg, double level) { return __dadd_rn(__dmul_rn(
 #define FQ_SYNC_MEM() ((void)0)
 #define FQ_WG_BARRIER() ((void)0)
 #define FQ_WAVE_ID 0u
+#define FQ_TID 0u
+#define FQ_NTHREADS 1u
 FQ_DEV u32 lds_load_acq(const u32 *p) { return *p; }
 FQ_DEV void lds_store_rel(u32 *p, u32 v) { *p = v; }
 FQ_DEV void fq_sleep() {}
