@@ -87,6 +87,7 @@ _ABI = {
     "fqsx_cols_info": (_INT, [_P, _U64S]),
     "fqsx_cols_gather": (_INT, [_P, _P, _P, _U32, _P, _OUT, _OUT, _OUT]),
     "fqsx_cols_bases": (_INT, [_P, _P]),
+    "fqsx_cols_sort_order": (_INT, [_P, _P, _P, _U64S]),
     "fqsx_cols_download": (_INT, [_P, _P, _P, _U64]),
     "fqsx_cols_set_profiling": (_INT, [_P, _INT]),
     "fqsx_cols_kernel_times": (_INT, [_P, _MS]),
@@ -301,6 +302,11 @@ def sort_order(bases: np.ndarray, read_off: np.ndarray, device: int = 0, lib_pat
         raise _error(lib, "fqsx_sort_order", rc)
     if stats is not None:
         stats["batches"] = nb.value
+    return _bins_of(order, bins)
+
+
+def _bins_of(order: np.ndarray, bins: np.ndarray) -> List[np.ndarray]:
+    """order_out / bin_start of the fqsx_*sort_order calls as one index array per non-empty bin"""
     return [order[bins[b]:bins[b + 1]].astype(np.int64) for b in range(256) if bins[b + 1] > bins[b]]
 
 
@@ -674,8 +680,20 @@ class DeviceColumns(_Handle):
         self._call("fqsx_cols_download", self._h, d_ptr, out.ctypes.data, n_bytes)
         return out
 
+    def sort_order(self, stats: Optional[dict] = None) -> List[np.ndarray]:
+        """Read order of `fqs e -om s` for the store's records, sorted where they lie (fqsx_cols_sort_order): what sort_order
+        returns for the same reads.  stats receives "passes" (radix passes) and "scratch_bytes" (device memory the call
+        allocated at most, all of it handed back)."""
+        order = np.empty(max(len(self), 1), dtype=np.uint32)
+        bins = np.zeros(257, dtype=np.uint32)
+        info = (C.c_uint64 * 4)()
+        self._call("fqsx_cols_sort_order", self._h, order.ctypes.data, bins.ctypes.data, info)
+        if stats is not None:
+            stats["passes"], stats["scratch_bytes"] = int(info[0]), int(info[1])
+        return _bins_of(order, bins)
+
     def bases_to_host(self) -> np.ndarray:
-        """the whole base column (the sort pre-pass bins on the host)"""
+        """the whole base column"""
         out = np.empty(int(self.read_off[-1]), dtype=np.uint8)
         self._call("fqsx_cols_bases", self._h, out.ctypes.data)
         return out

@@ -2894,31 +2894,42 @@ FQ_KERNEL64 void k_sort_scatter(SortCfg c) {
 FQ_KERNEL64 void k_sort_flags(SortCfg c) { sort_flags_body(c, FQ_BLOCK); }
 FQ_KERNEL64 void k_sort_rank(SortCfg c) { sort_rank_body(c); }
 
-static int sort_rank_impl(DevCtx *c, const u8 *bases, const u64 *off, u32 n, std::vector<u32> &rank, u32 *passes_out) {
+// Device memory of one call on a context that outlives it: handed back together when the call ends, whatever its outcome
+struct DevScratch {
+  DevCtx *c;
+  std::vector<void *> held;
+  explicit DevScratch(DevCtx *ctx) : c(ctx) {}
+  template <class T> int get(T *&ptr, u64 bytes) {
+    void *p = nullptr;
+    const int rc = dalloc(c, &p, bytes, false);
+    if (rc) return rc;
+    held.push_back(p);
+    ptr = (T *)p;
+    return FQSX_OK;
+  }
+  ~DevScratch() {
+    if (held.empty()) return;
+    dev_drain(c);   // (a call that failed half-way may have launches in flight)
+    for (void *p : held) dfree(c, p);
+  }
+};
+
+// Dense ranks of the n reads s describes (s.bases / s.off or s.addr / s.len: sort_read): the rest of s is made here, in mem.
+// Launches are timed under kernel index kidx.
+static int sort_rank_run(DevCtx *c, u32 kidx, SortCfg &s, DevScratch &mem, std::vector<u32> &rank, u32 *passes_out) {
   int rc;
-  void *p = nullptr;
-  SortCfg s;
-  memset(&s, 0, sizeof(s));
-  s.n = n;
+  const u32 n = s.n;
   s.n_tiles = (n + FQSX_SORT_TILE - 1) / FQSX_SORT_TILE;
-  const u64 nb = off[n];
-  if ((rc = dalloc(c, &p, nb ? nb : 8, false))) return rc;
-  u8 *d_bases = (u8 *)p;
-  if ((rc = dalloc(c, &p, ((u64)n + 1) * sizeof(u64), false))) return rc;
-  u64 *d_off = (u64 *)p;
-  if ((rc = h2d(c, d_bases, bases, nb))) return rc;
-  if ((rc = h2d(c, d_off, off, ((u64)n + 1) * sizeof(u64)))) return rc;
-  s.bases = d_bases; s.off = d_off;
-  if ((rc = dalloc(c, &p, (u64)n * 4, false))) return rc; s.perm_in = (u32 *)p;
-  if ((rc = dalloc(c, &p, (u64)n * 4, false))) return rc; s.perm_out = (u32 *)p;
-  if ((rc = dalloc(c, &p, (u64)s.n_tiles * 256 * 4, false))) return rc; s.tile_hist = (u32 *)p;
-  if ((rc = dalloc(c, &p, 256 * 4, false))) return rc; s.dig_tot = (u32 *)p;
-  if ((rc = dalloc(c, &p, 257 * 4, false))) return rc; s.dig_off = (u32 *)p;
-  if ((rc = dalloc(c, &p, (u64)n * 4, false))) return rc; s.flags = (u32 *)p;
-  if ((rc = dalloc(c, &p, (u64)n * 4, false))) return rc; s.rank = (u32 *)p;
-  if ((rc = dalloc(c, &p, (u64)s.n_tiles * 10 * 4, false))) return rc; s.info = (u32 *)p;
-  LAUNCH(c, 2, k_sort_info, s.n_tiles, 64, s);
-  LAUNCH(c, 2, k_sort_iota, s.n_tiles, 64, s);
+  if ((rc = mem.get(s.perm_in, (u64)n * 4))) return rc;
+  if ((rc = mem.get(s.perm_out, (u64)n * 4))) return rc;
+  if ((rc = mem.get(s.tile_hist, (u64)s.n_tiles * 256 * 4))) return rc;
+  if ((rc = mem.get(s.dig_tot, 256 * 4))) return rc;
+  if ((rc = mem.get(s.dig_off, 257 * 4))) return rc;
+  if ((rc = mem.get(s.flags, (u64)n * 4))) return rc;
+  if ((rc = mem.get(s.rank, (u64)n * 4))) return rc;
+  if ((rc = mem.get(s.info, (u64)s.n_tiles * 10 * 4))) return rc;
+  LAUNCH(c, kidx, k_sort_info, s.n_tiles, 64, s);
+  LAUNCH(c, kidx, k_sort_iota, s.n_tiles, 64, s);
   std::vector<u32> info((u64)s.n_tiles * 10);
   if ((rc = d2h_sync(c, info.data(), s.info, info.size() * 4))) return rc;
   u32 mn = 0xffffffffu, mx = 0, set[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2934,10 +2945,10 @@ static int sort_rank_impl(DevCtx *c, const u8 *bases, const u64 *off, u32 n, std
   u32 passes = 0;
   auto pass = [&](u32 kind, u32 arg) -> int {
     s.kind = kind; s.arg = arg;
-    LAUNCH(c, 2, k_sort_count, s.n_tiles, 64, s);
-    LAUNCH(c, 2, k_sort_scan, 256, 64, s);
-    LAUNCH(c, 2, k_sort_dstoff, 1, 64, s);
-    LAUNCH(c, 2, k_sort_scatter, s.n_tiles, 64, s);
+    LAUNCH(c, kidx, k_sort_count, s.n_tiles, 64, s);
+    LAUNCH(c, kidx, k_sort_scan, 256, 64, s);
+    LAUNCH(c, kidx, k_sort_dstoff, 1, 64, s);
+    LAUNCH(c, kidx, k_sort_scatter, s.n_tiles, 64, s);
     std::swap(s.perm_in, s.perm_out);
     ++passes;
     return FQSX_OK;
@@ -2951,12 +2962,55 @@ static int sort_rank_impl(DevCtx *c, const u8 *bases, const u64 *off, u32 n, std
   if (mn != mx)
     for (u32 k = 0; k < 4 && (mx >> (8 * k)); ++k) if ((rc = pass(SORT_LEN, k))) return rc;
   for (u32 b = (mx + 3) / 4; b-- > 0;) if ((rc = pass(SORT_NT, b))) return rc;
-  LAUNCH(c, 2, k_sort_flags, s.n_tiles, 64, s);
-  LAUNCH(c, 2, k_sort_rank, 1, 64, s);
+  LAUNCH(c, kidx, k_sort_flags, s.n_tiles, 64, s);
+  LAUNCH(c, kidx, k_sort_rank, 1, 64, s);
   rank.resize(n);
   if ((rc = d2h_sync(c, rank.data(), s.rank, (u64)n * 4))) return rc;
   if (passes_out) *passes_out = passes;
   return FQSX_OK;
+}
+
+// the same for reads on the host: they are uploaded side by side
+static int sort_rank_impl(DevCtx *c, const u8 *bases, const u64 *off, u32 n, std::vector<u32> &rank, u32 *passes_out) {
+  int rc;
+  DevScratch mem(c);
+  SortCfg s;
+  memset(&s, 0, sizeof(s));
+  s.n = n;
+  const u64 nb = off[n];
+  u8 *d_bases = nullptr;
+  u64 *d_off = nullptr;
+  if ((rc = mem.get(d_bases, nb ? nb : 8))) return rc;
+  if ((rc = mem.get(d_off, ((u64)n + 1) * sizeof(u64)))) return rc;
+  if ((rc = h2d(c, d_bases, bases, nb))) return rc;
+  if ((rc = h2d(c, d_off, off, ((u64)n + 1) * sizeof(u64)))) return rc;
+  s.bases = d_bases; s.off = d_off;
+  return sort_rank_run(c, 2, s, mem, rank, passes_out);
+}
+
+// bin_start[257] and the reads grouped by bin, input order inside a bin, from the bin of every read
+static void sort_group_bins(const std::vector<u8> &bin, u32 *bin_start, std::vector<u32> &member) {
+  const u32 n = (u32)bin.size();
+  for (u32 b = 0; b <= 256; ++b) bin_start[b] = 0;
+  for (u32 r = 0; r < n; ++r) ++bin_start[bin[r] + 1u];
+  for (u32 b = 0; b < 256; ++b) bin_start[b + 1] += bin_start[b];
+  std::vector<u32> cur(bin_start, bin_start + 256);
+  member.resize(n);
+  for (u32 r = 0; r < n; ++r) member[cur[bin[r]]++] = r;
+}
+// libstdc++'s std::sort on the ranks, bin by bin for the bins [b0, b1): rank_of(i) is the rank of member[lo + i], lo the first
+// bin's start (the ranks of one GPU sort are comparable).  What std::sort does with reads that compare equal depends on the
+// order it meets them in: the bin's input order, which is member's.
+template <class R>
+static void sort_replay_bins(const u32 *bin_start, u32 b0, u32 b1, const std::vector<u32> &member, R &&rank_of,
+                             std::vector<std::pair<u32, u32>> &v /* (rank, read) */, u32 *order_out) {
+  const u32 lo = bin_start[b0], n = bin_start[b1] - lo;
+  v.resize(n);
+  for (u32 i = 0; i < n; ++i) v[i] = std::make_pair(rank_of(i), member[lo + i]);
+  for (u32 b = b0; b < b1; ++b)
+    std::sort(v.begin() + (bin_start[b] - lo), v.begin() + (bin_start[b + 1] - lo),
+              [](const std::pair<u32, u32> &x, const std::pair<u32, u32> &y) { return x.first < y.first; });
+  for (u32 i = 0; i < n; ++i) order_out[lo + i] = v[i].second;
 }
 
 // The reference keeps device^Whost memory bounded by binning to disk first (preprocess_se, application.cpp:349-412) and
@@ -2970,7 +3024,7 @@ extern "C" int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *rea
   for (u32 b = 0; b <= 256; ++b) bin_start[b] = 0;
   if (n_batches_out) *n_batches_out = 0;
   if (n_reads == 0) return FQSX_OK;
-  DevCtx dev;   // (every batch hands its allocations back before the next one)
+  DevCtx dev;   // (every batch hands its allocations back before the next one: sort_rank_impl)
   DevCtx *c = &dev;
   int rc = dev_open(c, device);
   if (rc) return rc;
@@ -2985,13 +3039,10 @@ extern "C" int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *rea
     u32 id = 0;
     for (u32 i = 0; i < 4; ++i) id = (id << 2) | (i < len ? nt(bases[b + i]) : 3u);
     bin[r] = (u8)id;
-    ++bin_start[id + 1];
     bin_bases[id] += len;
   }
-  for (u32 b = 0; b < 256; ++b) bin_start[b + 1] += bin_start[b];
-  std::vector<u32> cur(bin_start, bin_start + 256);
-  std::vector<u32> member(n_reads);   // reads grouped by bin, input order inside a bin
-  for (u32 r = 0; r < n_reads; ++r) member[cur[bin[r]]++] = r;
+  std::vector<u32> member;
+  sort_group_bins(bin, bin_start, member);
   u32 n_batches = 0;
   std::vector<u8> gb;
   std::vector<u64> go;
@@ -3021,16 +3072,8 @@ extern "C" int fqsx_sort_order_batched(const uint8_t *bases, const uint64_t *rea
         pb = gb.data(); po = go.data();
       }
       rc = sort_rank_impl(c, pb, po, n, rank, nullptr);
-      dev_drain(c);
-      dfree_all(c);
       if (rc) break;
-      // libstdc++'s std::sort per bin on the ranks (ranks of one batch are comparable; a bin never spans batches)
-      v.resize(n);
-      for (u32 i = 0; i < n; ++i) v[i] = std::make_pair(whole ? rank[member[lo + i]] : rank[i], member[lo + i]);
-      for (u32 b = b0; b < b1; ++b)
-        std::sort(v.begin() + (bin_start[b] - lo), v.begin() + (bin_start[b + 1] - lo),
-                  [](const std::pair<u32, u32> &x, const std::pair<u32, u32> &y) { return x.first < y.first; });
-      for (u32 i = 0; i < n; ++i) order_out[lo + i] = v[i].second;
+      sort_replay_bins(bin_start, b0, b1, member, [&](u32 i) { return whole ? rank[member[lo + i]] : rank[i]; }, v, order_out);
       ++n_batches;
     }
     b0 = b1;
@@ -3246,6 +3289,40 @@ static int cols_launch(fqsx_cols *a, const ColsCfg &cfg, u32 kidx) {
   return FQSX_OK;
 }
 
+// Sort pre-pass on the store (n records, n > 0): where every record lies and its bin (k_cols_locate), then the ranks of the
+// sort of fqsx_sort.h reading the reads there.  Everything it allocates is in mem: per record 8 + 4 + 1 bytes here and 16 in
+// sort_rank_run, the tiles' histograms and info, and a copy of the chunk table (48 bytes a chunk: the store's own is written
+// when the first block is cut, and the store is left as it was found).  Launches are timed under kernel index 1.
+static int cols_sort_ranks(fqsx_cols *s, DevScratch &mem, std::vector<u32> &rank, std::vector<u8> &bin, u32 *passes_out) {
+  const u32 n = (u32)s->n_rec;
+  ColsLocCfg loc;
+  memset(&loc, 0, sizeof(loc));
+  ColsChunk *table = nullptr;
+  DEVCHK(mem.get(table, s->chunks.size() * sizeof(ColsChunk)));
+  DEVCHK(mem.get(loc.addr, (u64)n * sizeof(u64)));
+  DEVCHK(mem.get(loc.len, (u64)n * sizeof(u32)));
+  DEVCHK(mem.get(loc.bin, n));
+  DEVCHK(h2d(s, table, s->chunks.data(), s->chunks.size() * sizeof(ColsChunk)));
+  DEVCHK(dzero(s, s->d_err, 4 * sizeof(u32)));
+  loc.src.chunk = table; loc.src.n_chunks = (u32)s->chunks.size(); loc.src.n_rec = n;
+  loc.err = s->d_err;
+  const u64 per_group = (u64)COLS_WAVES * FQ_WAVE;
+  LAUNCH(s, 1, k_cols_locate, (u32)((n + per_group - 1) / per_group), 256, loc);
+  u32 err[4] = {0, 0, 0, 0};
+  DEVCHK(d2h_sync(s, err, s->d_err, sizeof(err)));
+  if (err[COLS_ERR_INDEX] || err[COLS_ERR_LENGTH] || err[COLS_ERR_RANGE]) {
+    g_err = "device error in the column sort: a record outside its chunk or a read outside its chunk's bases";
+    return FQSX_E_DEVICE;
+  }
+  SortCfg cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.n = n;
+  cfg.addr = loc.addr; cfg.len = loc.len;
+  DEVCHK(sort_rank_run(s, 1, cfg, mem, rank, passes_out));
+  bin.resize(n);
+  return d2h_sync(s, bin.data(), loc.bin, n);
+}
+
 extern "C" {
 
 void fqsx_cols_destroy(fqsx_cols *s) {
@@ -3362,6 +3439,30 @@ int fqsx_cols_bases(fqsx_cols *s, uint8_t *out) {
     at += ck.n_bytes;
   }
   return dev_sync(s);
+}
+
+int fqsx_cols_sort_order(fqsx_cols *s, uint32_t *order_out, uint32_t *bin_start /*[257]*/, uint64_t info_out[4]) {
+  if (!s || !order_out || !bin_start) { g_err = "null argument"; return FQSX_E_ARG; }
+  for (u32 b = 0; b <= 256; ++b) bin_start[b] = 0;
+  if (info_out) info_out[0] = info_out[1] = info_out[2] = info_out[3] = 0;
+  if (s->n_rec == 0) return FQSX_OK;
+  DEVCHK(dev_enter(s));
+  const u64 held = s->dev_bytes;
+  std::vector<u32> rank, member;
+  std::vector<u8> bin;
+  u32 passes = 0;
+  u64 scratch = 0;
+  {
+    DevScratch mem(s);   // (nothing is handed back before the end: what is held then is the most the call held)
+    const int rc = cols_sort_ranks(s, mem, rank, bin, &passes);
+    scratch = s->dev_bytes - held;
+    if (rc) return rc;
+  }
+  sort_group_bins(bin, bin_start, member);
+  std::vector<std::pair<u32, u32>> v;
+  sort_replay_bins(bin_start, 0, 256, member, [&](u32 i) { return rank[member[i]]; }, v, order_out);
+  if (info_out) { info_out[0] = passes; info_out[1] = scratch; info_out[2] = s->n_rec; }
+  return FQSX_OK;
 }
 
 int fqsx_cols_download(fqsx_cols *s, const void *d_src, void *h_dst, uint64_t n_bytes) {

@@ -10,9 +10,13 @@
 //                   records, sixteen lanes to a record, 16 bytes per lane where the destination is aligned.
 // A record that fails a check sets its error word and is not copied, so nothing outside the block buffers is ever written;
 // with store = 0 the kernel only checks, which is how the host refuses a block before a byte of the previous one is touched.
+//   k_cols_locate   for the sort pre-pass of `-om s` (fqsx_sort.h), which reads the reads where the store keeps them: per record
+//                   of the store the device address of its first base, its length and its bin, one record per lane, checked
+//                   the same way.
 // Workgroups are 256 threads (4 waves); the emulation build runs them as one 1-lane wave.
 #pragma once
 #include "fqsx_plat.h"
+#include "fqsx_sort.h"
 
 #ifndef FQSX_EMU
 #define COLS_WAVES 4u   // waves of a workgroup
@@ -49,6 +53,16 @@ struct ColsCfg {
 struct ColsRec { const u8 *sb, *sq; u64 d; u32 len; };   // source of the bases and of the qualities, destination offset, bytes
 struct alignas(16) Cols16 { u64 lo, hi; };
 
+// the last of the n_chunks > 0 chunks whose rec0 is not above rec
+FQ_DEV u32 cols_chunk_of(const ColsChunk *chunk, u32 n_chunks, u64 rec) {
+  u32 lo = 0, hi = n_chunks;   // chunk[lo].rec0 <= rec < chunk[hi].rec0
+  while (hi - lo > 1) {
+    const u32 mid = lo + (hi - lo) / 2;
+    if (chunk[mid].rec0 <= rec) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // read i of the block: where it comes from and where it goes, len = 0 unless every check passes
 FQ_DEV ColsRec cols_lookup(const ColsCfg &c, u64 i) {
   ColsRec r = {nullptr, nullptr, 0, 0};
@@ -60,12 +74,7 @@ FQ_DEV ColsRec cols_lookup(const ColsCfg &c, u64 i) {
   const u64 rec = c.idx[c.n_src == 2 ? i >> 1 : i];
   if (rec >= n_rec) { c.err[COLS_ERR_INDEX] = 1; return r; }
   if (n_chunks == 0) { c.err[COLS_ERR_RANGE] = 1; return r; }
-  u32 lo = 0, hi = n_chunks;   // chunk[lo].rec0 <= rec < chunk[hi].rec0
-  while (hi - lo > 1) {
-    const u32 mid = lo + (hi - lo) / 2;
-    if (chunk[mid].rec0 <= rec) lo = mid; else hi = mid;
-  }
-  const ColsChunk ch = chunk[lo];
+  const ColsChunk ch = chunk[cols_chunk_of(chunk, n_chunks, rec)];
   if (rec < ch.rec0 || rec - ch.rec0 >= ch.n_rec) { c.err[COLS_ERR_RANGE] = 1; return r; }
   const u64 so = ch.off[rec - ch.rec0], se = ch.off[rec - ch.rec0 + 1];
   if (se < so || se > ch.n_bytes || se - so > 0xffffffffull) { c.err[COLS_ERR_RANGE] = 1; return r; }
@@ -105,4 +114,38 @@ FQ_KERNEL256 void k_cols_gather(ColsCfg c) {
     cols_copy(c.out[0] + d, sb, len, sl);
     cols_copy(c.out[1] + d, sq, len, sl);
   }
+}
+
+// Where the sort pre-pass finds record r, and the reference's bin of it: the first four bases under A, C, G = 0, 1, 2 and
+// everything else 3 -- a position past the end of the read included, which there lands on the line feed (preprocess_se,
+// application.cpp:383-391).  (The sort KEY of a missing position is 0, sort_digit: "shorter first".  Both rules meet in reads
+// of fewer than four bases.)  A record that fails a check sets the error word and is written as an empty read at address 0.
+struct ColsLocCfg {
+  ColsSrc src;
+  u64 *addr;   // [src.n_rec] device address of the record's first base
+  u32 *len;    // [src.n_rec]
+  u8 *bin;     // [src.n_rec]
+  u32 *err;    // [COLS_N_ERR]
+};
+FQ_KERNEL256 void k_cols_locate(ColsLocCfg c) {
+  const u64 r = ((u64)FQ_BLOCK * COLS_WAVES + FQ_WAVE_ID) * FQ_WAVE + FQ_LANE;
+  if (r >= c.src.n_rec) return;
+  const u8 *p = nullptr;
+  u32 len = 0;
+  bool ok = c.src.n_chunks != 0;
+  if (ok) {
+    const ColsChunk ch = c.src.chunk[cols_chunk_of(c.src.chunk, c.src.n_chunks, r)];
+    ok = r >= ch.rec0 && r - ch.rec0 < ch.n_rec;
+    if (ok) {
+      const u64 so = ch.off[r - ch.rec0], se = ch.off[r - ch.rec0 + 1];
+      ok = se >= so && se <= ch.n_bytes && se - so <= 0xffffffffull;
+      if (ok) { p = ch.bases + so; len = (u32)(se - so); }
+    }
+  }
+  if (!ok) c.err[COLS_ERR_RANGE] = 1;
+  u32 id = 0;
+  for (u32 i = 0; i < 4; ++i) id = (id << 2) | (i < len ? sort_nt(p[i]) : 3u);
+  c.addr[r] = (u64)(uintptr_t)p;
+  c.len[r] = len;
+  c.bin[r] = (u8)id;
 }

@@ -14,8 +14,10 @@
 enum { SORT_NT = 0, SORT_LEN = 1, SORT_RAW = 2 };
 
 struct SortCfg {
-  const u8 *bases;
+  const u8 *bases;    // the reads side by side under off[n + 1] ...
   const u64 *off;
+  const u64 *addr;    // ... or, addr != null, each where it lies: device address of read r's first base and its length
+  const u32 *len;     //     (resident columns, fqsx_cols.h: k_cols_locate)
   u32 n, n_tiles;
   u32 *perm_in, *perm_out;
   u32 *tile_hist;   // [n_tiles][256]
@@ -29,9 +31,23 @@ struct SortCfg {
 };
 
 FQ_DEV u32 sort_nt(u8 c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : 3u; }  // dna_convert_NT, io.h:552-562
+// read r: the one place that knows where the reads are kept
+struct SortRead { const u8 *p; u32 len; };
+FQ_DEV SortRead sort_read(const SortCfg &c, u32 r) {
+  SortRead x;
+  if (c.addr) {
+    x.p = (const u8 *)(uintptr_t)c.addr[r];
+    x.len = c.len[r];
+  } else {
+    const u64 b = c.off[r];
+    x.p = c.bases + b;
+    x.len = (u32)(c.off[r + 1] - b);
+  }
+  return x;
+}
 FQ_DEV u32 sort_digit(const SortCfg &c, u32 r) {
-  const u64 b = c.off[r];
-  const u32 len = (u32)(c.off[r + 1] - b);
+  const SortRead x = sort_read(c, r);
+  const u32 len = x.len;
   if (c.kind == SORT_LEN) return (len >> (8 * c.arg)) & 255u;
   u32 d = 0;
   if (c.kind == SORT_NT) {
@@ -39,14 +55,14 @@ FQ_DEV u32 sort_digit(const SortCfg &c, u32 r) {
     // "equal on the common prefix: shorter first"
     for (u32 k = 0; k < 4; ++k) {
       const u32 pos = 4 * c.arg + k;
-      d = (d << 2) | (pos < len ? sort_nt(c.bases[b + pos]) : 0u);
+      d = (d << 2) | (pos < len ? sort_nt(x.p[pos]) : 0u);
     }
     return d;
   }
   const u32 per = 8 / c.raw_bits;   // raw bytes decide only between reads equal so far: same length, same N->T codes
   for (u32 k = 0; k < per; ++k) {
     const u32 pos = per * c.arg + k;
-    d = (d << c.raw_bits) | (pos < len ? (u32)c.raw_code[c.bases[b + pos]] : 0u);
+    d = (d << c.raw_bits) | (pos < len ? (u32)c.raw_code[x.p[pos]] : 0u);
   }
   return d;
 }
@@ -57,12 +73,12 @@ FQ_DEV void sort_info_body(const SortCfg &c, u32 blk, u32 *lds /*[64][10]*/) {
   for (u32 l = FQ_LANE; l < 64; l += FQ_WAVE) {
     u32 mn = 0xffffffffu, mx = 0, set[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (u32 r = lo + l; r < hi; r += 64) {
-      const u64 b = c.off[r];
-      const u32 len = (u32)(c.off[r + 1] - b);
+      const SortRead x = sort_read(c, r);
+      const u32 len = x.len;
       mn = len < mn ? len : mn;
       mx = len > mx ? len : mx;
       for (u32 i = 0; i < len; ++i) {
-        const u8 ch = c.bases[b + i];
+        const u8 ch = x.p[i];
         if (ch != 'A' && ch != 'C' && ch != 'G') set[ch >> 5] |= 1u << (ch & 31);
       }
     }
@@ -148,11 +164,9 @@ FQ_DEV void sort_flags_body(const SortCfg &c, u32 blk) {
   for (u32 e = lo + FQ_LANE; e < hi; e += FQ_WAVE) {
     u32 f = 0;
     if (e > 0) {
-      const u32 x = c.perm_in[e - 1], y = c.perm_in[e];
-      const u64 bx = c.off[x], by = c.off[y];
-      const u32 lx = (u32)(c.off[x + 1] - bx), ly = (u32)(c.off[y + 1] - by);
-      f = lx != ly;
-      for (u32 i = 0; i < lx && !f; ++i) f = c.bases[bx + i] != c.bases[by + i];
+      const SortRead x = sort_read(c, c.perm_in[e - 1]), y = sort_read(c, c.perm_in[e]);
+      f = x.len != y.len;
+      for (u32 i = 0; i < x.len && !f; ++i) f = x.p[i] != y.p[i];
     }
     c.flags[e] = f;
   }

@@ -12,14 +12,19 @@ from . import hostpipe as hp
 from .codec import DeviceBlock, DeviceColumns, DnaCodec, IdFallback, MetaCodec, QualCodec, parse_fastq, sort_order
 
 
-def _gpu_groups(rec, device: int, lib_path: Optional[str]):
+def _gpu_groups(rec, device: int, lib_path: Optional[str], stats: Optional[dict] = None):
     """Sorted-mode read order from the GPU pre-pass (bins + per-bin order incl. the reference's order of equal reads) on the base
-    column of rec: hostpipe.Records, hostpipe.Columns or codec.DeviceColumns (which brings the column to the host for it)."""
-    if isinstance(rec, hp.Records):
-        bases, off = rec.block(np.arange(len(rec), dtype=np.int64))
+    column of rec: hostpipe.Records, hostpipe.Columns or codec.DeviceColumns (sorted in the store: no base comes to the host).
+    stats["sort"]: "resident", "passes" and "scratch_bytes" of the store's sort, or "resident" False and "batches"."""
+    st = {"resident": isinstance(rec, DeviceColumns)}
+    if st["resident"]:
+        groups = rec.sort_order(stats=st)
     else:
-        bases, off = (rec.bases_to_host() if isinstance(rec, DeviceColumns) else rec.bases), rec.read_off
-    return sort_order(bases, off, device=device, lib_path=lib_path)
+        bases, off = rec.block(np.arange(len(rec), dtype=np.int64)) if isinstance(rec, hp.Records) else (rec.bases, rec.read_off)
+        groups = sort_order(bases, off, device=device, lib_path=lib_path, stats=st)
+    if stats is not None:
+        stats["sort"] = st
+    return groups
 
 
 def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device: int, lib_path: Optional[str], stats: Optional[dict] = None,
@@ -152,7 +157,7 @@ def _compress(inputs, ids_fit, threads: int, order: str, genome_size_mbp: int, q
         stats["gpu_ids"] = gpu_ids
     mode = ("pe_" if paired else "se_") + ("sorted" if order == "s" else "original")
     header = hp.make_header(threads, mode, genome_size_mbp, quality_mode, id_mode, quality_thr)
-    groups = _gpu_groups(c1, device, lib_path) if order == "s" else None   # mates follow mate 1's order, io.h:541-550
+    groups = _gpu_groups(c1, device, lib_path, stats) if order == "s" else None   # mates follow mate 1's order, io.h:541-550
     if resident and profile:
         c1.set_profiling(True)
     sizes = [c.record_sizes() for c in inputs]
@@ -219,11 +224,12 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
     reference's, params.h:53-78).  The text is parsed on the GPU into columns (codec.parse_fastq), the sort pre-pass runs on the
     base column, and the blocks are cut from the columns with vectorised gathers.  Returns what compress_records* return.
     ValueError: a record whose quality line differs in length from its base line; mate files with different numbers of records.
-    gpu_ids: see compress_records.  stats: "parse" (one dict per input), "gpu_ids" (the choice made), "id_host_fallback" (the id coder
-    changed over to the host coder in mid-file) and what encode_blocks adds.
+    gpu_ids: see compress_records.  stats: "parse" (one dict per input), "sort" (sorted order: what _gpu_groups reports of the
+    pre-pass), "gpu_ids" (the choice made), "id_host_fallback" (the id coder changed over to the host coder in mid-file) and what
+    encode_blocks adds.
     resident: the base and quality columns stay in device memory (codec.DeviceColumns, one store per input) and the blocks are
-    cut there; the same bytes.  Sorted order brings the base column to the host once, for the sort pre-pass; qualities never
-    come to the host.  stats then also has "columns" (DeviceColumns.info() per input once the last block is written, with
+    cut there; the same bytes.  Neither column comes to the host: sorted order sorts mate 1's store where it lies
+    (DeviceColumns.sort_order).  stats then also has "columns" (DeviceColumns.info() per input once the last block is written, with
     -- profile -- the gather kernel's "kernels")."""
     paired = text2_or_path2 is not None
     cols, parse_stats = [], []

@@ -395,7 +395,8 @@ def sorted_order_exact(rec: Records) -> List[np.ndarray]:
         first4 = _NT_ARR[rec.seq[:, :4]]
         bins = ((_CODE_NT[first4[:, 0]] * 4 + _CODE_NT[first4[:, 1]]) * 4 + _CODE_NT[first4[:, 2]]) * 4 + _CODE_NT[first4[:, 3]]
     else:
-        bins = np.array([sum(_CODE_NT[c] << (2 * (3 - k)) for k, c in enumerate(s[:4])) for s in rec.seq], dtype=np.int64)
+        # (a position past the end of the read lands on the line feed there: code 3, application.cpp:383-391)
+        bins = np.array([sum(_CODE_NT[c] << (2 * (3 - k)) for k, c in enumerate(s[:4].ljust(4, b"\n"))) for s in rec.seq], dtype=np.int64)
     h = _host_lib()
     out = []
     for b in range(NO_BINS):

@@ -385,7 +385,14 @@ int fqsx_fastq_kernel_times(fqsx_fastq *, double out[14]);
  *   the call returns with its stream drained.  Every record is checked on the device before anything is stored: an index
  *   that is no record of the store, or offsets that give a read another length than the store holds: FQSX_E_ARG; a range
  *   outside a buffer: FQSX_E_DEVICE.  A refused call leaves the buffers of the previous block as they were.
- * fqsx_cols_bases: the whole base column into out[bases] (the sort pre-pass bins on the host).
+ * fqsx_cols_bases: the whole base column into out[bases].
+ * fqsx_cols_sort_order: the read order of `fqs e -om s` for the records of the store, computed where they lie: the same
+ *   order_out / bin_start as fqsx_sort_order on the same reads.  No read is copied: the sort reads every record through its
+ *   device address, and what it allocates on the store (per record 8 address + 4 length + 1 bin + 8 permutations + 4 flags +
+ *   4 rank bytes, about 0.5 more for the tiles, 48 per chunk) is handed back before it returns -- also when an allocation
+ *   fails (FQSX_E_NOMEM; the call can be repeated).  Only the ranks and the bins come to the host, which replays std::sort
+ *   per bin as fqsx_sort_order does.  An empty store: bin_start all zero.  info_out (optional): [0] radix passes [1] scratch
+ *   bytes allocated at most during the call [2] records [3] 0.  A record outside its chunk: FQSX_E_DEVICE, order_out unwritten.
  * fqsx_cols_download: n_bytes of the store's device memory (a gathered block) to the host.
  * fqsx_cols_kernel_times (after fqsx_cols_set_profiling): out[0] / out[1] milliseconds and launches of the copying gather,
  *   out[2] / out[3] of the checking pass in front of it. */
@@ -397,6 +404,7 @@ int fqsx_fastq_columns_into(fqsx_fastq *, fqsx_cols *, uint8_t *ids, uint64_t *i
 int fqsx_cols_gather(fqsx_cols *a, fqsx_cols *b, const uint32_t *idx, uint32_t n, const uint64_t *h_off, const uint8_t **d_bases,
                      const uint8_t **d_quals, const uint64_t **d_off);
 int fqsx_cols_bases(fqsx_cols *, uint8_t *out);
+int fqsx_cols_sort_order(fqsx_cols *, uint32_t *order_out, uint32_t *bin_start /*[257]*/, uint64_t info_out[4]);
 int fqsx_cols_download(fqsx_cols *, const void *d_src, void *h_dst, uint64_t n_bytes);
 int fqsx_cols_set_profiling(fqsx_cols *, int enable);
 int fqsx_cols_kernel_times(fqsx_cols *, double out[4]);
