@@ -4,8 +4,11 @@
 // sizes the per-block buffers, and drives the kernel schedule of one reads block:
 //
 //   for seg in 0..S:  k_encode_segment  (T workgroups, one wavefront = one worker)
-//                     k_insert_phase    (3 T workgroups: (owner, mailbox kind), eight waves each: the keys go in window by window)
-//                     clear local tables
+//                     k_part_sender     (3 T workgroups: (mailbox kind, source), eight waves each: the source's list sorted by owner)
+//                     k_insert_phase    (3 T workgroups: (owner, mailbox kind), eight waves each: growth check, then the keys go in
+//                                        window by window; further workgroups clear the local tables)
+//   (decoding and the sharded drivers: k_part_count, k_part_scan, k_part_dstoff, k_part_scatter in place of k_part_sender, the
+//    demand read by the host in between, the local tables cleared by a launch of their own)
 //   k_finish_block
 //
 // which is the barrier structure of the reference worker loop (fqs/application.cpp:610-669)
@@ -45,34 +48,53 @@ extern "C" const char *fqsx_version(void) {
 // kernels.  The encode / decode kernels live in translation units of their own (fqsx_k_se.hip, fqsx_k_pe.hip,
 // fqsx_k_dec.hip; launchers in fqsx_kernels.h); here: the insert phase, the mailbox partition, growth, the block epilogue.
 // Deferred growth check (single-end encoding): the host queues the kernels of all phases of a block without reading
-// anything back.  The group-offset kernel of a phase sees the exact demand of the coming inserts; if a sub-table would
-// pass the load the host grows it at, it posts the phase (err[1] = segment + 1) instead, and every later kernel of the
-// queue -- the inserts of that phase included -- does nothing.  The host finds the word with the end-of-block transfer,
+// anything back.  The insert kernel of a phase (FQSX_PART_SENDER=0: the scatter kernel before it) sees the exact demand of the
+// coming inserts; if a sub-table would pass the load the host grows it at, it posts the phase (err[1] = segment + 1) instead,
+// and every later kernel of the queue -- the inserts of that phase included -- does nothing.  The host finds the word with the end-of-block transfer,
 // grows the tables and takes the block up again at that phase's inserts (block_recover).  err[0]: device error word.
 FQ_DEV bool phase_skip(const DevCfg &cfg) { return (cfg.err[0] | cfg.err[1]) != 0; }
 // grid = 3 * T: (owner, mailbox kind), FQSX_INS_THREADS threads each, plus -- single-end encoding -- workgroups that clear the
 // workers' local tables (ClearKmersToHT, dna.cpp:2475-2488: the insert phase does not touch them), which saves that launch
 // win: keys of a window of the s- / b-mer inserts (0: everything in order); maxmult: occurrences of one k-mer a window may hold
-FQ_KERNEL_NW(FQSX_INS_THREADS, FQSX_INS_WG_PER_CU * FQSX_INS_WAVES / 4) void k_insert_phase(DevCfg cfg, u64 nb_slots, u64 ns_slots, u32 win, u32 maxmult) {
+// by_source: layout of Mail.sorted (1: k_part_sender's, 0: grouped by owner)
+// seg1 != 0 (behind k_part_sender): segment + 1 -- the growth check of the deferred path is this kernel's.  Every inserting
+// workgroup applies the host's rule (block_segment: occupancy after the inserts <= tab_load_pct % of the capacity) to all 2 T s- and
+// b-mer sub-tables before it writes anything, from words no workgroup of this launch changes (DevCfg.demand: the entry totals
+// and the occupancies k_part_sender copied -- KTab.filled itself moves as the owners finish), so all of them find the same
+// answer without hearing of each other; if a sub-table would pass the load, the phase is posted and nothing is inserted.
+FQ_KERNEL_NW(FQSX_INS_THREADS, FQSX_INS_WG_PER_CU * FQSX_INS_WAVES / 4) void k_insert_phase(DevCfg cfg, u64 nb_slots, u64 ns_slots, u32 win, u32 maxmult, u32 by_source, u32 seg1) {
   FQ_SHARED InsWgShared sm;
+  const bool inserts = FQ_BLOCK < 3 * cfg.T;
+  u32 over = 0;
+  if (seg1 && inserts)
+    for (u32 i = FQ_TID; i < 2 * cfg.T; i += FQ_NTHREADS) {
+      const KTab &t = i < cfg.T ? cfg.g_s : cfg.g_b;
+      if (((u64)cfg.demand[2 * cfg.T + 1 + i] + cfg.demand[i]) * 100 > t.nb * FQSX_BKT * cfg.tab_load_pct) over = 2;
+    }
 #ifndef FQSX_EMU
   // (another workgroup of this launch may post an error meanwhile: one thread looks, so that the waves of a workgroup agree)
   if (FQ_TID == 0) sm.err = phase_skip(cfg) ? 1u : 0u;
   __syncthreads();
-  const bool skip = sm.err != 0;
+  if (over) atomicOr(&sm.err, over);
   __syncthreads();
-  if (skip) return;
+  const u32 stop = sm.err;
+  __syncthreads();
 #else
-  if (phase_skip(cfg)) return;
+  const u32 stop = (phase_skip(cfg) ? 1u : 0u) | over;
 #endif
-  if (FQ_BLOCK >= 3 * cfg.T) {
+  if (stop & 1) return;
+  if (stop) {   // (every inserting workgroup of the launch comes here, and stores the same words)
+    if (FQ_TID == 0) { cfg.demand[5 * cfg.T + 1] = seg1; cfg.err[1] = seg1; }
+    return;
+  }
+  if (!inserts) {
     const u64 stride = (u64)(FQ_NBLOCKS - 3 * cfg.T) * FQ_NTHREADS, first = (u64)(FQ_BLOCK - 3 * cfg.T) * FQ_NTHREADS + FQ_TID;
     for (u64 i = first; i < nb_slots; i += stride) cfg.l_b.slots[i] = 0;
     for (u64 i = first; i < ns_slots; i += stride) cfg.l_s.slots[i] = 0;
     for (u64 i = first; i < 2ull * cfg.T; i += stride) cfg.l_s.filled[i] = 0;   // l_s.filled and l_b.filled are adjacent
     return;
   }
-  insert_phase_body(cfg, &sm, FQ_BLOCK / 3, FQ_BLOCK % 3, win, maxmult);
+  insert_phase_body(cfg, &sm, FQ_BLOCK / 3, FQ_BLOCK % 3, win, maxmult, by_source != 0);
   // partitioned tables: this owner's slots are read by other GPUs in the next launch -- out of this XCD's L2 into HBM
   // before the kernel ends (the phase's collective then orders the end of this kernel before anybody's next look-up)
   if (cfg.sys_scope) fq_release_system();
@@ -188,6 +210,14 @@ FQ_KERNEL64 void k_part_scatter(DevCfg cfg, u32 seg1, u32 *demand) {
     if (blk == 0) part_dstoff_leader(cfg, kind, demand, seg1);
   }
   part_scatter_body(cfg, kind, blk, cursor, ld, gm, demand ? doff : nullptr);
+}
+// single-GPU encoding: the partition in one launch -- grid = 3 * T: (kind, source), every source sorts its own list by owner
+// (part_sender_body); k_insert_phase (by_source) reads the owners' keys from there and decides about growth
+static_assert(FQSX_SND_THREADS == 512, "k_part_sender's launch bound");
+FQ_KERNEL512 void k_part_sender(DevCfg cfg) {
+  FQ_SHARED SndShared sm;
+  if (phase_skip(cfg)) return;   // (nothing of this launch posts: the workgroup's waves agree)
+  part_sender_body(cfg, &sm, FQ_BLOCK / cfg.T, FQ_BLOCK % cfg.T);
 }
 // paired-end insert phase: per-owner demand, then the inserts
 // seg1 != 0 (paired-end encoding on one GPU): nothing is read back inside a block -- the kernel applies the host's growth
@@ -640,6 +670,7 @@ struct fqsx_dna : DevCtx {   // (a new fqsx_dna() starts with every field zero u
   u32 *d_plog_n;                      // counter of the p-mer transition log (DevCfg.p_log_n)
   u32 ins_win, ins_maxmult;           // k_insert_phase: keys per window of the s- / b-mer inserts (FQSX_INS_WINDOW; 0 = all in order, FQSX_INS_PARALLEL=0)
                                       // and the occurrences of one k-mer a window may hold before it goes in order (FQSX_INS_MAXMULT)
+  bool part_sender;                   // encoding on one GPU: k_part_sender instead of k_part_count / _scan / _scatter (FQSX_PART_SENDER=0: those)
   u64 vm_own_bytes;   // physical table memory held by this rank
 };
 
@@ -1154,12 +1185,14 @@ int clear_local_tables(fqsx_dna *c) {
   return FQSX_OK;
 }
 
-// insert phase and ClearKmersToHT in one launch (single-end encoding)
-int insert_and_clear(fqsx_dna *c) {
+// insert phase and ClearKmersToHT in one launch (encoding on one GPU)
+// seg1: segment + 1 if the kernel is to decide about growth itself (behind k_part_sender), else 0
+int insert_and_clear(fqsx_dna *c, u32 seg1) {
   const u64 words = (c->cur_need_lb + c->cur_need_ls) * c->T;
   const u64 per = 64ull * FQSX_INS_THREADS;   // words a clearing workgroup takes
   const u32 cgrid = (u32)std::min<u64>(2048, (words + per - 1) / per + 1);
-  LAUNCH(c, 1, k_insert_phase, 3 * c->T + cgrid, FQSX_INS_THREADS, c->cfg, c->cur_need_lb * c->T, c->cur_need_ls * c->T, c->ins_win, c->ins_maxmult);
+  LAUNCH(c, 1, k_insert_phase, 3 * c->T + cgrid, FQSX_INS_THREADS, c->cfg, c->cur_need_lb * c->T, c->cur_need_ls * c->T, c->ins_win, c->ins_maxmult,
+         c->part_sender ? 1u : 0u, c->part_sender ? seg1 : 0u);
   return FQSX_OK;
 }
 // growth decision from the demand words (k_part_dstoff): a sub-table is at most half full after the coming inserts
@@ -1183,10 +1216,17 @@ int block_recover(fqsx_dna *c, u32 seg) {
   const u32 T = c->T;
   int rc;
   if ((rc = d2h_sync(c, c->h_demand.data(), c->d_demand, (4 * T + 1) * sizeof(u32)))) return rc;
+  // paired-end: a phase k_insert_phase posted itself has its pair-table inserts behind it (block_segment's order); one that
+  // the bucket kernels posted has not
+  u32 pairs_done = 0;
+  if (c->paired && c->part_sender) {
+    if ((rc = d2h_sync(c, &pairs_done, c->d_demand + 5 * T + 1, sizeof(u32)))) return rc;
+    if (pairs_done && (rc = dzero(c, c->d_demand + 5 * T + 1, sizeof(u32)))) return rc;
+  }
   const u64 before = c->gs_cap + c->gb_cap + c->gpe_cap;
   if ((rc = grow_for_demand(c))) return rc;
   if ((rc = dzero(c, c->cfg.err + 1, sizeof(u32)))) return rc;
-  if (c->paired) {   // the pair table's demand again (the queued count stopped at the posted word), growth, then the phase's inserts
+  if (c->paired && !pairs_done) {   // the pair table's demand again (the queued count stopped at the posted word), growth, then the phase's inserts
     if ((rc = dzero(c, c->cfg.pe_bkt_n, T * sizeof(u32)))) return rc;   // (the per-owner counts of the stopped pass: the next phase counts from zero)
     LAUNCH(c, 2, k_pe_demand, T, 64, c->cfg, c->d_demand + 4 * T + 1, 0u);
     std::vector<u32> dem(T), fil(T);
@@ -1197,8 +1237,8 @@ int block_recover(fqsx_dna *c, u32 seg) {
     if (need * 2 > c->gpe_cap && (rc = grow_gpe(c, pow2_at_least(need * 2 + 2)))) return rc;
   }
   if (c->gs_cap + c->gb_cap + c->gpe_cap == before) { g_err = "phase " + std::to_string(seg) + " posted for growth, but no table needs it"; return FQSX_E_DEVICE; }
-  if (c->paired && (rc = pe_insert_and_clear(c))) return rc;
-  return insert_and_clear(c);
+  if (c->paired && !pairs_done && (rc = pe_insert_and_clear(c))) return rc;
+  return insert_and_clear(c, 0);   // (no second look at the demand: the tables have just been sized for it)
 }
 // paired-end: the pair-table inserts of a phase and the clearing of the workers' local pair tables
 int pe_clear_local(fqsx_dna *c) {
@@ -1225,11 +1265,14 @@ int block_segment(fqsx_dna *c, u32 seg) {
     if ((rc = launch_segment(c, decode, n_reads, (u32)S, seg))) return rc;
     // size the global tables for this phase's inserts (exact per-owner demand)
     const u32 part_grid = T * (cfg.mail[0].n_tiles + cfg.mail[1].n_tiles + cfg.mail[2].n_tiles);
-    LAUNCH(c, 2, k_part_count, part_grid, 64, cfg);
-    LAUNCH(c, 2, k_part_scan, 3 * T, 64, cfg);
+    if (!decode && c->part_sender) LAUNCH(c, 2, k_part_sender, 3 * T, FQSX_SND_THREADS, cfg);   // (every source for itself; k_insert_phase checks for growth)
+    else {
+      LAUNCH(c, 2, k_part_count, part_grid, 64, cfg);
+      LAUNCH(c, 2, k_part_scan, 3 * T, 64, cfg);
+      if (!decode) LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, seg + 1, c->d_demand);   // (FQSX_PART_SENDER=0; group offsets, demand words and growth check included)
+    }
     if (!decode) {
       // encoding: nothing is read back inside a block -- the growth checks are the device's (phase_skip)
-      LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, seg + 1, c->d_demand);   // (group offsets, demand words and growth check included)
       if (c->paired) {   // pair table: triples grouped by owner (count, offsets + growth check, scatter), then every owner's own group
         const u32 bgrid = FQ_GRID((u32)std::min<u64>(1024, ((u64)T * cfg.pe_cap + 255) / 256));
         LAUNCH(c, 2, k_pe_bucket_count, bgrid, 256, cfg);
@@ -1238,7 +1281,7 @@ int block_segment(fqsx_dna *c, u32 seg) {
         LAUNCH(c, 2, k_pe_insert_buckets, T, 64, cfg);
         if ((rc = pe_clear_local(c))) return rc;
       }
-      return insert_and_clear(c);
+      return insert_and_clear(c, seg + 1);
     }
     LAUNCH(c, 2, k_part_dstoff, 3, 64, cfg, c->d_demand, 0u);
     // the demand travels to the host while the scatter (which does not depend on the growth decision) runs
@@ -1259,7 +1302,7 @@ int block_segment(fqsx_dna *c, u32 seg) {
       if (need * 2 > c->gpe_cap && (rc = grow_gpe(c, pow2_at_least(need * 2 + 2)))) return rc;
       if ((rc = pe_insert_and_clear(c))) return rc;
     }
-    LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult);
+    LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult, 0u, 0u);
     if ((rc = clear_local_tables(c))) return rc;
   }
   return FQSX_OK;
@@ -1358,6 +1401,8 @@ int create_impl(fqsx_dna *c, const u8 *h) {
   if (const char *e = getenv("FQSX_INS_WINDOW")) c->ins_win = (u32)std::min<u64>(FQSX_WIN_MAX, std::max<u64>(1, strtoull(e, nullptr, 10)));
   if (const char *e = getenv("FQSX_INS_MAXMULT")) c->ins_maxmult = (u32)std::min<u64>(FQSX_WIN_MULT_MAX, std::max<u64>(1, strtoull(e, nullptr, 10)));
   if (const char *e = getenv("FQSX_INS_PARALLEL")) if (atoi(e) == 0) c->ins_win = 0;
+  c->part_sender = true;
+  if (const char *e = getenv("FQSX_PART_SENDER")) c->part_sender = atoi(e) != 0;
 #ifdef FQSX_EMU
   c->ins_win = 0;   // (one lane: the in-order routine)
 #endif
@@ -1427,6 +1472,8 @@ int create_impl(fqsx_dna *c, const u8 *h) {
     cfg.mail[k].dst_tot = (u32 *)p;
     if ((rc = dalloc(c, &p, ((u64)T + 1) * sizeof(u32), true))) return rc;
     cfg.mail[k].dst_off = (u32 *)p;
+    if ((rc = dalloc(c, &p, ((u64)T + 1) * T * sizeof(u32), true))) return rc;
+    cfg.mail[k].soff = (u32 *)p;
     if ((rc = mail_alloc(c, k, FQSX_TILE))) return rc;
   }
   c->paired = cfg.mode >= 2;
@@ -1460,7 +1507,7 @@ int create_impl(fqsx_dna *c, const u8 *h) {
   cfg.trace = (u64 *)p;
 #endif
   if ((rc = dalloc(c, &p, (5 * (u64)T + 2) * sizeof(u32), true))) return rc;   // [0 .. 4T]: k-mer tables (k_part_dstoff); [4T+1 ..): pair table
-  c->d_demand = (u32 *)p;
+  c->d_demand = cfg.demand = (u32 *)p;   // (words: DevCfg.demand)
   if ((rc = dalloc(c, &p, ((u64)T + 64) * sizeof(u64), true))) return rc;
   c->d_lens = (u64 *)p;
   if ((rc = dalloc(c, &p, (2 * (u64)T + 2) * sizeof(u64), true))) return rc;
@@ -1687,7 +1734,7 @@ int fqsx_shard_insert(fqsx_dna *c, uint64_t need_s, uint64_t need_b, uint64_t *c
   if (tab_over(c, need_s, c->gs_cap) && (rc = grow_global(c, cfg.g_s, c->gs_cap, tab_new_cap(c, need_s)))) return rc;
   if (tab_over(c, need_b, c->gb_cap) && (rc = grow_global(c, cfg.g_b, c->gb_cap, tab_new_cap(c, need_b)))) return rc;
   if ((rc = d2h_sync(c, c->siv_before, cfg.siv_stats, 2 * sizeof(u64)))) return rc;
-  LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult);
+  LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult, 0u, 0u);
   u64 after[2];
   if ((rc = d2h_sync(c, after, cfg.siv_stats, 2 * sizeof(u64)))) return rc;
   siv_delta[0] = after[0] - c->siv_before[0];
@@ -1846,7 +1893,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
     if (M[MAIL_P]) LAUNCH(c, 2, k_zero_words, (u32)std::min<u64>(REHASH_GRID, (M[MAIL_P] + 255) / 256), 256, cfg.p_log, M[MAIL_P], 0u);
     if ((rc = dzero(c, c->d_plog_n, sizeof(u32)))) return rc;
   }
-  LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult);
+  LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult, 0u, 0u);
   // ---- one all-gather
   for (u32 k = 0; k < 3; ++k)
     if (n_items[(u64)k * G + me] && !(k == MAIL_P && cfg.siv_part)) LAUNCH(c, 2, k_shard_collect, REHASH_GRID, 256, cfg, k, c->d_items + off_k[k]);

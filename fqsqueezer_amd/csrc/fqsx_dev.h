@@ -808,20 +808,46 @@ FQ_DEV void insert_batch(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, cons
 template <class SM>
 FQ_DEV void insert_batch_k(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, u64 mykey, u32 n, u32 rng, const Cinc &ci,
                            u64 &nslots, u32 &err);
-template <class SM>
-FQ_DEV void insert_keys(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, const u64 *keys, u32 n, u32 rng, const Cinc &ci,
+// An owner's keys of one mailbox kind in (source, push) order, whichever layout Mail.sorted has (fqsx_layout.h); what
+// the insert phase reads its keys through (insert_keys, insert_windows, the p-mer loop), like an array.
+//   grouped:    p = the owner's group, pre = null
+//   by source:  p = Mail.sorted; key i is entry i - pre[s] of source s's run for this owner, s the last source with pre[s] <= i
+//               (binary search in LDS, as shard_merge_body does; sources without entries share a prefix value with their successor)
+struct MailKeys {
+  const u64 *p;
+  const u32 *pre;   // LDS[T + 1]: entries for this owner from the sources before s; [T] = all of them
+  const u32 *at;    // LDS[T]: where source s's run for this owner starts in its stretch of p
+  u32 T, cap, first;   // first: key 0 of this view (keys_from)
+};
+FQ_DEV u64 key_at(const MailKeys &k, u32 i) {
+  i += k.first;
+  if (!k.pre) return k.p[i];
+  u32 lo = 0, hi = k.T;
+  while (hi - lo > 1) {
+    const u32 mid = (lo + hi) >> 1;
+    if (k.pre[mid] <= i) lo = mid; else hi = mid;
+  }
+  return k.p[(u64)lo * k.cap + k.at[lo] + (i - k.pre[lo])];
+}
+FQ_DEV MailKeys keys_from(MailKeys k, u32 o) { k.first += o; return k; }
+FQ_DEV u64 key_at(const u64 *k, u32 i) { return k[i]; }
+FQ_DEV const u64 *keys_from(const u64 *k, u32 o) { return k + o; }
+
+// K: the keys -- const u64 * (a plain list), or MailKeys
+template <class SM, class K>
+FQ_DEV void insert_keys(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, const K keys, u32 n, u32 rng, const Cinc &ci,
                         u64 &nslots, u32 &err) {
 #if FQ_WAVE > 1
   // the keys of the next batch are fetched while the current one is applied (the list is read-only here)
   // ... and the home slots of the next batch are touched one batch ahead, so that the ordered walk of a batch finds
   // its cache lines (and address translations) in L2 instead of paying the HBM round trip inside the serial chain
   const u64 *s = t.slots + (u64)sub * t.stride;
-  u64 nextk = FQ_LANE < n ? keys[FQ_LANE] : 0;
+  u64 nextk = FQ_LANE < n ? key_at(keys, FQ_LANE) : 0;
   for (u32 o = 0; o < n && !err; o += FQ_WAVE) {
     const u64 k = nextk;
     u64 touch = 0;
     if (o + FQ_WAVE + FQ_LANE < n) {
-      nextk = keys[o + FQ_WAVE + FQ_LANE];
+      nextk = key_at(keys, o + FQ_WAVE + FQ_LANE);
       const TabHome th = tab_home(t, nextk >> (64 - 2 * t.k));
       touch = touch_load(&s[(u64)th.a * FQSX_BKT]) ^ touch_load(&s[(u64)th.b * FQSX_BKT]);
     }
@@ -829,7 +855,7 @@ FQ_DEV void insert_keys(const DevCfg &cfg, SM *sm, const KTab &t, u32 sub, const
     keep_live(touch);
   }
 #else
-  for (u32 j = 0; j < n && !err; ++j) insert_batch(cfg, sm, t, sub, keys + j, 1, rng, ci, nslots, err);
+  for (u32 j = 0; j < n && !err; ++j) insert_batch_k(cfg, sm, t, sub, key_at(keys, j), 1, rng, ci, nslots, err);
 #endif
 }
 // Local-table inserts (ht_*_local->insert, dna.cpp:826,839,861,872): every b-/s-mer a worker pushes to its
@@ -4551,6 +4577,7 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
   mt_copy((u64 *)&ws->mt[0][0], (const u64 *)&sm->mt[0][0]);
   for (u32 g = FQ_LANE; g < 4; g += FQ_WAVE) ws->mt_idx[g] = sm->mt_idx[g];
   for (u32 k = 0; k < 3; ++k) cfg.mail[k].n[tid] = w.mn[k];
+  cfg.demand[tid] = cfg.demand[cfg.T + tid] = 0;   // owner tid's s- and b-mer entries of the coming insert phase: k_part_sender counts from zero
   if (paired) cfg.pe_n[tid] = w.pe_n;
   if (w.err) *cfg.err = w.err;
 }
@@ -4767,6 +4794,81 @@ FQ_DEV void part_scatter_body(const DevCfg &cfg, u32 kind, u32 blk, u32 *cursor 
   }
 }
 
+// ---- the same order without a GPU-wide partition: every source sorts its own list ------------
+// Source s's list of mailbox `kind`, stably by owner group, into its own stretch sorted[s * cap ..) -- one workgroup of
+// FQSX_SND_WAVES waves, nothing read that another workgroup of the launch writes.  Each wave takes a contiguous slice of
+// the list: owner histogram per wave, one scan over (owner, wave), then the slice again in rounds of a wave's worth of
+// entries (ranks inside a round from per-group lane masks, as part_scatter_body).  The source's offsets go to its column
+// of Mail.soff; s- and b-mers: its counts are added to the owners' entry totals, and the occupancy of sub-table s is
+// copied next to them (DevCfg.demand: what k_insert_phase decides about growth from -- the tables do not change here).
+#define FQSX_SND_WAVES 8u
+#define FQSX_SND_THREADS (FQSX_SND_WAVES * 64u)
+struct SndShared {
+  u32 cur[FQSX_SND_WAVES][256];   // entries of wave w's slice per group; after the scan: where its next entry of the group goes
+  u64 gm[FQSX_SND_WAVES][256];    // a round's lanes per group
+};
+FQ_DEV void part_sender_body(const DevCfg &cfg, SndShared *sm, u32 kind, u32 s) {
+  const Mail &m = cfg.mail[kind];
+  const u32 T = cfg.T, n = m.n[s] < m.cap ? m.n[s] : m.cap, wave = FQ_WAVE_ID, n_waves = FQ_NTHREADS / FQ_WAVE;
+  const u64 *list = m.list + (u64)s * m.cap;
+  u64 *dst = m.sorted + (u64)s * m.cap;
+  const u32 per = ((n + n_waves - 1) / n_waves + FQ_WAVE - 1) / FQ_WAVE * FQ_WAVE;   // entries of a slice: whole rounds
+  const u32 lo = wave * per < n ? wave * per : n, hi = lo + per < n ? lo + per : n;
+  for (u32 d = FQ_TID; d < n_waves * 256; d += FQ_NTHREADS) { sm->cur[d >> 8][d & 255] = 0; sm->gm[d >> 8][d & 255] = 0; }
+  FQ_WG_BARRIER();
+  for (u32 e = lo + FQ_LANE; e < hi; e += FQ_WAVE) lds_inc32(&sm->cur[wave][mail_group(cfg, kind, list[e])]);
+  FQ_WG_BARRIER();
+  if (wave == 0) {   // exclusive scan over (owner, wave); the source's totals per owner and their offsets
+    u32 *tot = kind == MAIL_P ? nullptr : cfg.demand + (kind == MAIL_S ? 0 : T);
+    u32 run = 0;
+    for (u32 base = 0; base < T; base += FQ_WAVE) {
+      const u32 d = base + FQ_LANE;
+      u32 v = 0;
+      if (d < T)
+        for (u32 w = 0; w < n_waves; ++w) { const u32 c = sm->cur[w][d]; sm->cur[w][d] = v; v += c; }
+      const u32 ex = wave_excl_scan32(v) + run;
+      if (d < T) {
+        for (u32 w = 0; w < n_waves; ++w) sm->cur[w][d] += ex;
+        m.soff[(u64)d * T + s] = ex;
+        if (tot && v) atomic_add32(&tot[d], v);   // (integer adds: the sum does not depend on their order)
+      }
+      run += wave_sum32(v);
+    }
+    if (FQ_LANE == 0) {
+      m.soff[(u64)T * T + s] = run;
+      if (tot) cfg.demand[2 * T + 1 + (kind == MAIL_S ? 0 : T) + s] = (kind == MAIL_S ? cfg.g_s : cfg.g_b).filled[s];
+    }
+  }
+  FQ_WG_BARRIER();
+  u32 *cur = sm->cur[wave];
+  u64 *gm = sm->gm[wave];
+  for (u32 base = lo; base < hi; base += FQ_WAVE) {
+    const u32 e = base + FQ_LANE;
+    u64 x = 0;
+    u32 d = 0;
+    if (e < hi) {
+      x = list[e];
+      d = mail_group(cfg, kind, x);
+    }
+#if FQ_WAVE > 1
+    if (e < hi) lds_or64(&gm[d], 1ull << FQ_LANE);
+    FQ_SYNC();
+    const u64 mine = e < hi ? gm[d] : 0;
+    const u32 rank = popc64(mine & ((1ull << FQ_LANE) - 1ull));
+    const bool last = ((mine >> FQ_LANE) >> 1) == 0;   // last entry of its group in the round: advances the cursor, clears the mask
+    const u32 at = e < hi ? cur[d] : 0;
+    FQ_SYNC();
+    if (e < hi) {
+      dst[at + rank] = x;
+      if (last) { cur[d] = at + rank + 1; gm[d] = 0; }
+    }
+    FQ_SYNC();
+#else
+    if (e < hi) dst[cur[d]++] = x;
+#endif
+  }
+}
+
 // the count index of the p-mer vector follows a field that went from value `from` to value `to` (DevCfg.siv_idx)
 FQ_DEV void siv_idx_move(const DevCfg &cfg, u64 idx, u32 from, u32 to) {
   u32 *e = cfg.siv_idx + 4 * (idx >> FQSX_SIV_BLK_LOG);
@@ -4811,7 +4913,7 @@ FQ_DEV void siv_idx_move(const DevCfg &cfg, u64 idx, u32 from, u32 to) {
 #define FQSX_WIN_MAX (FQSX_WIN_PER * FQSX_INS_THREADS)      /* keys of a window (FQSX_INS_WINDOW: fewer) */
 #define FQSX_WIN_HASH (2u * FQSX_WIN_MAX)
 #define FQSX_WIN_MULT_MAX 32u                                /* upper limit of the multiplicity cap (FQSX_INS_MAXMULT) */
-// LDS of k_insert_phase: 36 KB at 1 024 keys a window; with the registers the launch bound leaves (FQSX_INS_WG_PER_CU) two
+// LDS of k_insert_phase: 38 KB at 1 024 keys a window; with the registers the launch bound leaves (FQSX_INS_WG_PER_CU) two
 // workgroups share a CU, so that four files on CU partitions (192 workgroups on 64 CUs) do not take turns
 struct InsWgShared {
   u32 mt[2][624];                  // the owner's stream of this kind (RNG_B / RNG_S)
@@ -4827,6 +4929,8 @@ struct InsWgShared {
   u32 filled;                      // occupied slots of the sub-table
   u32 err;
   u64 acc[2];                      // p-mers: fields filled / updated, summed over the waves
+  u32 src_pre[FQSX_MAX_T + 2];     // mailbox sorted by source: the owner's column of Mail.soff as MailKeys wants it (pre, at)
+  u32 src_at[FQSX_MAX_T + 1];
 };
 static_assert(RNG_B == 0 && RNG_S == 1, "InsWgShared.mt holds the streams of the global tables only");
 #ifndef FQSX_EMU
@@ -4842,7 +4946,7 @@ FQ_DEVN u64 tab_claim_new(const KTab t, u64 *s, u64 v) {
 
 // keys[0 .. n) of sub-table `sub`, window by window (see above).  Called by every thread of the workgroup; err, n_par and
 // n_fb (windows applied in parallel / in order) come out workgroup-uniform, nslots is this thread's own count.
-FQ_DEV void insert_windows(const DevCfg &cfg, InsWgShared *sm, const KTab &t, u32 sub, const u64 *keys, u32 n, u32 rng, const Cinc &ci,
+FQ_DEV void insert_windows(const DevCfg &cfg, InsWgShared *sm, const KTab &t, u32 sub, const MailKeys &keys, u32 n, u32 rng, const Cinc &ci,
                            u32 win, u32 maxmult, u64 &nslots, u32 &err, u32 &n_par, u32 &n_fb) {
   u64 *s = t.slots + (u64)sub * t.stride;
   const u32 cm = (1u << t.cbits) - 1u;
@@ -4869,7 +4973,7 @@ FQ_DEV void insert_windows(const DevCfg &cfg, InsWgShared *sm, const KTab &t, u3
       act[j] = i < wn;
       v[j] = 0; pos[j] = ~0ull; item[j] = 0; he[j] = 0; rk[j] = ~0u; drw[j] = false;
       if (act[j]) {
-        v[j] = keys[wo + i] >> (64 - 2 * t.k);
+        v[j] = key_at(keys, wo + i) >> (64 - 2 * t.k);
         const TabLoc L = tab_locate_live(t, s, v[j]);   // (absent: item == 0; where the key goes is the claim's business)
         pos[j] = L.pos; item[j] = L.item; nslots += L.ns;
         u32 h = (u32)((v[j] * 0x9E3779B97F4A7C15ull) >> 40) & (hs - 1);
@@ -4919,7 +5023,7 @@ FQ_DEV void insert_windows(const DevCfg &cfg, InsWgShared *sm, const KTab &t, u3
       if (wave == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // (its look-ups read through this CU's L1: drop lines older than the claims)
         u32 e1 = 0;
-        insert_keys(cfg, sm, t, sub, keys + wo, wn, rng, ci, nslots, e1);
+        insert_keys(cfg, sm, t, sub, keys_from(keys, wo), wn, rng, ci, nslots, e1);
         FQ_SYNC_MEM();
         if (lane == 0) { sm->filled = t.filled[sub]; if (e1) sm->err = e1; }
       }
@@ -4994,15 +5098,36 @@ FQ_DEV void insert_windows(const DevCfg &cfg, InsWgShared *sm, const KTab &t, u3
 #endif   // !FQSX_EMU
 
 template <class SM>
-FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind, u32 win, u32 maxmult) {
+FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind, u32 win, u32 maxmult, bool by_source) {
   WState *ws = cfg.ws + tid;
   const Mail &m = cfg.mail[kind];
-  const u32 lo = m.dst_off[tid], hi = m.dst_off[tid + 1];
+  MailKeys keys = {m.sorted, nullptr, nullptr, cfg.T, m.cap, 0};
+  u32 n;             // this owner's keys: keys[0 .. n)
+  if (by_source) {   // the owner's column of the sources' offsets (k_part_sender), its prefix over the sources
+    if (FQ_WAVE_ID == 0) {
+      const u32 T = cfg.T;
+      u32 run = 0;
+      for (u32 base = 0; base < T; base += FQ_WAVE) {
+        const u32 s = base + FQ_LANE;
+        const u32 a = s < T ? m.soff[(u64)tid * T + s] : 0, b = s < T ? m.soff[(u64)(tid + 1) * T + s] : 0;
+        const u32 ex = wave_excl_scan32(b - a) + run;
+        if (s < T) { sm->src_at[s] = a; sm->src_pre[s] = ex; }
+        run += wave_sum32(b - a);
+      }
+      if (FQ_LANE == 0) sm->src_pre[T] = run;
+    }
+    FQ_WG_BARRIER();
+    keys.pre = sm->src_pre; keys.at = sm->src_at;
+    n = sm->src_pre[cfg.T];
+  } else {
+    keys.p = m.sorted + m.dst_off[tid];
+    n = m.dst_off[tid + 1] - m.dst_off[tid];
+  }
   if (kind == MAIL_P) {
     // p-mers: saturating 2-bit increments; order-free, so all threads update concurrently with CAS
     u64 nf = 0, nu = 0;
-    for (u32 e = lo + FQ_TID; e < hi; e += FQ_NTHREADS) {
-      u64 idx = m.sorted[e];
+    for (u32 e = FQ_TID; e < n; e += FQ_NTHREADS) {
+      u64 idx = key_at(keys, e);
       u64 *wp = cfg.siv + (idx >> 5);
       u32 sh = 2 * (u32)(idx & 31);
       u64 old = *wp;
@@ -5045,7 +5170,7 @@ FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind, u32 
       cfg.siv_stats[0] += nu + ws->hidden_updates;
 #endif
       ws->hidden_updates = 0;
-      ws->stat[ST_SIV_WORDS] += hi - lo;
+      ws->stat[ST_SIV_WORDS] += n;
     }
     return;
   }
@@ -5058,10 +5183,10 @@ FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind, u32 
   if (FQ_TID == 0) { sm->mt_idx[rng] = ws->mt_idx[rng]; sm->err = 0; }
   FQ_WG_BARRIER();
 #ifndef FQSX_EMU
-  if (win && t.two) insert_windows(cfg, sm, t, tid, m.sorted + lo, hi - lo, rng, ci, win, maxmult, n_slots, err, n_par, n_fb);
+  if (win && t.two) insert_windows(cfg, sm, t, tid, keys, n, rng, ci, win, maxmult, n_slots, err, n_par, n_fb);
   else
 #endif
-  if (FQ_WAVE_ID == 0) insert_keys(cfg, sm, t, tid, m.sorted + lo, hi - lo, rng, ci, n_slots, err);   // everything in order: one wave
+  if (FQ_WAVE_ID == 0) insert_keys(cfg, sm, t, tid, keys, n, rng, ci, n_slots, err);   // everything in order: one wave
   (void)win; (void)maxmult;
   FQ_WG_BARRIER();
   for (u32 i = FQ_TID; i < 624; i += FQ_NTHREADS) ws->mt[rng][i] = sm->mt[rng][i];
@@ -5077,11 +5202,11 @@ FQ_DEV void insert_phase_body(const DevCfg &cfg, SM *sm, u32 tid, u32 kind, u32 
   if (FQ_TID == 0) {
     ws->mt_idx[rng] = sm->mt_idx[rng];
 #ifndef FQSX_EMU
-    atomicAdd((unsigned long long *)&ws->stat[ST_GINS], (unsigned long long)(hi - lo));
+    atomicAdd((unsigned long long *)&ws->stat[ST_GINS], (unsigned long long)n);
     if (n_par) atomicAdd((unsigned long long *)&ws->stat[ST_INS_WIN], (unsigned long long)n_par);
     if (n_fb) atomicAdd((unsigned long long *)&ws->stat[ST_INS_WIN_ORDER], (unsigned long long)n_fb);
 #else
-    ws->stat[ST_GINS] += hi - lo;
+    ws->stat[ST_GINS] += n;
 #endif
   }
 }

@@ -65,13 +65,19 @@ struct CtxSlot {
 };
 
 // Mailbox of one kind (p-, s- or b-mers).  Sources append to a flat per-source list in push
-// order; a GPU-wide stable partition (k_part_*) then groups the entries by owner, keeping
-// (source, push) order inside each group -- the order InsertKmersToHT drains its column in.
+// order; the insert phase applies an owner's entries in (source, push) order -- the order InsertKmersToHT drains its
+// column in.  `sorted` holds the phase's entries in one of two layouts:
+//   by source  (single-GPU encoding, k_part_sender): every source sorts its own list stably by owner into its own
+//              stretch sorted[s * cap ..) and leaves the offsets in `soff`; owner o walks the sources in ascending order
+//              (MailKeys, fqsx_dev.h).  No source needs to know anything of another one: one launch.
+//   grouped    (decoding, the sharded drivers: k_part_count / _scan / _dstoff / _scatter): a GPU-wide stable partition,
+//              one contiguous group per owner at dst_off[o].
 #define FQSX_TILE 2048u
 struct Mail {
   u64 *list;       // [T][cap]     entries in push order per source
   u32 *n;          // [T]          entries per source (written at the end of an encode launch)
-  u64 *sorted;     // [T*cap]      entries grouped by owner
+  u64 *sorted;     // [T*cap]      the entries by source and owner, or grouped by owner (see above)
+  u32 *soff;       // [T+1][T]     by source: soff[o * T + s] = where source s's entries for owner o start in its stretch ([T]: their end)
   u32 *tile_hist;  // [T*n_tiles][T] per-tile owner histogram, exclusive offsets after the scan
   u32 *dst_tot;    // [T]          entries per owner
   u32 *dst_off;    // [T+1]        start of each owner's group in `sorted`
@@ -228,6 +234,10 @@ struct DevCfg {
   const u8 *vmap;              // [256] owner -> position of its group in the partitioned mailbox: identity, or rank-major
                                // (all owners of rank 0, then rank 1, ...) so that what goes to one rank is contiguous
   u32 *shard_cnt;              // [3][T][T] entries source s pushed for owner o in this phase (own sources; else 0)
+  u32 *demand;                 // the growth decision's words: [0 .. 2T) s- / b-mer entries per owner of the coming insert phase, [2T] error
+                               // word, [2T+1 .. 4T+1) the sub-tables' occupancies before it, [4T+1 .. 5T+1) pair table, [5T+1] segment + 1
+                               // of a phase k_insert_phase itself posted.  An encode launch ends with owner tid's two entry counts zero;
+                               // k_part_sender adds the sources' rows to them.
 };
 
 // Protocol test switches (DevCfg.dbg).  Which wave settles what depends on wave timing in the product run, so the
