@@ -65,6 +65,7 @@ _ABI = {
     "fqsx_idg_create": (_INT, [_HDR, _INT, _OUT]),
     "fqsx_idg_destroy": (None, [_P]),
     "fqsx_idg_encode_block": (_INT, _ID_ENCODE),
+    "fqsx_idg_encode_block_dev": (_INT, [_P, _P, _P, _P, _U32, _INT, _OUT, _U64S]),
     "fqsx_idg_decode_block": (_INT, _ID_DECODE),
     "fqsx_idg_decode_block_dev": (_INT, [_P, _IN, _P, _U32, _INT, _OUT, _OUT, _U64S]),
     "fqsx_idg_error_kind": (_INT, [_P]),
@@ -72,6 +73,7 @@ _ABI = {
     "fqsx_idg_state": (_INT, [_P, _P]),
     "fqsx_idg_set_profiling": (_INT, [_P, _INT]),
     "fqsx_idg_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_idg_separator_times": (_INT, [_P, _MS]),
     "fqsx_sort_order": (_INT, [_P, _P, _U32, _INT, _P, _P]),
     "fqsx_sort_order_batched": (_INT, [_P, _P, _U32, _INT, _U64, _P, _P, C.POINTER(_U32)]),
     "fqsx_fastq_create": (_INT, [_INT, _U64, _OUT]),
@@ -91,6 +93,11 @@ _ABI = {
     "fqsx_cols_download": (_INT, [_P, _P, _P, _U64]),
     "fqsx_cols_set_profiling": (_INT, [_P, _INT]),
     "fqsx_cols_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_cols_keep_ids": (_INT, [_P]),
+    "fqsx_cols_gather_ids": (_INT, [_P, _P, _P, _U32, _P, _OUT, _OUT]),
+    "fqsx_cols_id_info": (_INT, [_P, _U64S]),
+    "fqsx_cols_id_survey": (_INT, [_P, _U64S]),
+    "fqsx_cols_id_kernel_times": (_INT, [_P, _MS]),
     "fqsx_fqtext_create": (_INT, [_INT, _OUT]),
     "fqsx_fqtext_destroy": (None, [_P]),
     "fqsx_fqtext_block": (_INT, [_P, _U32, _INT, _P, _P, _INT, _U64, _P, _P, _INT, _P, _U64S]),
@@ -332,12 +339,27 @@ class IdCodec(_Handle):
             e.staging = self._gpu and rc == -5 and self._lib.fqsx_idg_error_kind(self._h) in (5, 6)
         return e
 
+    @property
+    def on_device(self) -> bool:
+        """the GPU flavour"""
+        return self._gpu
+
     def encode_block(self, ids: np.ndarray, id_off: np.ndarray, paired: bool = False) -> List[bytes]:
         ids = np.ascontiguousarray(ids, dtype=np.uint8)
         id_off = np.ascontiguousarray(id_off, dtype=np.uint64)
         self._call("fqsx_idg_encode_block" if self._gpu else "fqsx_id_encode_block", self._h, ids.ctypes.data, id_off.ctypes.data,
                    len(id_off) - 1, int(paired), self._streams, self._lens,
                    text=None if self._gpu else lambda rc: self._host_refusal(ids, id_off, paired))
+        return self._collect()
+
+    def encode_block_dev(self, d_ids: int, d_off: int, id_off: np.ndarray, paired: bool = False) -> List[bytes]:
+        """GPU flavour only: encode_block for a block in device memory (DeviceColumns.ids_dev: the device pointers of its id lines
+        and of their offsets, and the offsets on the host).  The same streams, errors and `staging` as encode_block's."""
+        if not self._gpu:
+            raise FqsxError("encode_block_dev: the host id coder reads host arrays")
+        id_off = np.ascontiguousarray(id_off, dtype=np.uint64)
+        self._call("fqsx_idg_encode_block_dev", self._h, d_ids or None, d_off or None, id_off.ctypes.data, len(id_off) - 1, int(paired),
+                   self._streams, self._lens)
         return self._collect()
 
     def _host_refusal(self, ids: np.ndarray, id_off: np.ndarray, paired: bool) -> str:
@@ -411,7 +433,9 @@ class IdCodec(_Handle):
     def kernel_times(self) -> dict:
         a = (C.c_double * 2)()
         self._lib.fqsx_idg_kernel_times(self._h, a)
-        return {"ms": a[0], "launches": int(a[1])}
+        b = (C.c_double * 2)()
+        self._lib.fqsx_idg_separator_times(self._h, b)
+        return {"ms": a[0], "launches": int(a[1]), "separators_ms": b[0], "separators_launches": int(b[1])}
 
 
 class IdFallback:
@@ -529,12 +553,14 @@ class FastqParser(_Handle):
 
     def columns_into(self, info: dict, store: "DeviceColumns"):
         """(ids, id_off, read_off, plus_len) of the chunk indexed last; its base and quality columns are appended to `store`
-        without leaving the device.  FqsxError, the store unchanged: a record whose quality line differs in length from its base line."""
+        without leaving the device -- its id lines too if the store keeps ids (`ids` is then empty).  FqsxError, the store unchanged:
+        a record whose quality line differs in length from its base line."""
         n = info["records"]
-        ids = np.empty(info["id_bytes"], dtype=np.uint8)
+        ids = np.empty(0 if store.keeps_ids else info["id_bytes"], dtype=np.uint8)   # (a store that keeps ids: no id byte comes to the host)
         id_off, read_off = (np.zeros(n + 1, dtype=np.uint64) for _ in range(2))
         plus_len = np.empty(n, dtype=np.uint32)
-        self._call("fqsx_fastq_columns_into", self._h, store._h, ids.ctypes.data, id_off.ctypes.data, read_off.ctypes.data, plus_len.ctypes.data)
+        self._call("fqsx_fastq_columns_into", self._h, store._h, None if store.keeps_ids else ids.ctypes.data, id_off.ctypes.data,
+                   read_off.ctypes.data, plus_len.ctypes.data)
         return ids, id_off, read_off, plus_len
 
     def set_profiling(self, on: bool) -> None:
@@ -606,16 +632,33 @@ class DeviceBlock:
         self.bases, self.quals, self.d_off, self.off = bases, quals, d_off, off
 
 
+class DeviceIds:
+    """The id lines of a container block in device memory (DeviceColumns.ids_dev), the counterpart of DeviceBlock: device pointers
+    of the lines and of their offsets, valid until the next id block is cut from the same columns, and the offsets on the host."""
+    __slots__ = ("ids", "d_off", "off")
+
+    def __init__(self, ids: int, d_off: int, off: np.ndarray):
+        self.ids, self.d_off, self.off = ids, d_off, off
+
+
 class DeviceColumns(_Handle):
     """The records of a FASTQ file with the base and the quality column resident in device memory (fqsx_cols_*), filled chunk by
     chunk by FastqParser.columns_into.  ids, id_off, read_off and plus_len are host arrays as in hostpipe.Columns, so that
     record_sizes(), ids_of / ids_of_pe and the block formation work as they do there; block_dev / block_pe_dev cut a block on
-    the device where Columns.block / quals_of (block_pe / quals_of_pe) gather on the host."""
+    the device where Columns.block / quals_of (block_pe / quals_of_pe) gather on the host.
+    After keep_ids() the id column is resident too: `ids` stays empty (id_off as ever), ids_dev / ids_pe_dev cut a block's id
+    lines on the device, and ids_of / ids_of_pe are that block downloaded."""
+    keeps_ids = False
 
     def __init__(self, device: int = 0, lib_path: Optional[str] = None):
         from . import hostpipe as hp
         self._open(lib_path, "fqsx_cols_create", "fqsx_cols_destroy", device)
         self._set_host(hp.Columns.from_chunks([]))
+
+    def keep_ids(self) -> None:
+        """Before the first chunk: the store keeps the id column too (fqsx_cols_keep_ids).  FqsxError afterwards."""
+        self._call("fqsx_cols_keep_ids", self._h)
+        self.keeps_ids = True
 
     def _set_host(self, host) -> None:
         self._host = host
@@ -634,18 +677,53 @@ class DeviceColumns(_Handle):
         return self._host.record_sizes()
 
     def ids_of(self, idx):
-        return self._host.ids_of(idx)
+        return self._ids_to_host(self.ids_dev(idx)) if self.keeps_ids else self._host.ids_of(idx)
 
     def ids_of_pe(self, mate2: "DeviceColumns", idx):
-        return self._host.ids_of_pe(mate2._host, idx)
+        return self._ids_to_host(self.ids_pe_dev(mate2, idx)) if self.keeps_ids else self._host.ids_of_pe(mate2._host, idx)
+
+    def _ids_to_host(self, blk: DeviceIds):
+        return self.download(blk.ids, int(blk.off[-1])), blk.off
+
+    def gather_ids(self, idx, off: np.ndarray, mate2: Optional["DeviceColumns"] = None) -> DeviceIds:
+        """fqsx_cols_gather_ids: the id lines of the reads idx (with mate2: of the pairs idx, mates interleaved) under the offsets off."""
+        idx, off = self._gather_args(idx, off, mate2)
+        out = [C.c_void_p() for _ in range(2)]
+        self._call("fqsx_cols_gather_ids", self._h, mate2._h if mate2 is not None else None, idx.ctypes.data if len(idx) else None, len(idx),
+                   off.ctypes.data, *[C.byref(p) for p in out])
+        return DeviceIds(out[0].value, out[1].value, off)
+
+    def ids_dev(self, idx) -> DeviceIds:
+        idx = np.asarray(idx, dtype=np.int64)
+        off = np.zeros(len(idx) + 1, dtype=np.uint64)
+        io = self.id_off.view(np.int64)
+        off[1:] = np.cumsum(io[idx + 1] - io[idx])
+        return self.gather_ids(idx, off)
+
+    def ids_pe_dev(self, mate2: "DeviceColumns", idx) -> DeviceIds:
+        idx = np.asarray(idx, dtype=np.int64)
+        ln = np.empty(2 * len(idx), dtype=np.int64)
+        i1, i2 = self.id_off.view(np.int64), mate2.id_off.view(np.int64)
+        ln[0::2], ln[1::2] = i1[idx + 1] - i1[idx], i2[idx + 1] - i2[idx]
+        off = np.zeros(2 * len(idx) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(ln)
+        return self.gather_ids(idx, off, mate2)
+
+    def id_survey(self) -> dict:
+        """fqsx_cols_id_survey: over the id lines of the store the four quantities the id kernel's staging limits are about."""
+        a = (C.c_uint64 * 8)()
+        self._call("fqsx_cols_id_survey", self._h, a)
+        return {"keeps_ids": bool(a[0]), "id_bytes": int(a[1]), "max_line": int(a[2]), "max_tokens": int(a[3]), "max_name": int(a[4]),
+                "max_name_tokens": int(a[5])}
 
     def info(self) -> dict:
-        a = (C.c_uint64 * 4)()
+        a, b = (C.c_uint64 * 4)(), (C.c_uint64 * 2)()
         self._call("fqsx_cols_info", self._h, a, fmt="{name}: {text}")
-        return {"records": int(a[0]), "bases": int(a[1]), "device_bytes": int(a[2]), "device_bytes_peak": int(a[3])}
+        self._call("fqsx_cols_id_info", self._h, b, fmt="{name}: {text}")
+        return {"records": int(a[0]), "bases": int(a[1]), "device_bytes": int(a[2]), "device_bytes_peak": int(a[3]), "id_bytes": int(b[1])}
 
-    def gather(self, idx, off: np.ndarray, mate2: Optional["DeviceColumns"] = None) -> DeviceBlock:
-        """fqsx_cols_gather: the block of the reads idx (with mate2: of the pairs idx, mates interleaved) whose offsets are off."""
+    @staticmethod
+    def _gather_args(idx, off: np.ndarray, mate2):
         idx = np.asarray(idx)
         if len(idx) and (int(idx.min()) < 0 or int(idx.max()) >> 32):
             raise ValueError("read indices are 32-bit")
@@ -653,6 +731,11 @@ class DeviceColumns(_Handle):
         off = np.ascontiguousarray(off, dtype=np.uint64)
         if len(off) != len(idx) * (2 if mate2 is not None else 1) + 1:
             raise ValueError("a block of n reads has n + 1 offsets")
+        return idx, off
+
+    def gather(self, idx, off: np.ndarray, mate2: Optional["DeviceColumns"] = None) -> DeviceBlock:
+        """fqsx_cols_gather: the block of the reads idx (with mate2: of the pairs idx, mates interleaved) whose offsets are off."""
+        idx, off = self._gather_args(idx, off, mate2)
         out = [C.c_void_p() for _ in range(3)]
         self._call("fqsx_cols_gather", self._h, mate2._h if mate2 is not None else None, idx.ctypes.data if len(idx) else None, len(idx),
                    off.ctypes.data, *[C.byref(p) for p in out])
@@ -704,7 +787,11 @@ class DeviceColumns(_Handle):
     def kernel_times(self) -> dict:
         a = (C.c_double * 4)()
         self._lib.fqsx_cols_kernel_times(self._h, a)
-        return {"gather_ms": a[0], "gather_launches": int(a[1]), "check_ms": a[2], "check_launches": int(a[3])}
+        b = (C.c_double * 6)()
+        self._lib.fqsx_cols_id_kernel_times(self._h, b)
+        return {"gather_ms": a[0], "gather_launches": int(a[1]), "check_ms": a[2], "check_launches": int(a[3]),
+                "id_check_ms": b[0], "id_check_launches": int(b[1]), "id_gather_ms": b[2], "id_gather_launches": int(b[3]),
+                "id_survey_ms": b[4], "id_survey_launches": int(b[5])}
 
 
 def _chunk_source(src):
@@ -724,20 +811,25 @@ def _chunk_source(src):
 
 
 def parse_fastq(text_or_path, device: int = 0, lib_path: Optional[str] = None, max_chunk_bytes: int = 0, stats: Optional[dict] = None,
-                profile: bool = False, resident: bool = False):
+                profile: bool = False, resident: bool = False, resident_ids: bool = False):
     """FASTQ text (bytes / uint8 array) or a file (path) to hostpipe.Columns, parsed on the GPU chunk by chunk: a file is read in
     chunk-sized pieces into one reused buffer, the partial record at the end of a chunk is carried to the front of the next, and a
     chunk that holds no complete record doubles the chunk size.  What follows the last complete record (the reference drops an
     unterminated last record too) is not returned; its size is stats["tail_bytes"].  stats: also "chunks", "consumed",
     "max_id_line", "length_mismatch" and -- profile -- "kernels".
     resident: a DeviceColumns instead -- the base and quality columns never come to the host (the caller closes it); ValueError
-    for a record whose quality line differs in length from its base line, which resident columns cannot hold."""
+    for a record whose quality line differs in length from its base line, which resident columns cannot hold.
+    resident_ids (with resident): the id column stays in device memory too (DeviceColumns.keep_ids): the store's `ids` is empty."""
     from . import hostpipe as hp
+    if resident_ids and not resident:
+        raise ValueError("resident_ids needs resident: the id column stays beside the two others")
     p = FastqParser(device, lib_path, max_chunk_bytes)
     store = DeviceColumns(device, lib_path) if resident else None
     readinto, close = _chunk_source(text_or_path)
     parts, n_chunks, consumed, max_id, mismatch = [], 0, 0, 0, False
     try:
+        if resident_ids:
+            store.keep_ids()
         p.set_profiling(profile)
         size = p.max_chunk_bytes
         buf = np.empty(size, dtype=np.uint8)

@@ -2578,6 +2578,10 @@ FQ_KERNEL64 void k_id_encode(IdCfg cfg, u32 n_reads, u32 paired) {
   FQ_SHARED IdShared sm;
   id_encode_body(cfg, &sm, FQ_BLOCK, n_reads, paired);
 }
+FQ_KERNEL256 void k_id_separators(IdSepCfg c) {
+  FQ_SHARED u64 ws[IDK_SEP_WAVES];
+  id_separators_body(c, ws, FQ_BLOCK);
+}
 FQ_KERNEL64 void k_id_decode(IdCfg cfg, IdDecArgs da, u32 n_reads, u32 paired) {
   FQ_SHARED IdShared sm;
   id_decode_body(cfg, da, &sm, FQ_BLOCK, n_reads, paired);
@@ -2601,6 +2605,9 @@ struct fqsx_idg : DevCtx {
   u64 *d_off;
   u8 *d_compact;   // the T streams back to back (collect_streams)
   u64 compact_cap;
+  u64 *d_sep = nullptr; u64 sep_cap = 0;   // [T] fqsx_idg_encode_block_dev: the separators of every worker's lines (k_id_separators)
+  std::vector<u64> h_sep;
+  double sep_ms = 0; u64 sep_n = 0;        // ... and that kernel's time
   std::vector<u32> h_state;
   std::vector<u64> h_lens;
   std::vector<u8> h_out;
@@ -2675,45 +2682,36 @@ int fqsx_idg_create(const uint8_t *h, int device, fqsx_idg **out) {
   return FQSX_OK;
 }
 
-// ids: concatenated id lines, each INCLUDING its '\n' (read_desc_t::id_len, defs.h:70-72); id_off: n_reads + 1 offsets;
-// paired != 0: reads alternate mate 1 / mate 2.  streams[t] / lens[t]: worker t's id stream of the block (callee-owned until
-// the next call) -- byte-identical to fqsx_id_encode_block's (the host coder) and hence to the reference's.
-int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, uint32_t n_reads, int paired,
-                          const uint8_t **streams, uint64_t *lens) {
-  if (!q || !ids || !off || !streams || !lens || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
+// ---- the two halves both encode entry points share
+// Table sizes: a worker creates at most one big model per byte it codes plus nine per numeric token, and three small ones per
+// token plus two per read; tokens end at separators, sep[t] of them in worker t's lines.  Then the output and its compact copy:
+// every allocation of the block before the launch, so a call that fails for memory has not moved the models and can be repeated.
+static int idg_fit_block(fqsx_idg *q, const uint64_t *off, uint32_t n_reads, const u64 *sep) {
   DevCtx *c = q;
   IdCfg &cfg = q->cfg;
   const u64 T = q->T;
-  DEVCHK(dev_enter(c));
   int rc;
-  // ---- table sizes: a worker creates at most one big model per byte it codes plus nine per numeric token, and three small
-  // ones per token plus two per read; tokens end at separators, which are counted here
   u64 max_bytes = 0, max_big = 0, max_small = 0;
   for (u64 t = 0; t < T; ++t) {
     u64 first, last;
     worker_reads(t, T, n_reads, first, last);
     const u64 nb = off[last] - off[first];
-    u64 sep = 0;
-    for (u64 i = off[first]; i < off[last]; ++i) {
-      const u8 ch = ids[i];
-      sep += !((ch >= '0' && ch <= '9') || (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z') || ch == '@');
-    }
     max_bytes = std::max(max_bytes, nb);
-    max_big = std::max(max_big, (u64)q->h_state[4 * t + 1] + nb + 9 * sep + 2 * (last - first) + 16);
-    max_small = std::max(max_small, (u64)q->h_state[4 * t] + 3 * sep + 4 * (last - first) + 16);
+    max_big = std::max(max_big, (u64)q->h_state[4 * t + 1] + nb + 9 * sep[t] + 2 * (last - first) + 16);
+    max_small = std::max(max_small, (u64)q->h_state[4 * t] + 3 * sep[t] + 4 * (last - first) + 16);
   }
   if (max_small * 10 >= q->small_cap * 8 && (rc = hash_tab_regrow(c, cfg.small, q->small_cap, cfg.small_mask, pow2_at_least(max_small * 2), q->T, 2))) return rc;
   if (max_big * 10 >= q->big_cap * 8 && (rc = hash_tab_regrow(c, cfg.big, q->big_cap, cfg.big_mask, pow2_at_least(max_big * 2), q->T, IDK_BIG_U64))) return rc;
-  const u64 need_out = (max_bytes * 2 + 4096 + 7) & ~7ull, ni = off[n_reads] + 64, no = ((u64)n_reads + 1) * sizeof(u64);
+  const u64 need_out = (max_bytes * 2 + 4096 + 7) & ~7ull;
   if ((rc = dfit(c, cfg.out, cfg.out_cap, need_out, need_out, T))) return rc;
-  // (every allocation of the block before the launch: a call that fails for memory has not moved the models and can be repeated)
-  if ((rc = dfit(c, q->d_compact, q->compact_cap, cfg.out_cap * T, cfg.out_cap * T, 1))) return rc;
-  if ((rc = dfit(c, q->d_ids, q->ids_cap, ni, ni + ni / 4, 1))) return rc;
-  if ((rc = dfit(c, q->d_off, q->off_cap, no, no + no / 4, 1))) return rc;
-  if ((rc = h2d(c, q->d_ids, ids, off[n_reads]))) return rc;
-  if ((rc = h2d(c, q->d_off, off, no))) return rc;
-  cfg.ids = q->d_ids;
-  cfg.off = q->d_off;
+  return dfit(c, q->d_compact, q->compact_cap, cfg.out_cap * T, cfg.out_cap * T, 1);
+}
+// the kernel on cfg.ids / cfg.off, its error word, the streams
+static int idg_encode_run(fqsx_idg *q, uint32_t n_reads, int paired, const uint8_t **streams, uint64_t *lens) {
+  DevCtx *c = q;
+  IdCfg &cfg = q->cfg;
+  const u64 T = q->T;
+  int rc;
   LAUNCH(c, 0, k_id_encode, q->T, 64, cfg, n_reads, (u32)(paired != 0));
   if ((rc = d2h_sync(c, q->h_lens.data(), cfg.lens, (T + 2 + 2 * T) * sizeof(u64)))) return rc;
   memcpy(q->h_state.data(), q->h_lens.data() + T + 2, 4 * T * sizeof(u32));
@@ -2728,6 +2726,67 @@ int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, 
   for (u64 t = 0; t < T; ++t)
     if (q->h_lens[t] > cfg.out_cap) { g_err = "id stream overflow"; return FQSX_E_DEVICE; }
   return collect_streams(c, q->d_compact, (u32)T, cfg.out, cfg.out_cap, cfg.lens, q->h_lens, q->h_out, streams, lens);
+}
+
+// ids: concatenated id lines, each INCLUDING its '\n' (read_desc_t::id_len, defs.h:70-72); id_off: n_reads + 1 offsets;
+// paired != 0: reads alternate mate 1 / mate 2.  streams[t] / lens[t]: worker t's id stream of the block (callee-owned until
+// the next call) -- byte-identical to fqsx_id_encode_block's (the host coder) and hence to the reference's.
+int fqsx_idg_encode_block(fqsx_idg *q, const uint8_t *ids, const uint64_t *off, uint32_t n_reads, int paired,
+                          const uint8_t **streams, uint64_t *lens) {
+  if (!q || !ids || !off || !streams || !lens || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
+  DevCtx *c = q;
+  IdCfg &cfg = q->cfg;
+  const u64 T = q->T;
+  DEVCHK(dev_enter(c));
+  int rc;
+  q->h_sep.assign(T, 0);
+  for (u64 t = 0; t < T; ++t) {
+    u64 first, last;
+    worker_reads(t, T, n_reads, first, last);
+    u64 sep = 0;
+    for (u64 i = off[first]; i < off[last]; ++i) {
+      const u8 ch = ids[i];
+      sep += !((ch >= '0' && ch <= '9') || (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z') || ch == '@');
+    }
+    q->h_sep[t] = sep;
+  }
+  if ((rc = idg_fit_block(q, off, n_reads, q->h_sep.data()))) return rc;
+  const u64 ni = off[n_reads] + 64, no = ((u64)n_reads + 1) * sizeof(u64);
+  if ((rc = dfit(c, q->d_ids, q->ids_cap, ni, ni + ni / 4, 1))) return rc;
+  if ((rc = dfit(c, q->d_off, q->off_cap, no, no + no / 4, 1))) return rc;
+  if ((rc = h2d(c, q->d_ids, ids, off[n_reads]))) return rc;
+  if ((rc = h2d(c, q->d_off, off, no))) return rc;
+  cfg.ids = q->d_ids;
+  cfg.off = q->d_off;
+  return idg_encode_run(q, n_reads, paired, streams, lens);
+}
+
+// The same for a block that lies in device memory (fqsx_cols_gather_ids): d_ids with the 64 bytes of slack of the coder's own
+// staging buffer, d_id_off its offsets there and h_id_off the same offsets on the host.  What the loop over the bytes above
+// counts, k_id_separators counts where the block lies; its T counts come back in one transfer.  The caller has drained the
+// stream that wrote the buffers.
+int fqsx_idg_encode_block_dev(fqsx_idg *q, const uint8_t *d_ids, const uint64_t *d_id_off, const uint64_t *h_id_off, uint32_t n_reads, int paired,
+                              const uint8_t **streams, uint64_t *lens) {
+  if (!q || !d_ids || !d_id_off || !h_id_off || !streams || !lens || (paired && (n_reads & 1))) { g_err = "bad argument"; return FQSX_E_ARG; }
+  DevCtx *c = q;
+  IdCfg &cfg = q->cfg;
+  const u64 T = q->T;
+  DEVCHK(dev_enter(c));
+  int rc;
+  if ((rc = dfit(c, q->d_sep, q->sep_cap, T, T, sizeof(u64)))) return rc;
+  IdSepCfg sc;
+  sc.ids = d_ids; sc.off = d_id_off; sc.n_bytes = h_id_off[n_reads]; sc.sep = q->d_sep; sc.T = (u32)T; sc.n_reads = n_reads;
+  const double t0 = c->k_ms[2];
+  const u64 n0 = c->k_n[2];
+  LAUNCH(c, 2, k_id_separators, q->T, 256, sc);
+  q->sep_ms += c->k_ms[2] - t0;
+  q->sep_n += c->k_n[2] - n0;   // (launches timed, as k_n counts them)
+  q->h_sep.assign(T, 0);
+  if ((rc = d2h_sync(c, q->h_sep.data(), q->d_sep, T * sizeof(u64)))) return rc;
+  if ((rc = idg_fit_block(q, h_id_off, n_reads, q->h_sep.data()))) return rc;
+  cfg.ids = d_ids;
+  cfg.off = d_id_off;
+  return idg_encode_run(q, n_reads, paired, streams, lens);
 }
 
 // Inverse of fqsx_idg_encode_block.  The encoder sizes its tables and its output from the ids it is given; the decoder
@@ -2906,6 +2965,12 @@ int fqsx_idg_error_kind(fqsx_idg *q) { return q ? (int)q->last_kind : FQSX_E_ARG
 int fqsx_idg_set_profiling(fqsx_idg *q, int enable) {
   if (!q) return FQSX_E_ARG;
   q->profiling = enable != 0;
+  return FQSX_OK;
+}
+int fqsx_idg_separator_times(fqsx_idg *q, double out[2]) {
+  if (!q || !out) return FQSX_E_ARG;
+  out[0] = q->sep_ms;
+  out[1] = (double)q->sep_n;
   return FQSX_OK;
 }
 int fqsx_idg_kernel_times(fqsx_idg *q, double out[2]) {
@@ -3245,20 +3310,22 @@ int fqsx_fastq_index(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t ou
 
 // Offsets and gather of the chunk indexed last (records in it), then what the caller wants on the host (a null pointer skips
 // the array).  The base and quality columns go behind the ids in the parser's own buffer, or -- d_bases / d_quals, device
-// memory of the chunk's sizes -- where the caller keeps them, with read_off copied to d_read_off on the device.
-static int fq_columns_impl(fqsx_fastq *h, u8 *d_bases, u8 *d_quals, u64 *d_read_off, uint8_t *ids, uint64_t *id_off, uint8_t *bases,
-                           uint64_t *read_off, uint8_t *quals, uint64_t *qual_off, uint32_t *plus_len) {
+// memory of the chunk's sizes -- where the caller keeps them, with read_off copied to d_read_off on the device; with them the
+// caller may keep the id column too (d_ids, and id_off copied to d_id_off).
+static int fq_columns_impl(fqsx_fastq *h, u8 *d_bases, u8 *d_quals, u64 *d_read_off, u8 *d_ids, u64 *d_id_off, uint8_t *ids, uint64_t *id_off,
+                           uint8_t *bases, uint64_t *read_off, uint8_t *quals, uint64_t *qual_off, uint32_t *plus_len) {
   FqCfg &c = h->cfg;
   const u64 nb[3] = {h->sum[FQ_SUM_ID_BYTES], h->sum[FQ_SUM_BASES], h->sum[FQ_SUM_QUALS]};
-  const u64 own = d_bases ? nb[0] : nb[0] + nb[1] + nb[2];
+  const u64 own = d_ids ? 0 : d_bases ? nb[0] : nb[0] + nb[1] + nb[2];
   DEVCHK(dfit(h, h->d_off, h->off_cap, c.n_rec + 1, c.n_rec + c.n_rec / 8 + 1, 3 * sizeof(u64)));
   DEVCHK(dfit(h, h->d_col, h->col_cap, own, own, 1));
   c.off = h->d_off; c.off_stride = h->off_cap;
-  c.col[0] = h->d_col; c.col[1] = d_bases ? d_bases : c.col[0] + nb[0]; c.col[2] = d_bases ? d_quals : c.col[1] + nb[1];
+  c.col[0] = d_ids ? d_ids : h->d_col; c.col[1] = d_bases ? d_bases : c.col[0] + nb[0]; c.col[2] = d_bases ? d_quals : c.col[1] + nb[1];
   for (u32 q = 0; q < 3; ++q) c.col_n[q] = nb[q];
   FQ_LAUNCH(h, FQ_PASS_OFFSETS, k_fq_offsets, c.n_rtiles);
   FQ_LAUNCH(h, FQ_PASS_GATHER, k_fq_gather, (u32)((c.n_rec + 4 * FQSX_FQ_GBATCH - 1) / (4 * FQSX_FQ_GBATCH)));
   if (d_read_off) DEVCHK(d2d(h, d_read_off, c.off + c.off_stride, (c.n_rec + 1) * sizeof(u64)));
+  if (d_id_off) DEVCHK(d2d(h, d_id_off, c.off, (c.n_rec + 1) * sizeof(u64)));
   u8 *const hc[3] = {ids, bases, quals};
   u64 *const ho[3] = {id_off, read_off, qual_off};
   for (u32 q = 0; q < 3; ++q) {
@@ -3280,7 +3347,7 @@ int fqsx_fastq_columns(fqsx_fastq *h, uint8_t *ids, uint64_t *id_off, uint8_t *b
     if (qual_off) qual_off[0] = 0;
     return FQSX_OK;
   }
-  return fq_columns_impl(h, nullptr, nullptr, nullptr, ids, id_off, bases, read_off, quals, qual_off, plus_len);
+  return fq_columns_impl(h, nullptr, nullptr, nullptr, nullptr, nullptr, ids, id_off, bases, read_off, quals, qual_off, plus_len);
 }
 
 int fqsx_fastq_set_profiling(fqsx_fastq *h, int enable) {
@@ -3302,17 +3369,28 @@ int fqsx_fastq_kernel_times(fqsx_fastq *h, double out[14]) {
 // =======================================================================================================
 #include "fqsx_cols.h"
 
-struct fqsx_cols : DevCtx {
-  std::vector<ColsChunk> chunks;   // (device pointers) one allocation per parsed chunk: offsets, bases, qualities
-  u64 n_rec = 0, n_bases = 0;
-  ColsChunk *d_chunks = nullptr; u64 chunks_cap = 0;
-  bool table_stale = false;        // chunks appended since d_chunks was written
-  // the block gathered last: bases, qualities, and its offsets in one of two buffers (a refused gather leaves the other alone)
+// the block gathered last from one column: its bytes (reads: bases and qualities; ids: the lines), and its offsets in one of
+// two buffers (a refused gather leaves the other alone)
+struct ColsBlock {
   u8 *d_out[2] = {nullptr, nullptr}; u64 out_cap[2] = {0, 0};
   u64 *d_boff[2] = {nullptr, nullptr}; u64 boff_cap[2] = {0, 0};
   u32 boff_cur = 0;
+};
+enum { COLS_T_ID_CHECK = 0, COLS_T_ID_GATHER = 1, COLS_T_ID_SURVEY = 2, COLS_N_T_ID = 3 };
+
+struct fqsx_cols : DevCtx {
+  std::vector<ColsChunk> chunks;   // (device pointers) one allocation per parsed chunk: offsets, bases, qualities -- and, in a
+                                   // store that keeps ids, id offsets and id lines
+  u64 n_rec = 0, n_bases = 0, n_id_bytes = 0;
+  bool keep_ids = false;
+  ColsChunk *d_chunks = nullptr; u64 chunks_cap = 0;
+  bool table_stale = false;        // chunks appended since d_chunks was written
+  ColsBlock blk[2];                // [COLS_READS], [COLS_IDS]: buffers of their own, so a block's bases and its ids are valid together
   u32 *d_idx = nullptr; u64 idx_cap = 0;
   u32 *d_err = nullptr;            // [4]
+  u32 *d_survey = nullptr; u64 survey_cap = 0;   // [groups][COLS_N_SV]
+  double id_ms[COLS_N_T_ID] = {0, 0, 0};         // kernel time of the id column's launches (booked under kernel index 1)
+  u64 id_n[COLS_N_T_ID] = {0, 0, 0};
 };
 
 static u64 up16(u64 x) { return (x + 15) & ~15ull; }
@@ -3329,16 +3407,76 @@ static int cols_fit_table(fqsx_cols *s) {
   return FQSX_OK;
 }
 
-static int cols_launch(fqsx_cols *a, const ColsCfg &cfg, u32 kidx) {
+// one launch of the id column's kernels, its time (while profiling) booked under `what`
+#define COLS_ID_LAUNCH(s, what, kern, grid, cfg)     \
+  do {                                               \
+    const double t0_ = (s)->k_ms[1];                 \
+    const u64 n0_ = (s)->k_n[1];                     \
+    LAUNCH(s, 1, kern, grid, 256, cfg);              \
+    (s)->id_ms[what] += (s)->k_ms[1] - t0_;          \
+    (s)->id_n[what] += (s)->k_n[1] - n0_;            \
+  } while (0)
+
+// the checking (cfg.store 0) or the copying pass of a gather from column col
+static int cols_launch(fqsx_cols *a, const ColsCfg &cfg, u32 col) {
   const u64 per_group = (u64)COLS_WAVES * FQ_WAVE;
   const u32 grid = (u32)((cfg.n_out + per_group - 1) / per_group);
-  LAUNCH(a, kidx, k_cols_gather, grid, 256, cfg);
+  if (col == COLS_IDS)
+    COLS_ID_LAUNCH(a, cfg.store ? COLS_T_ID_GATHER : COLS_T_ID_CHECK, k_cols_gather_ids, grid, cfg);
+  else
+    LAUNCH(a, cfg.store ? 0 : 2, k_cols_gather, grid, 256, cfg);
+  return FQSX_OK;
+}
+
+// fqsx_cols_gather / fqsx_cols_gather_ids: the block of column col whose read i is record idx[i] (with b: mates interleaved)
+// and whose offsets are h_off, in the column's block buffers; *d_off: the offsets on the device
+static int cols_gather_run(fqsx_cols *a, fqsx_cols *b, u32 col, const uint32_t *idx, uint32_t n, const uint64_t *h_off, const uint64_t **d_off) {
+  if (b && b->device != a->device) { g_err = "the two column stores are on different devices"; return FQSX_E_ARG; }
+  if (col == COLS_IDS && (!a->keep_ids || (b && !b->keep_ids))) { g_err = "a column store that does not keep ids (fqsx_cols_keep_ids)"; return FQSX_E_ARG; }
+  const u64 n_out = (u64)n * (b ? 2 : 1);
+  if (n_out > 0xffffffffull) { g_err = "a block of 2^32 reads or more"; return FQSX_E_ARG; }
+  if (h_off[0] != 0) { g_err = "block offsets must start at 0"; return FQSX_E_ARG; }
+  DEVCHK(cols_fit_table(a));
+  if (b) DEVCHK(cols_fit_table(b));
+  DEVCHK(dev_enter(a));
+  ColsBlock &k = a->blk[col];
+  const u32 nxt = k.boff_cur ^ 1u, n_col = col == COLS_IDS ? 1 : 2;
+  DEVCHK(dfit(a, a->d_idx, a->idx_cap, std::max<u64>(n, 1), (u64)n + n / 4 + 16, sizeof(u32)));
+  DEVCHK(dfit(a, k.d_boff[nxt], k.boff_cap[nxt], n_out + 1, n_out + n_out / 4 + 16, sizeof(u64)));
+  if (n) DEVCHK(h2d(a, a->d_idx, idx, (u64)n * sizeof(u32)));
+  DEVCHK(h2d(a, k.d_boff[nxt], h_off, (n_out + 1) * sizeof(u64)));
+  DEVCHK(dzero(a, a->d_err, 4 * sizeof(u32)));
+  ColsCfg cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.src[0].chunk = a->d_chunks; cfg.src[0].n_chunks = (u32)a->chunks.size(); cfg.src[0].n_rec = a->n_rec;
+  if (b) { cfg.src[1].chunk = b->d_chunks; cfg.src[1].n_chunks = (u32)b->chunks.size(); cfg.src[1].n_rec = b->n_rec; }
+  cfg.n_src = b ? 2 : 1;
+  cfg.idx = a->d_idx; cfg.off = k.d_boff[nxt]; cfg.n_out = n_out;
+  cfg.out_n = h_off[n_out];
+  cfg.err = a->d_err;
+  u32 err[4] = {0, 0, 0, 0};
+  // every record checked before the block buffers are touched (or grown): a refused block leaves the previous one as it was
+  if (n_out) DEVCHK(cols_launch(a, cfg, col));
+  DEVCHK(d2h_sync(a, err, a->d_err, sizeof(err)));
+  if (!err[COLS_ERR_INDEX] && !err[COLS_ERR_LENGTH] && !err[COLS_ERR_RANGE]) {
+    const u64 need = cfg.out_n + 64;
+    for (u32 q = 0; q < n_col; ++q) DEVCHK(dfit(a, k.d_out[q], k.out_cap[q], need, need + need / 4, 1));
+    cfg.out[0] = k.d_out[0]; cfg.out[1] = k.d_out[1];
+    cfg.store = 1;
+    if (n_out) DEVCHK(cols_launch(a, cfg, col));
+    DEVCHK(d2h_sync(a, err, a->d_err, sizeof(err)));   // (the stream is drained: the coders read the block from streams of their own)
+  }
+  if (err[COLS_ERR_INDEX]) { g_err = "a read index beyond the records of the column store"; return FQSX_E_ARG; }
+  if (err[COLS_ERR_LENGTH]) { g_err = "the block's offsets give a read another length than the column store holds"; return FQSX_E_ARG; }
+  if (err[COLS_ERR_RANGE]) { g_err = "device error in the column gather: a source or destination range outside its buffer"; return FQSX_E_DEVICE; }
+  k.boff_cur = nxt;
+  *d_off = k.d_boff[nxt];
   return FQSX_OK;
 }
 
 // Sort pre-pass on the store (n records, n > 0): where every record lies and its bin (k_cols_locate), then the ranks of the
 // sort of fqsx_sort.h reading the reads there.  Everything it allocates is in mem: per record 8 + 4 + 1 bytes here and 16 in
-// sort_rank_run, the tiles' histograms and info, and a copy of the chunk table (48 bytes a chunk: the store's own is written
+// sort_rank_run, the tiles' histograms and info, and a copy of the chunk table (72 bytes a chunk: the store's own is written
 // when the first block is cut, and the store is left as it was found).  Launches are timed under kernel index 1.
 static int cols_sort_ranks(fqsx_cols *s, DevScratch &mem, std::vector<u32> &rank, std::vector<u8> &bin, u32 *passes_out) {
   const u32 n = (u32)s->n_rec;
@@ -3412,15 +3550,20 @@ int fqsx_fastq_columns_into(fqsx_fastq *h, fqsx_cols *s, uint8_t *ids, uint64_t 
     return FQSX_OK;
   }
   if (s->n_rec + c.n_rec > 0xffffffffull) { g_err = "a block is cut by 32-bit record indices: 2^32 records or more in one store"; return FQSX_E_ARG; }
-  const u64 nb = h->sum[FQ_SUM_BASES], off_bytes = up16((c.n_rec + 1) * sizeof(u64));
+  const u64 nb = h->sum[FQ_SUM_BASES], off_bytes = up16((c.n_rec + 1) * sizeof(u64)), ni = s->keep_ids ? h->sum[FQ_SUM_ID_BYTES] : 0;
   void *mem = nullptr;
-  DEVCHK(dalloc(s, &mem, off_bytes + 2 * up16(nb), false));
+  DEVCHK(dalloc(s, &mem, off_bytes + 2 * up16(nb) + (s->keep_ids ? off_bytes + up16(ni) : 0), false));
   ColsChunk ck;
   ck.off = (const u64 *)mem;
   ck.bases = (const u8 *)mem + off_bytes;
   ck.quals = ck.bases + up16(nb);
   ck.rec0 = s->n_rec; ck.n_rec = c.n_rec; ck.n_bytes = nb;
-  const int rc = fq_columns_impl(h, (u8 *)ck.bases, (u8 *)ck.quals, (u64 *)ck.off, ids, id_off, nullptr, read_off, nullptr, nullptr, plus_len);
+  // (a store that keeps ids: the parser's id column is this part of the chunk, so the gather writes the lines where they stay)
+  ck.id_off = s->keep_ids ? (const u64 *)(ck.quals + up16(nb)) : nullptr;
+  ck.ids = s->keep_ids ? (const u8 *)ck.id_off + off_bytes : nullptr;
+  ck.n_id_bytes = ni;
+  const int rc = fq_columns_impl(h, (u8 *)ck.bases, (u8 *)ck.quals, (u64 *)ck.off, (u8 *)ck.ids, (u64 *)ck.id_off, ids, id_off, nullptr, read_off,
+                                 nullptr, nullptr, plus_len);
   if (rc) {   // (the store is what it was)
     dev_drain(h);
     dfree(s, mem);
@@ -3429,6 +3572,7 @@ int fqsx_fastq_columns_into(fqsx_fastq *h, fqsx_cols *s, uint8_t *ids, uint64_t 
   s->chunks.push_back(ck);
   s->n_rec += c.n_rec;
   s->n_bases += nb;
+  s->n_id_bytes += ni;
   s->table_stale = true;
   return FQSX_OK;
 }
@@ -3436,44 +3580,64 @@ int fqsx_fastq_columns_into(fqsx_fastq *h, fqsx_cols *s, uint8_t *ids, uint64_t 
 int fqsx_cols_gather(fqsx_cols *a, fqsx_cols *b, const uint32_t *idx, uint32_t n, const uint64_t *h_off, const uint8_t **d_bases,
                      const uint8_t **d_quals, const uint64_t **d_off) {
   if (!a || (n && !idx) || !h_off || !d_bases || !d_quals || !d_off) { g_err = "null argument"; return FQSX_E_ARG; }
-  if (b && b->device != a->device) { g_err = "the two column stores are on different devices"; return FQSX_E_ARG; }
-  const u64 n_out = (u64)n * (b ? 2 : 1);
-  if (n_out > 0xffffffffull) { g_err = "a block of 2^32 reads or more"; return FQSX_E_ARG; }
-  if (h_off[0] != 0) { g_err = "block offsets must start at 0"; return FQSX_E_ARG; }
-  DEVCHK(cols_fit_table(a));
-  if (b) DEVCHK(cols_fit_table(b));
-  DEVCHK(dev_enter(a));
-  const u32 nxt = a->boff_cur ^ 1u;
-  DEVCHK(dfit(a, a->d_idx, a->idx_cap, std::max<u64>(n, 1), (u64)n + n / 4 + 16, sizeof(u32)));
-  DEVCHK(dfit(a, a->d_boff[nxt], a->boff_cap[nxt], n_out + 1, n_out + n_out / 4 + 16, sizeof(u64)));
-  if (n) DEVCHK(h2d(a, a->d_idx, idx, (u64)n * sizeof(u32)));
-  DEVCHK(h2d(a, a->d_boff[nxt], h_off, (n_out + 1) * sizeof(u64)));
-  DEVCHK(dzero(a, a->d_err, 4 * sizeof(u32)));
-  ColsCfg cfg;
+  DEVCHK(cols_gather_run(a, b, COLS_READS, idx, n, h_off, d_off));
+  *d_bases = a->blk[COLS_READS].d_out[0]; *d_quals = a->blk[COLS_READS].d_out[1];
+  return FQSX_OK;
+}
+
+int fqsx_cols_gather_ids(fqsx_cols *a, fqsx_cols *b, const uint32_t *idx, uint32_t n, const uint64_t *h_id_off, const uint8_t **d_ids,
+                         const uint64_t **d_id_off) {
+  if (!a || (n && !idx) || !h_id_off || !d_ids || !d_id_off) { g_err = "null argument"; return FQSX_E_ARG; }
+  DEVCHK(cols_gather_run(a, b, COLS_IDS, idx, n, h_id_off, d_id_off));
+  *d_ids = a->blk[COLS_IDS].d_out[0];
+  return FQSX_OK;
+}
+
+int fqsx_cols_keep_ids(fqsx_cols *s) {
+  if (!s) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (!s->chunks.empty()) { g_err = "fqsx_cols_keep_ids after the first chunk was appended"; return FQSX_E_ARG; }
+  s->keep_ids = true;
+  return FQSX_OK;
+}
+
+int fqsx_cols_id_info(fqsx_cols *s, uint64_t out[2]) {
+  if (!s || !out) { g_err = "null argument"; return FQSX_E_ARG; }
+  out[0] = s->keep_ids ? 1 : 0; out[1] = s->n_id_bytes;
+  return FQSX_OK;
+}
+
+int fqsx_cols_id_survey(fqsx_cols *s, uint64_t out[8]) {
+  if (!s || !out) { g_err = "null argument"; return FQSX_E_ARG; }
+  for (u32 k = 0; k < 8; ++k) out[k] = 0;
+  out[0] = s->keep_ids ? 1 : 0; out[1] = s->n_id_bytes;
+  if (!s->keep_ids || s->n_rec == 0) return FQSX_OK;
+  DEVCHK(cols_fit_table(s));
+  DEVCHK(dev_enter(s));
+  const u64 per_group = (u64)COLS_WAVES * FQ_WAVE;
+  const u32 grid = (u32)((s->n_rec + per_group - 1) / per_group);
+  DEVCHK(dfit(s, s->d_survey, s->survey_cap, grid, grid, COLS_N_SV * sizeof(u32)));
+  DEVCHK(dzero(s, s->d_err, 4 * sizeof(u32)));
+  ColsSurveyCfg cfg;
   memset(&cfg, 0, sizeof(cfg));
-  cfg.src[0].chunk = a->d_chunks; cfg.src[0].n_chunks = (u32)a->chunks.size(); cfg.src[0].n_rec = a->n_rec;
-  if (b) { cfg.src[1].chunk = b->d_chunks; cfg.src[1].n_chunks = (u32)b->chunks.size(); cfg.src[1].n_rec = b->n_rec; }
-  cfg.n_src = b ? 2 : 1;
-  cfg.idx = a->d_idx; cfg.off = a->d_boff[nxt]; cfg.n_out = n_out;
-  cfg.out_n = h_off[n_out];
-  cfg.err = a->d_err;
+  cfg.src.chunk = s->d_chunks; cfg.src.n_chunks = (u32)s->chunks.size(); cfg.src.n_rec = s->n_rec;
+  cfg.part = s->d_survey; cfg.err = s->d_err;
+  COLS_ID_LAUNCH(s, COLS_T_ID_SURVEY, k_cols_id_survey, grid, cfg);
   u32 err[4] = {0, 0, 0, 0};
-  // every record checked before the block buffers are touched (or grown): a refused block leaves the previous one as it was
-  if (n_out) DEVCHK(cols_launch(a, cfg, 2));
-  DEVCHK(d2h_sync(a, err, a->d_err, sizeof(err)));
-  if (!err[COLS_ERR_INDEX] && !err[COLS_ERR_LENGTH] && !err[COLS_ERR_RANGE]) {
-    const u64 need = cfg.out_n + 64;
-    for (u32 q = 0; q < 2; ++q) DEVCHK(dfit(a, a->d_out[q], a->out_cap[q], need, need + need / 4, 1));
-    cfg.out[0] = a->d_out[0]; cfg.out[1] = a->d_out[1];
-    cfg.store = 1;
-    if (n_out) DEVCHK(cols_launch(a, cfg, 0));
-    DEVCHK(d2h_sync(a, err, a->d_err, sizeof(err)));   // (the stream is drained: the coders read the block from streams of their own)
+  std::vector<u32> part((u64)grid * COLS_N_SV);
+  DEVCHK(d2h(s, err, s->d_err, sizeof(err)));
+  DEVCHK(d2h_sync(s, part.data(), s->d_survey, part.size() * sizeof(u32)));
+  if (err[COLS_ERR_INDEX] || err[COLS_ERR_LENGTH] || err[COLS_ERR_RANGE]) {
+    g_err = "device error in the id survey: a record outside its chunk or an id line outside its chunk's ids";
+    return FQSX_E_DEVICE;
   }
-  if (err[COLS_ERR_INDEX]) { g_err = "a read index beyond the records of the column store"; return FQSX_E_ARG; }
-  if (err[COLS_ERR_LENGTH]) { g_err = "the block's offsets give a read another length than the column store holds"; return FQSX_E_ARG; }
-  if (err[COLS_ERR_RANGE]) { g_err = "device error in the column gather: a source or destination range outside its buffer"; return FQSX_E_DEVICE; }
-  a->boff_cur = nxt;
-  *d_bases = a->d_out[0]; *d_quals = a->d_out[1]; *d_off = a->d_boff[nxt];
+  for (u64 g = 0; g < grid; ++g)
+    for (u32 k = 0; k < COLS_N_SV; ++k) out[2 + k] = std::max<u64>(out[2 + k], part[g * COLS_N_SV + k]);
+  return FQSX_OK;
+}
+
+int fqsx_cols_id_kernel_times(fqsx_cols *s, double out[6]) {
+  if (!s || !out) return FQSX_E_ARG;
+  for (u32 k = 0; k < COLS_N_T_ID; ++k) { out[2 * k] = s->id_ms[k]; out[2 * k + 1] = (double)s->id_n[k]; }
   return FQSX_OK;
 }
 

@@ -416,3 +416,52 @@ FQ_DEV void id_encode_body(const IdCfg &cfg, IdShared *sm, u32 tid, u32 n_reads,
     if (k.err) *cfg.err = k.err; else if (rc_overflowed(k.e)) *cfg.err = IDK_ERR_OUT;
   }
 }
+
+// The separators -- bytes outside [0-9A-Za-z@], idk_is_lit -- of every worker's lines, for a block that lies in device memory
+// (fqsx_idg_encode_block_dev): the host sizes the model tables from them.  One workgroup of 256 threads per worker over the
+// bytes [off[first], off[last]) of its reads: single bytes up to the first 16-byte boundary, 16 bytes per lane from there, the
+// bytes that are left; reduced over the wave, then over the workgroup's waves in LDS, one plain store per worker.
+#ifndef FQSX_EMU
+#define IDK_SEP_WAVES 4u
+#else
+#define IDK_SEP_WAVES 1u
+#endif
+struct IdSepCfg {
+  const u8 *ids;      // the block's id lines
+  const u64 *off;     // [n_reads + 1]
+  u64 n_bytes;        // off[n_reads] as the host knows it: nothing at or past it is read
+  u64 *sep;           // [T]
+  u32 T, n_reads;
+};
+struct alignas(16) IdSep16 { u64 lo, hi; };
+FQ_DEV u32 idk_separators8(u64 w) {
+  u32 n = 0;
+  for (u32 j = 0; j < 8; ++j) n += idk_is_lit((u8)(w >> (8 * j))) ? 0u : 1u;
+  return n;
+}
+FQ_DEV void id_separators_body(const IdSepCfg &c, u64 *ws, u32 tid) {
+  u64 first, last;
+  worker_reads(tid, c.T, c.n_reads, first, last);
+  u64 e = c.off[last], b = c.off[first];
+  e = e < c.n_bytes ? e : c.n_bytes;
+  b = b < e ? b : e;
+  const u8 *p = c.ids + b;
+  const u64 n = e - b;
+  const u64 to_boundary = (16u - ((u64)(uintptr_t)p & 15u)) & 15u, head = to_boundary < n ? to_boundary : n;
+  const u64 groups = (n - head) / 16u, tail = head + 16u * groups;
+  u64 cnt = 0;
+  for (u64 k = FQ_TID; k < head; k += FQ_NTHREADS) cnt += idk_is_lit(p[k]) ? 0u : 1u;
+  for (u64 g = FQ_TID; g < groups; g += FQ_NTHREADS) {
+    const IdSep16 v = *(const IdSep16 *)(p + head + 16u * g);
+    cnt += idk_separators8(v.lo) + idk_separators8(v.hi);
+  }
+  for (u64 k = tail + FQ_TID; k < n; k += FQ_NTHREADS) cnt += idk_is_lit(p[k]) ? 0u : 1u;
+  cnt = wave_sum64(cnt);
+  if (FQ_LANE == 0) ws[FQ_WAVE_ID] = cnt;
+  FQ_WG_BARRIER();
+  if (FQ_TID == 0) {
+    u64 s = 0;
+    for (u32 w = 0; w < IDK_SEP_WAVES; ++w) s += ws[w];
+    c.sep[tid] = s;
+  }
+}

@@ -127,6 +127,8 @@ FQ_DEV bool wave_any(bool p) { return __ballot(p) != 0ull; }
 FQ_DEV u64 wave_ballot(bool p) { return __ballot(p); }
 FQ_DEV u32 wave_bcast32(u32 v, u32 lane) { return __shfl(v, (int)lane, 64); }
 FQ_DEV u64 wave_bcast64(u64 v, u32 lane) { return __shfl(v, (int)lane, 64); }
+// the value of lane (this lane ^ mask): the step of a butterfly reduction over aligned groups of lanes
+FQ_DEV u32 wave_xor32(u32 v, u32 mask) { return __shfl_xor(v, (int)mask, 64); }
 FQ_DEV u32 uniform32(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
 FQ_DEV u64 uniform64(u64 v) {
   u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
@@ -207,6 +209,7 @@ FQ_DEV bool wave_any(bool p) { return p; }
 FQ_DEV u64 wave_ballot(bool p) { return p ? 1ull : 0ull; }
 FQ_DEV u32 wave_bcast32(u32 v, u32) { return v; }
 FQ_DEV u64 wave_bcast64(u64 v, u32) { return v; }
+FQ_DEV u32 wave_xor32(u32 v, u32) { return v; }
 FQ_DEV u32 uniform32(u32 v) { return v; }
 FQ_DEV u64 uniform64(u64 v) { return v; }
 FQ_DEV u64 touch_load(const u64 *p) { return *p; }

@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DeviceBlock, DeviceColumns, DnaCodec, IdFallback, MetaCodec, QualCodec, parse_fastq, sort_order
+from .codec import DeviceBlock, DeviceColumns, DeviceIds, DnaCodec, IdFallback, MetaCodec, QualCodec, parse_fastq, sort_order
 
 
 def _gpu_groups(rec, device: int, lib_path: Optional[str], stats: Optional[dict] = None):
@@ -34,7 +34,10 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
     and the id kernel on their own HIP streams (host threads inside the C ABI, which releases the GIL), the meta coder on a host
     thread meanwhile.  arrays(idx) may hand back the bases as a codec.DeviceBlock (a block cut on the device, its qualities with
     it): the DNA and quality coders then read it where it lies.  ids_of(idx): the id columns of a block alone (default: from
-    arrays), for the id coder's change-over to the host coder in mid-file (codec.IdFallback); stats then has "id_host_fallback" True."""
+    arrays), for the id coder's change-over to the host coder in mid-file (codec.IdFallback); stats then has "id_host_fallback" True.
+    arrays(idx) may also hand back the ids as a codec.DeviceIds (id lines cut on the device), which the id kernel reads where they
+    lie, or as None: the id job then cuts them itself with ids_of(idx) -- from its own thread, while this one waits for it and
+    touches no column store."""
     from concurrent.futures import ThreadPoolExecutor
     threads = header[4]
     stored = hp.stored_streams(header)
@@ -45,8 +48,16 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
     # of a block coded on the kernel only the index array is kept: a change-over to the host coder in mid-file (codec.IdFallback)
     # cuts its id columns again; a block's first run takes the columns arrays(idx) has cut already
     ids_of = ids_of or (lambda idx: arrays(idx)[2:4])
-    idc = IdFallback(header, device, lib_path, gpu_ids, lambda enc, idx, held: enc.encode_block(*(held or ids_of(idx)), paired)) \
-        if hp.STREAM_ID in stored else None
+
+    def code_ids(enc, idx, held):
+        """held: (DeviceIds, its offsets) for the kernel coder -- the host coder, after a change-over, cuts the block again as it cuts
+        the blocks before it --, (ids, id_off) host arrays, or None"""
+        if held is not None and isinstance(held[0], DeviceIds):
+            if enc.on_device:
+                return enc.encode_block_dev(held[0].ids, held[0].d_off, held[0].off, paired)
+            held = None
+        return enc.encode_block(*(held or ids_of(idx)), paired)
+    idc = IdFallback(header, device, lib_path, gpu_ids, code_ids) if hp.STREAM_ID in stored else None
     qual = QualCodec(header, device=device, lib_path=lib_path) if hp.STREAM_QUALITY in stored else None
     pool = ThreadPoolExecutor(max_workers=3)
     try:
@@ -62,7 +73,7 @@ def encode_blocks(header: bytes, blocks, arrays, sizes_of, paired: bool, device:
                 if qual is not None:
                     jobs[hp.STREAM_QUALITY] = pool.submit(qual.encode_block, quals, off)
             if idc is not None:
-                jobs[hp.STREAM_ID] = pool.submit(idc.run, idx, (ids, id_off))
+                jobs[hp.STREAM_ID] = pool.submit(idc.run, idx, (ids, id_off) if ids is not None else None)
             st = {hp.STREAM_META: meta.encode_block(np.diff(off.astype(np.int64)).astype(np.uint32), paired)}
             for k, f in jobs.items():
                 st[k] = f.result()
@@ -110,29 +121,45 @@ def _first_at_or_after(marks: np.ndarray, start: np.ndarray, stop: np.ndarray) -
     return np.where((k < len(marks)) & (at < stop), at, stop)
 
 
-def _id_lines_fit_the_kernel(ids: np.ndarray, id_off: np.ndarray, id_mode: str) -> bool:
-    """The id kernel's rule (idk_id_lossless / idk_id_instrument / idk_lossless, csrc/fqsx_idk.h) for the id lines `ids` (each
-    with its line feed), in one pass: False if the kernel would answer one of them with IDK_ERR_TOO_LONG.  Lossless mode: the
-    line with its line feed within _ID_LINE_MAX bytes and within _ID_TOKENS_MAX tokens.  Instrument mode: the line within
-    _ID_LINE_MAX; the name -- up to the first '.', ' ' or ':', cut short at a NUL -- within _ID_NAME_MAX bytes; and, as a new
-    name is coded through the lossless path with a terminating NUL, the bytes up to the '.', ' ' or ':' within _ID_TOKENS_MAX
-    tokens with that terminator.  (A line without a name, or with a byte >= 128 where it is coded, is refused by both coders: not a
-    staging matter.)"""
+def _id_maxima_fit(id_mode: str, max_line: int, max_tokens: int, max_name: int, max_name_tokens: int) -> bool:
+    """The id kernel's rule (idk_id_lossless / idk_id_instrument / idk_lossless, csrc/fqsx_idk.h) on the maxima over a file's id
+    lines: False if the kernel would answer one of them with IDK_ERR_TOO_LONG.  Lossless mode: the line with its line feed within
+    _ID_LINE_MAX bytes and within _ID_TOKENS_MAX tokens.  Instrument mode: the line within _ID_LINE_MAX; the name -- up to the
+    first '.', ' ' or ':', cut short at a NUL -- within _ID_NAME_MAX bytes; and, as a new name is coded through the lossless path
+    with a terminating NUL, the bytes up to the '.', ' ' or ':' within _ID_TOKENS_MAX tokens with that terminator.  (A line
+    without a name, or with a byte >= 128 where it is coded, is refused by both coders: not a staging matter.)"""
+    if max_line > _ID_LINE_MAX:
+        return False
+    if id_mode != "instrument":
+        return max_tokens <= _ID_TOKENS_MAX
+    return max_name <= _ID_NAME_MAX and max_name_tokens <= _ID_TOKENS_MAX
+
+
+def _id_line_maxima(ids: np.ndarray, id_off: np.ndarray, names: bool = True):
+    """(longest line, most tokens in a line, longest instrument name, most tokens up to a name's end plus its terminator) of the
+    id lines `ids` (each with its line feed), in one pass: what _id_maxima_fit takes, and what DeviceColumns.id_survey() reports
+    of a resident id column.  The last two are over the lines that have a name; names False: 0 for both, not looked for."""
     off = np.asarray(id_off).astype(np.int64)
     if len(off) < 2:
-        return True
+        return 0, 0, 0, 0
     start, stop = off[:-1], off[1:]
-    if int((stop - start).max()) > _ID_LINE_MAX:
-        return False
     ids = np.asarray(ids)
     seps = np.zeros(len(ids) + 1, dtype=np.int64)
     np.cumsum(~_ID_LITERAL[ids], out=seps[1:])
-    if id_mode != "instrument":
-        return int((seps[stop] - seps[start]).max()) <= _ID_TOKENS_MAX
+    line, tokens = int((stop - start).max()), int((seps[stop] - seps[start]).max())
+    if not names:
+        return line, tokens, 0, 0
     end = _first_at_or_after(np.flatnonzero(_ID_NAME_END[ids]), start, stop)
     named = end < stop
+    if not bool(named.any()):
+        return line, tokens, 0, 0
     name_len = _first_at_or_after(np.flatnonzero(ids == 0), start, end) - start
-    return not bool((named & ((name_len > _ID_NAME_MAX) | (seps[end] - seps[start] + 1 > _ID_TOKENS_MAX))).any())
+    return line, tokens, int(name_len[named].max()), int((seps[end] - seps[start] + 1)[named].max())
+
+
+def _id_lines_fit_the_kernel(ids: np.ndarray, id_off: np.ndarray, id_mode: str) -> bool:
+    """_id_maxima_fit for the id lines `ids` (each with its line feed)"""
+    return _id_maxima_fit(id_mode, *_id_line_maxima(ids, id_off, names=id_mode == "instrument"))
 
 
 def _ids_fit_the_kernel(id_mode: str, *recs) -> bool:
@@ -144,11 +171,12 @@ def _ids_fit_the_kernel(id_mode: str, *recs) -> bool:
 
 def _compress(inputs, ids_fit, threads: int, order: str, genome_size_mbp: int, quality_mode: str, id_mode: str, quality_thr: int, device: int,
               lib_path: Optional[str], as_blocks: bool, gpu_ids: Optional[bool], stats: Optional[dict], resident: bool = False,
-              profile: bool = False):
+              profile: bool = False, resident_ids: bool = False):
     """The file of one input (`fqs e -s`) or of two mate inputs (`fqs e -p`), each a hostpipe.Records, a hostpipe.Columns or
     -- resident -- a codec.DeviceColumns, which all cut a block's columns under the same names: block, ids_of, quals_of, with a
     mate block_pe, ids_of_pe, quals_of_pe (DeviceColumns: block_dev / block_pe_dev, the block cut on the device with its
-    qualities).  ids_fit(): the caller's pre-scan of the id lines, asked if gpu_ids is None.  Returns the file's bytes or
+    qualities; resident_ids: ids_dev / ids_pe_dev too, the id lines cut on the device for the id kernel, and ids_of / ids_of_pe
+    for the host coder).  ids_fit(): the caller's pre-scan of the id lines, asked if gpu_ids is None.  Returns the file's bytes or
     -- as_blocks -- (header, generator of container blocks); resident columns are released behind the last block."""
     paired, c1, mates = len(inputs) == 2, inputs[0], inputs[1:]
     if gpu_ids is None:
@@ -167,9 +195,20 @@ def _compress(inputs, ids_fit, threads: int, order: str, genome_size_mbp: int, q
         name += ("_pe" if paired else "") + dev
         return lambda idx: getattr(c1, name)(*mates, idx)
     block, ids_of, quals_of = cutter("block", "_dev" if resident else ""), cutter("ids_of"), cutter("quals_of")
+    ids_dev = cutter("ids", "_dev")
+
+    def ids_for_the_coder(idx):
+        if id_mode == "none":
+            return None, None
+        if not resident_ids:
+            return ids_of(idx)
+        if not gpu_ids:   # (the host coder: its job cuts and downloads the lines, encode_blocks)
+            return None, None
+        blk = ids_dev(idx)
+        return blk, blk.off
 
     def arrays(idx):
-        ids, id_off = ids_of(idx) if id_mode != "none" else (None, None)
+        ids, id_off = ids_for_the_coder(idx)
         if resident:
             blk = block(idx)
             return blk, blk.off, ids, id_off, None
@@ -219,7 +258,7 @@ def _id_columns_fit_the_kernel(cols: hp.Columns, max_id_line: int, id_mode: str)
 def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: str = "s", genome_size_mbp: int = 3100,
                    quality_mode: str = "illumina_8", id_mode: str = "instrument", quality_thr: int = 20, device: int = 0,
                    lib_path: Optional[str] = None, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None,
-                   max_chunk_bytes: int = 0, resident: bool = False, profile: bool = False):
+                   max_chunk_bytes: int = 0, resident: bool = False, profile: bool = False, resident_ids: bool = False):
     """`fqs e` on FASTQ files: `-s` with one input, `-p` with two (text as bytes / uint8 array, or a path; the defaults are the
     reference's, params.h:53-78).  The text is parsed on the GPU into columns (codec.parse_fastq), the sort pre-pass runs on the
     base column, and the blocks are cut from the columns with vectorised gathers.  Returns what compress_records* return.
@@ -230,14 +269,21 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
     resident: the base and quality columns stay in device memory (codec.DeviceColumns, one store per input) and the blocks are
     cut there; the same bytes.  Neither column comes to the host: sorted order sorts mate 1's store where it lies
     (DeviceColumns.sort_order).  stats then also has "columns" (DeviceColumns.info() per input once the last block is written, with
-    -- profile -- the gather kernel's "kernels")."""
+    -- profile -- the gather kernel's "kernels").
+    resident_ids (with resident; ValueError without): the id column stays in device memory too.  The pre-scan is the stores' id
+    survey, a block's id lines are cut on the device and the id kernel reads them there; no id byte of the input comes to the host
+    unless the host id coder is needed, which then downloads the blocks it codes.  The same bytes.  stats["ids_resident"]
+    says so, and "columns" has the "id_bytes" held."""
+    if resident_ids and not resident:
+        raise ValueError("resident_ids needs resident: the id column stays beside the two others")
     paired = text2_or_path2 is not None
     cols, parse_stats = [], []
     try:
         for src in (text_or_path, text2_or_path2)[:2 if paired else 1]:
             st = {}
             try:
-                cols.append(parse_fastq(src, device=device, lib_path=lib_path, max_chunk_bytes=max_chunk_bytes, stats=st, resident=resident))
+                cols.append(parse_fastq(src, device=device, lib_path=lib_path, max_chunk_bytes=max_chunk_bytes, stats=st, resident=resident,
+                                        resident_ids=resident_ids))
             except ValueError:   # (resident columns cannot hold such a record: parse_fastq stops at its chunk)
                 st["length_mismatch"] = True
             parse_stats.append(st)
@@ -247,9 +293,15 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
             raise ValueError("the mate files hold different numbers of records: %d and %d" % (len(cols[0]), len(cols[1])))
         if stats is not None:
             stats["parse"] = parse_stats
-        return _compress(cols, lambda: all(_id_columns_fit_the_kernel(c, st["max_id_line"], id_mode) for c, st in zip(cols, parse_stats)),
-                         threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr, device, lib_path, as_blocks, gpu_ids, stats,
-                         resident, profile)
+            stats["ids_resident"] = resident_ids
+
+        def ids_fit():
+            if resident_ids:   # (the survey kernel on every store: the maxima alone come to the host)
+                return all(_id_maxima_fit(id_mode, sv["max_line"], sv["max_tokens"], sv["max_name"], sv["max_name_tokens"])
+                           for sv in (c.id_survey() for c in cols))
+            return all(_id_columns_fit_the_kernel(c, st["max_id_line"], id_mode) for c, st in zip(cols, parse_stats))
+        return _compress(cols, ids_fit, threads, order, genome_size_mbp, quality_mode, id_mode, quality_thr, device, lib_path, as_blocks, gpu_ids,
+                         stats, resident, profile, resident_ids)
     except BaseException:
         if resident:
             for c in cols:
@@ -289,13 +341,16 @@ def main(argv=None) -> int:
     ap.add_argument("-device", type=int, default=0)
     ap.add_argument("-lib", default=None, help="path of the library to load (default: the package's libfqsx.so)")
     ap.add_argument("-resident", action="store_true", help="keep the base and quality columns in device memory and cut the blocks there")
+    ap.add_argument("-resident-ids", dest="resident_ids", action="store_true",
+                    help="keep the id column in device memory too and cut the id lines there (implies -resident)")
     ap.add_argument("inputs", nargs="+")
     a = ap.parse_args(argv)
     if len(a.inputs) != (2 if a.paired else 1):
         ap.error("-p takes two input files, -s one")
     header, blocks = compress_fastq(a.inputs[0], a.inputs[1] if a.paired else None, threads=min(max(a.t, 1), 64), order=a.om,
                                     genome_size_mbp=min(max(a.gs, 1), 32768), quality_mode=_QM[a.qm], id_mode=_IM[a.im], quality_thr=a.qt,
-                                    device=a.device, lib_path=a.lib, as_blocks=True, resident=a.resident)
+                                    device=a.device, lib_path=a.lib, as_blocks=True, resident=a.resident or a.resident_ids,
+                                    resident_ids=a.resident_ids)
     with open(a.out, "wb") as f:
         for chunk in hp.fqs_chunks(header, blocks):   # block by block: the file is never held whole
             f.write(chunk)

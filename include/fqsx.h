@@ -278,6 +278,15 @@ typedef struct fqsx_idg fqsx_idg;
 int fqsx_idg_create(const uint8_t *header17, int device, fqsx_idg **out);
 int fqsx_idg_encode_block(fqsx_idg *, const uint8_t *ids, const uint64_t *id_off, uint32_t n_reads, int paired,
                           const uint8_t **streams, uint64_t *lens);
+/* fqsx_idg_encode_block for a block that lies in device memory, as fqsx_cols_gather_ids leaves it: d_ids = the id lines back to
+ * back in a buffer with 64 spare bytes behind them, d_id_off = their n_reads + 1 offsets there, h_id_off = the same offsets on
+ * the host.  The same streams, errors, fqsx_idg_error_kind and table sizes (fqsx_idg_stats [4], [5]) as fqsx_idg_encode_block
+ * on the same ids: what that call counts on the host to size its model tables, the separators of every worker's lines, a
+ * kernel counts here (one workgroup per worker, one transfer of T counts).  Everything runs on the codec's stream: the caller
+ * guarantees that the stream that wrote the buffers is drained (fqsx_cols_gather_ids returns so) and keeps them until the call
+ * returns.  fqsx_idg_separator_times (after fqsx_idg_set_profiling): out[0] / out[1] milliseconds and launches of that kernel. */
+int fqsx_idg_encode_block_dev(fqsx_idg *, const uint8_t *d_ids, const uint64_t *d_id_off, const uint64_t *h_id_off, uint32_t n_reads,
+                              int paired, const uint8_t **streams, uint64_t *lens);
 void fqsx_idg_destroy(fqsx_idg *);
 
 /* Decode one block's id streams: the inverse of fqsx_idg_encode_block / fqsx_id_encode_block, and what the reference's
@@ -320,6 +329,7 @@ int fqsx_idg_error_kind(fqsx_idg *);
 /* Kernel timing of the id coder, as fqsx_qual_set_profiling / fqsx_qual_kernel_times: out[0] = milliseconds, out[1] = launches */
 int fqsx_idg_set_profiling(fqsx_idg *, int enable);
 int fqsx_idg_kernel_times(fqsx_idg *, double out[2]);
+int fqsx_idg_separator_times(fqsx_idg *, double out[2]);
 
 /* Read order of `fqs e -om s` with the string work on the GPU.  Replaces preprocess_se
  * (fqs/application.cpp:349-412: 256 bins by the first four bases, N->T) plus CSortedFASTQFile::sort_reads on every
@@ -372,7 +382,8 @@ int fqsx_fastq_kernel_times(fqsx_fastq *, double out[14]);
 
 /* Device-resident columns (csrc/fqsx_cols.h): a store keeps the base column and the quality column of one input file in
  * device memory, chunk by chunk as the parser produces them -- one allocation per chunk that never moves, so the file is
- * never held twice -- and cuts container blocks out of them by read index.  Ids stay host columns.
+ * never held twice -- and cuts container blocks out of them by read index.  Ids stay host columns unless the store keeps
+ * them too (fqsx_cols_keep_ids).
  * fqsx_cols_info: out[0] records  out[1] bases  out[2] / out[3] device bytes the store holds now / held at most so far.
  * fqsx_fastq_columns_into: what fqsx_fastq_columns does for the chunk indexed last, with the base and quality columns appended
  *   to the store instead of copied to the host; ids[out[2]], id_off, read_off (the chunk's, records + 1 entries from 0) and
@@ -389,13 +400,33 @@ int fqsx_fastq_kernel_times(fqsx_fastq *, double out[14]);
  * fqsx_cols_sort_order: the read order of `fqs e -om s` for the records of the store, computed where they lie: the same
  *   order_out / bin_start as fqsx_sort_order on the same reads.  No read is copied: the sort reads every record through its
  *   device address, and what it allocates on the store (per record 8 address + 4 length + 1 bin + 8 permutations + 4 flags +
- *   4 rank bytes, about 0.5 more for the tiles, 48 per chunk) is handed back before it returns -- also when an allocation
+ *   4 rank bytes, about 0.5 more for the tiles, 72 per chunk) is handed back before it returns -- also when an allocation
  *   fails (FQSX_E_NOMEM; the call can be repeated).  Only the ranks and the bins come to the host, which replays std::sort
  *   per bin as fqsx_sort_order does.  An empty store: bin_start all zero.  info_out (optional): [0] radix passes [1] scratch
  *   bytes allocated at most during the call [2] records [3] 0.  A record outside its chunk: FQSX_E_DEVICE, order_out unwritten.
  * fqsx_cols_download: n_bytes of the store's device memory (a gathered block) to the host.
  * fqsx_cols_kernel_times (after fqsx_cols_set_profiling): out[0] / out[1] milliseconds and launches of the copying gather,
- *   out[2] / out[3] of the checking pass in front of it. */
+ *   out[2] / out[3] of the checking pass in front of it.
+ * fqsx_cols_keep_ids: before the first chunk is appended, makes the store keep the id column beside the two others; afterwards
+ *   FQSX_E_ARG, the store unchanged.  On such a store fqsx_fastq_columns_into gives the chunk's one allocation two more parts,
+ *   each 16-byte aligned -- the chunk's own id_off (records + 1 entries from 0) and its id lines with their line feeds -- and
+ *   the parser writes the lines there; `ids` may then be null, and no id byte comes to the host.  id_off, read_off and plus_len
+ *   come back as before.
+ * fqsx_cols_gather_ids: fqsx_cols_gather for the id column, with the same index semantics (with b the mates' lines interleaved),
+ *   the same check-then-store passes, error texts and return codes.  h_id_off[reads + 1]: the block's id offsets (from 0), which
+ *   the caller knows from the line lengths.  *d_ids (h_id_off[reads] + 64 bytes) and *d_id_off are buffers of store a of their
+ *   own, not the ones of fqsx_cols_gather: a block's bases and its ids are valid at the same time, each until the next gather of
+ *   its kind.  A refused call leaves the previous block's ids and offsets as they were.  The call returns with the stream
+ *   drained.  FQSX_E_ARG if a, or a given b, does not keep ids.
+ * fqsx_cols_id_info: out[0] 1 if the store keeps ids  out[1] the id bytes it holds.
+ * fqsx_cols_id_survey: one kernel over the id lines of all records, for the id kernel's staging limits (fqsx_idg_*):
+ *   out[0] 1 if the store keeps ids  out[1] the id bytes held  out[2] the longest id line, with its line feed  out[3] the most
+ *   tokens in a line (bytes outside [0-9A-Za-z@], the line feed included)  out[4] the longest instrument name among the lines
+ *   that have one (up to the first of '.', ' ', ':', cut short at a NUL)  out[5] the most tokens up to the name's end plus its
+ *   terminator among those lines  out[6], out[7] 0.  A store without ids or without records: all zero apart from out[0].  A
+ *   record outside its chunk or a line outside its chunk's ids: FQSX_E_DEVICE.
+ * fqsx_cols_id_kernel_times (after fqsx_cols_set_profiling): milliseconds and launches of the id gather's checking pass
+ *   (out[0], out[1]), of its copying pass (out[2], out[3]) and of the survey (out[4], out[5]). */
 typedef struct fqsx_cols fqsx_cols;
 int fqsx_cols_create(int device, fqsx_cols **out);
 void fqsx_cols_destroy(fqsx_cols *);
@@ -408,6 +439,12 @@ int fqsx_cols_sort_order(fqsx_cols *, uint32_t *order_out, uint32_t *bin_start /
 int fqsx_cols_download(fqsx_cols *, const void *d_src, void *h_dst, uint64_t n_bytes);
 int fqsx_cols_set_profiling(fqsx_cols *, int enable);
 int fqsx_cols_kernel_times(fqsx_cols *, double out[4]);
+int fqsx_cols_keep_ids(fqsx_cols *);
+int fqsx_cols_gather_ids(fqsx_cols *a, fqsx_cols *b, const uint32_t *idx, uint32_t n, const uint64_t *h_id_off, const uint8_t **d_ids,
+                         const uint64_t **d_id_off);
+int fqsx_cols_id_info(fqsx_cols *, uint64_t out[2]);
+int fqsx_cols_id_survey(fqsx_cols *, uint64_t out[8]);
+int fqsx_cols_id_kernel_times(fqsx_cols *, double out[6]);
 
 /* Columns to FASTQ text on the device (csrc/fqsx_fqtext.h): the text `fqs d` writes for one container block, from the columns
  * the *_decode_block_dev entry points leave in device memory.  Per read: id line (with its line feed) + bases + "\n+\n" +
