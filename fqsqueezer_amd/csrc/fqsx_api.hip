@@ -671,6 +671,13 @@ struct fqsx_dna : DevCtx {   // (a new fqsx_dna() starts with every field zero u
   u32 ins_win, ins_maxmult;           // k_insert_phase: keys per window of the s- / b-mer inserts (FQSX_INS_WINDOW; 0 = all in order, FQSX_INS_PARALLEL=0)
                                       // and the occurrences of one k-mer a window may hold before it goes in order (FQSX_INS_MAXMULT)
   bool part_sender;                   // encoding on one GPU: k_part_sender instead of k_part_count / _scan / _scatter (FQSX_PART_SENDER=0: those)
+  bool defer_coding;                  // single-end sorted encoding on one whole GPU with 2 T <= its compute units: the phases of a block that are
+                                      // followed by another phase leave their models and range coder to k_code_se_sorted on the second stream
+                                      // (FQSX_DEFER_CODING=0: every launch codes itself)
+  u64 gq_entries;                     // entries per worker either queue buffer holds (cfg.gq_cap follows it)
+  u32 gq_test_cap;                    // tests (FQSX_TEST_GQ_CAP=n): 1 + the entries the queues hold whatever the block needs; n = 0: exactly the
+                                      // bound block_prepare computes, without its slack (0: not set)
+  bool cur_defer;                     // the block being processed has phases that defer their coding (block_prepare decides, once)
   u64 vm_own_bytes;   // physical table memory held by this rank
 };
 
@@ -1063,13 +1070,35 @@ int mail_alloc(fqsx_dna *c, u32 kind, u32 cap) {
 }
 
 // one encode / decode launch over segment `seg` (T workgroups), kernel index 0: timed when profiling is on, counted always
-int launch_segment(fqsx_dna *c, bool decode, u32 n_reads, u32 S, u32 seg) {
+// defer (single-end sorted encoding, block_segment decides): the launch leaves its symbols in queue buffer seg & 1, and
+// k_code_se_sorted codes them on the second stream behind it -- counted under kernel index 2, so that index 0 stays one
+// launch per segment.  While profiling it runs on the first stream like everything else (serial, timed).
+int launch_segment(fqsx_dna *c, bool decode, u32 n_reads, u32 S, u32 seg, bool defer = false) {
   EncArgs a;
   a.cfg = c->cfg;
   a.n_reads = n_reads; a.S = S; a.seg = seg; a.pad = (u32)c->k_n[0];   // (launch index: time stamps of the timing build)
-  return dev_launch(c, 0, true, [&] {
+  a.defer = 0; a.seq = 0;
+#ifndef FQSX_EMU
+  const u32 buf = seg & 1u;
+  if (defer) {
+    a.defer = buf + 1;
+    a.seq = (u32)c->k_n[0] + 1;   // (never 0, the tag of a fresh buffer; a block has far fewer launches than 2^32)
+    DEVCHK(dev_side_wait(c, buf));   // the coding kernel that read this buffer two phases ago is done with it
+  }
+#endif
+  int rc = dev_launch(c, 0, true, [&] {
+#ifndef FQSX_EMU
+    if (defer) return fqsx_launch_encode_se_defer(c->stream, a);
+#endif
     return decode ? fqsx_launch_decode(c->stream, a) : c->paired ? fqsx_launch_encode_pe(c->stream, a) : fqsx_launch_encode_se(c->stream, a);
   });
+#ifndef FQSX_EMU
+  if (!rc && defer) {
+    if (c->profiling) rc = dev_launch(c, 2, true, [&] { return fqsx_launch_code_se(c->stream, a); });
+    else if (!(rc = dev_side_launch(c, buf, [&] { return fqsx_launch_code_se(c->side, a); }))) c->k_n[2] += 1;
+  }
+#endif
+  return rc;
 }
 
 // Sizes the per-block buffers and fixes the block's schedule (number of synchronisation points S)
@@ -1083,7 +1112,8 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
   u64 cap_s = (u64)n_reads / T / 2;
   if (S > cap_s) S = cap_s;
   if (S) --S;
-  u64 max_wbases = 0, max_seg_bases = 0, max_seg_reads = 0, max_wreads = 0;
+  u64 max_wbases = 0, max_seg_bases = 0, max_seg_reads = 0, max_wreads = 0, max_defer_entries = 0;
+  DEVCHK(dev_side_join(c));   // (a block that failed half-way may have left coding kernels behind: the buffers below are theirs too)
   std::vector<u64> wbases(T);
   for (u32 t = 0; t < T; ++t) {
     u64 first, last;
@@ -1103,6 +1133,12 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
       if (stop > cur) {
         max_seg_bases = std::max(max_seg_bases, h_off[stop] - h_off[cur]);
         max_seg_reads = std::max(max_seg_reads, stop - cur);
+        // Deferred coding: the queue entries of a phase that is followed by another.  A position of a read is committed once
+        // (code_chunk / code_letter: one entry); the read-head wave's record holds at most FQSX_HD_RAW triples, which the
+        // resolving wave copies; and that wave itself calls rc_encode nowhere in single-end sorted mode -- every small-model
+        // symbol (duplicate flag, N flags, prefix) is coded by the read-head wave, ranks and letters by the models wave -- so
+        // its own calls per read are 0.
+        if (seg < S) max_defer_entries = std::max(max_defer_entries, h_off[stop] - h_off[cur] + (stop - cur) * (FQSX_HD_RAW + 0u));
         cur = stop;
       }
     }
@@ -1136,6 +1172,51 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
     u64 max_len = 0;
     for (u32 i = 0; i < n_reads; ++i) max_len = std::max(max_len, h_off[i + 1] - h_off[i]);
     if (!decode && max_len > FQSX_RD_LDS && (rc = dfit(c, cfg.pe_scr, cfg.pe_scr_cap, max_len + 128, (max_len + max_len / 4 + 128 + 63) & ~63ull, (u64)T * 3, true))) return rc;
+  }
+  // Deferred coding, decided here for the whole block: whether the codec can defer at all is fqsx_dna.defer_coding (defer_possible,
+  // at creation); this block does if it encodes, has a phase that is followed by another, and the codec is not one rank of a sharded world.
+  c->cur_defer = c->defer_coding && !decode && S && c->shard_world == 1 && !cfg.sys_scope;
+#ifndef FQSX_EMU
+  const bool gq_held = c->gq_entries != 0;
+  if (!c->cur_defer && (c->side || gq_held)) {
+    // a block without a deferred phase (in a file: every block from generation 99 on): the second stream and the queues go back,
+    // and the block runs on what a codec that never deferred holds
+    dev_side_close(c);
+    for (u32 b = 0; b < 2; ++b) {
+      GQueue &q = cfg.gq[b];
+      dfree(c, q.key); dfree(c, q.kind); dfree(c, q.rsym); dfree(c, q.n);
+      q = GQueue{};
+    }
+    c->gq_entries = cfg.gq_cap = 0;
+  }
+  if (c->cur_defer && (rc = dev_side_open(c))) return rc;
+#endif
+  if (c->cur_defer) {   // the two coding queues: the largest deferred phase of any worker fits, or the block fails (FQSX_ERR_CQ_FULL)
+    const u64 need = max_defer_entries + 64;
+    const u64 cap = c->gq_test_cap > 1 ? c->gq_test_cap - 1 : c->gq_test_cap == 1 ? std::max<u64>(max_defer_entries, 1)
+                    : need > c->gq_entries ? (need + need / 4 + 63) & ~63ull : c->gq_entries;
+    if (cap != c->gq_entries) {
+      for (u32 b = 0; b < 2; ++b) {   // (handed back and forgotten before their successors are asked for, as dfit)
+        GQueue &q = cfg.gq[b];
+        dfree(c, q.key); dfree(c, q.kind); dfree(c, q.rsym); dfree(c, q.n);
+        q = GQueue{};
+      }
+      c->gq_entries = cfg.gq_cap = 0;
+      for (u32 b = 0; b < 2; ++b) {
+        GQueue &q = cfg.gq[b];
+        if ((rc = dalloc(c, &p, (u64)T * 10 * cap * sizeof(u64), false))) return rc;
+        q.key = (u64 *)p;
+        if ((rc = dalloc(c, &p, (u64)T * cap, false))) return rc;
+        q.kind = (u8 *)p;
+        if ((rc = dalloc(c, &p, (u64)T * cap, false))) return rc;
+        q.rsym = (u8 *)p;
+        if ((rc = dalloc(c, &p, 2 * (u64)T * sizeof(u32), true))) return rc;   // counts and tags, adjacent; tag 0 is no launch's
+        q.n = (u32 *)p;
+        q.tag = (u32 *)p + T;
+      }
+      c->gq_entries = cap;
+      cfg.gq_cap = (u32)cap;
+    }
   }
   // active geometry of the local tables for this block (cleared after every phase)
   cfg.l_b.nb = need_lb / FQSX_BKT; cfg.l_b.stride = need_lb;
@@ -1215,6 +1296,7 @@ int pe_clear_local(fqsx_dna *c);
 int block_recover(fqsx_dna *c, u32 seg) {
   const u32 T = c->T;
   int rc;
+  DEVCHK(dev_side_join(c));   // (block_finish has joined the streams already; the recovery starts from one queue whoever calls it)
   if ((rc = d2h_sync(c, c->h_demand.data(), c->d_demand, (4 * T + 1) * sizeof(u32)))) return rc;
   // paired-end: a phase k_insert_phase posted itself has its pair-table inserts behind it (block_segment's order); one that
   // the bucket kernels posted has not
@@ -1262,7 +1344,11 @@ int block_segment(fqsx_dna *c, u32 seg) {
   DevCfg &cfg = c->cfg;
   int rc;
   {
-    if ((rc = launch_segment(c, decode, n_reads, (u32)S, seg))) return rc;
+    // Deferred coding: a phase that is followed by another one of the block.  Everything else -- the block's last segment
+    // above all, whose launch codes itself from the coder state the coding kernels leave -- comes behind both streams.
+    const bool defer = c->cur_defer && seg < S;
+    if (!defer) DEVCHK(dev_side_join(c));
+    if ((rc = launch_segment(c, decode, n_reads, (u32)S, seg, defer))) return rc;
     // size the global tables for this phase's inserts (exact per-owner demand)
     const u32 part_grid = T * (cfg.mail[0].n_tiles + cfg.mail[1].n_tiles + cfg.mail[2].n_tiles);
     if (!decode && c->part_sender) LAUNCH(c, 2, k_part_sender, 3 * T, FQSX_SND_THREADS, cfg);   // (every source for itself; k_insert_phase checks for growth)
@@ -1324,6 +1410,7 @@ int block_finish(fqsx_dna *c, const u64 *h_off, const u8 **streams, u64 *lens, u
     }
     return bases_out ? d2h_sync(c, bases_out, cfg.dout, h_off[n_reads]) : FQSX_OK;   // (null: the block stays in cfg.dout)
   }
+  DEVCHK(dev_side_join(c));   // (the streams' lengths and the context tables' occupancies are the coding kernels')
   LAUNCH(c, 2, k_finish_block, T, 64, cfg, c->d_lens, c->d_end);
   // ---- results: stream lengths, context-table occupancies (for the next block's sizing) and the error word at once
   {
@@ -1366,6 +1453,23 @@ int encode_block_impl(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u6
     seg = posted;
   }
   return rc;
+}
+
+// Whether this codec's single-end sorted blocks may defer their coding (block_prepare decides per block; nothing is opened or
+// allocated before a block does): the whole GPU to itself -- a codec on a compute-unit partition shares the chip with its
+// neighbours -- and T coding workgroups that find compute units beside T encode workgroups that fill a unit's LDS each.
+bool defer_possible(fqsx_dna *c, u32 n_parts) {
+#ifdef FQSX_EMU
+  (void)c; (void)n_parts;
+  return false;   // (the emulation codes inline)
+#else
+  if (c->cfg.mode != 1 || n_parts > 1) return false;
+  if (const char *e = getenv("FQSX_DEFER_CODING")) if (atoi(e) == 0) return false;
+  if (const char *e = getenv("FQSX_TEST_GQ_CAP")) c->gq_test_cap = (u32)strtoul(e, nullptr, 10) + 1;   // (tests: a queue too small, or without slack)
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) return false;
+  return 2 * c->T <= (u32)ncu;
+#endif
 }
 
 int create_impl(fqsx_dna *c, const u8 *h) {
@@ -1547,6 +1651,7 @@ int fqsx_dna_create_on_partition(const uint8_t *h, int device, uint32_t part, ui
     return rc;
   }
   rc = create_impl(c, h);
+  if (!rc) c->defer_coding = defer_possible(c, n_parts);
   if (!rc && getenv("FQSX_CHUNKED_TABLES") && atoi(getenv("FQSX_CHUNKED_TABLES"))) rc = fqsx_dna_use_chunked_tables(c);
   if (rc) {
     fqsx_dna_destroy(c);
@@ -2285,6 +2390,7 @@ int fqsx_dna_trace(fqsx_dna *c, uint64_t *out, uint32_t max_launches) {
 
 int fqsx_dna_set_profiling(fqsx_dna *c, int enable) {
   if (!c) return FQSX_E_ARG;
+  if (c->side_last >= 0) { DEVCHK(dev_enter(c)); DEVCHK(dev_sync(c)); }   // (a failed block's coding kernels: profiled launches are serial on one stream)
   c->profiling = enable != 0;
   return FQSX_OK;
 }

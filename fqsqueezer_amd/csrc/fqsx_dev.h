@@ -163,6 +163,7 @@ struct InsShared {
 struct EncArgs {
   DevCfg cfg;
   u32 n_reads, S, seg, pad;
+  u32 defer, seq;   // deferred coding (k_encode_se_sorted / k_code_se_sorted): queue buffer + 1 (0: the launch codes itself), the launch's tag
 };
 // A role receives the address of the kernel arguments as an ordinary (vector-register) argument -- the kernarg segment
 // pointer itself is only defined in the kernel function -- and makes it wave-uniform again, so that the arguments are
@@ -237,6 +238,7 @@ struct Wk {
   u32 rec_idx;                          // ... and the read's index within the launch
   bool piped;                           // this wave only resolves; a second wave of the workgroup drains the coding queue
   u32 cq_tail, cq_head;                 // this wave's copy of its own queue index
+  u32 defer;                            // piped wave: its queue entries go to DevCfg.gq[defer - 1] instead of the LDS ring (0: the ring)
   bool rcq;                             // coding steps go to the range-coder queue (another wave runs the coder proper)
   u32 rq_tail;                          // ... this wave's copy of its index
   u64 c_r_sym;                          // coder: ctx_r_sym, the last 8 rank-0 flags (dna.cpp:664-671)
@@ -1182,8 +1184,21 @@ FQ_DEV void rc_encode_rd(Wk &w, u32 freq, u32 cum, u32 tot, double rd) {
 }
 
 // producer side of the coding queue: wait until `need` more entries fit
+// Deferred coding: entry e of this worker's queue in device memory (w.defer != 0; e counts from the launch's first entry)
+FQ_DEV u64 *gq_key(const Wk &w, u32 l, u32 e) { return w.cfg->gq[w.defer - 1].key + ((u64)w.tid * 10 + l) * w.cfg->gq_cap + e; }
+FQ_DEV void gq_kind_rsym(const Wk &w, u32 e, u32 kind, u32 rsym) {
+  const GQueue &q = w.cfg->gq[w.defer - 1];
+  const u64 i = (u64)w.tid * w.cfg->gq_cap + e;
+  q.kind[i] = (u8)kind;
+  q.rsym[i] = (u8)rsym;
+}
 FQ_DEV bool cq_wait_space(Wk &w, u32 need) {
   if (!w.piped) return true;
+  if (w.defer) {   // nobody drains the queue in device memory during the launch: it holds the launch's entries or the block fails
+    if (w.cq_tail + need <= w.cfg->gq_cap) return true;
+    w.err = FQSX_ERR_CQ_FULL;
+    return false;
+  }
   if (w.cq_tail - lds_load_acq(&w.sm->cq_head) + need <= FQSX_CQ) return true;
   TM_BEGIN(t_cq);
   u32 spins = 0;
@@ -1196,7 +1211,7 @@ FQ_DEV bool cq_wait_space(Wk &w, u32 need) {
 }
 FQ_DEV void cq_publish(Wk &w, u32 n) {
   w.cq_tail += n;
-  if (w.piped) lds_store_rel(&w.sm->cq_tail, w.cq_tail);
+  if (w.piped && !w.defer) lds_store_rel(&w.sm->cq_tail, w.cq_tail);   // (deferred: the count goes out once, at the end of the launch)
 }
 // A symbol of a small direct-indexed model: coded right here, or (two-wave kernel) handed to the coder wave as a
 // finished triple so that it keeps its place in the stream.
@@ -1216,10 +1231,16 @@ FQ_DEV void rc_encode(Wk &w, u32 freq, u32 cum, u32 tot) {
   const u32 e = w.cq_tail & (FQSX_CQ - 1);
   FQ_SYNC();
   if (FQ_LANE == 0) {
-    sm->cq_key[0][e] = (u64)freq | ((u64)cum << 32);
-    sm->cq_key[1][e] = tot;
-    sm->cq_kind[e] = SK_RAW;
-    sm->cq_rsym[e] = 5;
+    if (w.defer) {
+      *gq_key(w, 0, w.cq_tail) = (u64)freq | ((u64)cum << 32);
+      *gq_key(w, 1, w.cq_tail) = tot;
+      gq_kind_rsym(w, w.cq_tail, SK_RAW, 5);
+    } else {
+      sm->cq_key[0][e] = (u64)freq | ((u64)cum << 32);
+      sm->cq_key[1][e] = tot;
+      sm->cq_kind[e] = SK_RAW;
+      sm->cq_rsym[e] = 5;
+    }
   }
   FQ_SYNC();
   cq_publish(w, 1);
@@ -2130,9 +2151,14 @@ FQ_DEV void code_letter(Wk &w, u32 pos, u32 sym, u32 read_len) {  // dna.cpp:520
     const u32 e = w.cq_tail & (FQSX_CQ - 1);
     FQ_SYNC();
     if (FQ_LANE == 0) {
-      for (u32 l = 0; l < 10; ++l) w.sm->cq_key[l][e] = lev[l];
-      w.sm->cq_kind[e] = SK_LETTER;
-      w.sm->cq_rsym[e] = (u8)sym;
+      if (w.defer) {
+        for (u32 l = 0; l < 10; ++l) *gq_key(w, l, w.cq_tail) = lev[l];
+        gq_kind_rsym(w, w.cq_tail, SK_LETTER, sym);
+      } else {
+        for (u32 l = 0; l < 10; ++l) w.sm->cq_key[l][e] = lev[l];
+        w.sm->cq_kind[e] = SK_LETTER;
+        w.sm->cq_rsym[e] = (u8)sym;
+      }
     }
     FQ_SYNC();
     cq_publish(w, 1);
@@ -3044,8 +3070,15 @@ FQ_DEV void code_chunk(Wk &w, const u8 *p, u32 size, u32 i0, u32 j0, u32 m, bool
     const u32 e = (w.cq_tail + (j - j0)) & (FQSX_CQ - 1);
     const u32 kind = w.sb->sp_kind[j];
     const u32 nk = kind == SK_LETTER ? 10u : 7u;
+    const u32 kd = kind | (first && j == j0 ? SK_RESET : 0u);
+    if (w.piped && w.defer) {
+      const u32 g = w.cq_tail + (j - j0);
+      for (u32 l = 0; l < nk; ++l) *gq_key(w, l, g) = w.sb->sp_key[l][j];
+      gq_kind_rsym(w, g, kd, w.sb->sp_rsym[j]);
+      continue;
+    }
     for (u32 l = 0; l < nk; ++l) sm->cq_key[l][e] = w.sb->sp_key[l][j];
-    sm->cq_kind[e] = (u8)(kind | (first && j == j0 ? SK_RESET : 0u));
+    sm->cq_kind[e] = (u8)kd;
     sm->cq_rsym[e] = w.sb->sp_rsym[j];
   }
   FQ_SYNC();
@@ -3801,6 +3834,12 @@ FQ_DEV void compress_read_rec(Wk &w, const u8 *p, u32 size, u32 idx, bool has_ne
   if (cq_wait_space(w, n_raw)) {
     for (u32 j = FQ_LANE; j < n_raw; j += FQ_WAVE) {
       const u32 e = (w.cq_tail + j) & (FQSX_CQ - 1);
+      if (w.defer) {
+        *gq_key(w, 0, w.cq_tail + j) = rec->raw[j][0];
+        *gq_key(w, 1, w.cq_tail + j) = rec->raw[j][1];
+        gq_kind_rsym(w, w.cq_tail + j, SK_RAW, 5);
+        continue;
+      }
       sm->cq_key[0][e] = rec->raw[j][0];
       sm->cq_key[1][e] = rec->raw[j][1];
       sm->cq_kind[e] = SK_RAW;
@@ -3980,6 +4019,44 @@ FQ_DEV void rc_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 seg, u
     for (u32 i = 0; i < FQSX_TM_SLOTS && i < 48; ++i) if (w.tm[i]) atomic_add64(&ws->stat[16 + i], w.tm[i]);
 #endif
   }
+  if (w.err) *cfg.err = w.err;
+}
+
+// The feeder wave of the coding kernel (deferred coding): what the resolving wave of encode launch `seq` left in the
+// worker's queue in device memory goes into the LDS ring, up to 64 entries a step, under the producer protocol the
+// resolving wave follows when it fills the ring itself -- the models and range-coder waves behind it do not know the difference.
+FQ_DEV void feeder_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 buf) {
+  Wk w;
+  w.cfg = &cfg;
+  w.sm = sm;
+  w.tid = tid;
+  w.err = 0;
+  w.piped = true;
+  w.defer = 0;
+  w.cq_head = w.cq_tail = 0;
+  for (u32 i = 0; i < FQSX_TM_SLOTS; ++i) w.tm[i] = 0;
+  const GQueue &q = cfg.gq[buf];
+  const u32 cap = cfg.gq_cap;
+  u32 n = uniform32(q.n[tid]);
+  if (n > cap) n = cap;   // (the producer never stores a count beyond the capacity)
+  const u64 *key = q.key + (u64)tid * 10 * cap;
+  const u8 *kinds = q.kind + (u64)tid * cap, *rsyms = q.rsym + (u64)tid * cap;
+  for (u32 i = 0; i < n; i += FQ_WAVE) {
+    const u32 m = n - i < FQ_WAVE ? n - i : FQ_WAVE;
+    if (!cq_wait_space(w, m)) break;
+    for (u32 j = FQ_LANE; j < m; j += FQ_WAVE) {
+      const u32 e = (w.cq_tail + j) & (FQSX_CQ - 1);
+      const u32 kd = kinds[i + j], kind = kd & SK_KIND_MASK;
+      const u32 nk = kind == SK_LETTER ? 10u : kind == SK_RAW ? 2u : 7u;
+      for (u32 l = 0; l < nk; ++l) sm->cq_key[l][e] = key[(u64)l * cap + i + j];
+      sm->cq_kind[e] = (u8)kd;
+      sm->cq_rsym[e] = rsyms[i + j];
+    }
+    FQ_SYNC();
+    cq_publish(w, m);
+  }
+  FQ_SYNC();
+  lds_store_rel(&sm->cq_done, 1u);
   if (w.err) *cfg.err = w.err;
 }
 
@@ -4398,8 +4475,10 @@ FQ_DEV void scout_request_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 me,
 
 // piped: this wave is the resolving half of a multi-wave worker (see coder_segment_body).
 // MODE (dna_mode), DECODE and PIPED are compile-time constants: every kernel holds only the code of its own mode.
-template <int MODE, bool DECODE, bool PIPED>
-FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_reads, u32 S, u32 seg, u32 launch = 0) {
+// DEFER (deferred coding) too: w.defer is the constant 0 in every other instantiation, so the launches that code themselves
+// hold no code for the queue in device memory.
+template <int MODE, bool DECODE, bool PIPED, bool DEFER = false>
+FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_reads, u32 S, u32 seg, u32 launch = 0, u32 defer = 0, u32 seq = 0) {
   constexpr bool decode = DECODE, piped = PIPED;
   Wk w;
   w.cfg = &cfg;
@@ -4429,6 +4508,7 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
   w.rq_early = false;
   w.rq_noscout = false;
   w.cq_head = w.cq_tail = 0;
+  w.defer = piped && DEFER ? uniform32(defer) : 0u;
   w.c_r_sym = 0;
   for (u32 i = 0; i < ST_N; ++i) w.st[i] = 0;
   for (u32 i = 0; i < FQSX_TM_SLOTS; ++i) w.tm[i] = 0;
@@ -4472,8 +4552,13 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
   w.pq_lo[0] = w.pq_lo[1] = 0;
   w.lq_pub[0] = w.lq_pub[1] = 0;
   FQ_SYNC();
-  enc_open(w, ws->rc_low, ws->rc_range, ws->out_len, cfg);
-  w.avg_code = ws->avg_code; w.avg_letters = ws->avg_letters;
+  // (deferred coding: the coder state and the averages are the coding kernel's, and the one of the phase before may still be
+  // writing them -- this wave, which never uses them when piped, does not even read them)
+  if (DEFER) w.avg_code = w.avg_letters = 0;
+  else {
+    enc_open(w, ws->rc_low, ws->rc_range, ws->out_len, cfg);
+    w.avg_code = ws->avg_code; w.avg_letters = ws->avg_letters;
+  }
   for (u32 i = 0; i < 4; ++i) w.s_let[i] = ws->s_letters[i];
   w.hidden = ws->hidden_updates;
   w.ctx_letters = 0; w.cor_pos = 0; w.N_run = 0;
@@ -4539,6 +4624,10 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
     FQ_SYNC();
     lds_store_rel(&sm->cq_done, 1u);
     lds_store_rel(&sm->lq_quit, 1u);
+    if (w.defer && FQ_LANE == 0) {   // the launch's entries are in place (in program order behind them): their number, then the tag
+      cfg.gq[w.defer - 1].n[tid] = w.cq_tail;
+      cfg.gq[w.defer - 1].tag[tid] = seq;
+    }
   }
   ws->cursor = (u32)cur;
   if (!piped) {

@@ -8,6 +8,9 @@
 #ifndef FQSX_EMU
 // Each returns the hipError_t of the launch as an int (0 = hipSuccess).
 int fqsx_launch_encode_se(hipStream_t s, const EncArgs &a);   // dna_mode 0 (original order) and 1 (sorted)
+// (fqsx_k_code.hip) dna_mode 1, deferred coding: the encode launch that leaves its symbols in DevCfg.gq, and their models and range coder
+int fqsx_launch_encode_se_defer(hipStream_t s, const EncArgs &a);
+int fqsx_launch_code_se(hipStream_t s, const EncArgs &a);
 int fqsx_launch_encode_pe(hipStream_t s, const EncArgs &a);   // dna_mode 2 and 3
 int fqsx_launch_decode(hipStream_t s, const EncArgs &a);      // all modes
 #else

@@ -173,6 +173,17 @@ enum { TM_TOTAL = 0, TM_SPEC, TM_FAST, TM_SLOW, TM_POST, TM_READ_HEAD, TM_LQ, TM
 #define FQSX_TM_SLOTS 1   /* (the timers only exist in the diagnostic build) */
 #endif
 
+// Deferred coding (single-end sorted blocks, phases that are followed by another phase): the resolving wave's coding-queue
+// entries of one launch, per worker, in device memory instead of the LDS ring; k_code_se_sorted runs the models and the
+// range coder over them on a second stream while the first goes on with the partition, the inserts and the next phase.
+struct GQueue {
+  u64 *key;                    // [T][10][cap] level-major, as WgShared.cq_key
+  u8 *kind;                    // [T][cap] SK_* | SK_RESET
+  u8 *rsym;                    // [T][cap]
+  u32 *n;                      // [T] entries of the launch that wrote `tag` ...
+  u32 *tag;                    // [T] ... its sequence number (EncArgs.seq), stored last: a skipped launch leaves a stale one
+};
+
 struct DevCfg {
   u32 T, mode;                 // mode 0 = original order, 1 = sorted (params.h:18)
   u32 prefix, pmer, smer, bmer;
@@ -238,6 +249,8 @@ struct DevCfg {
                                // word, [2T+1 .. 4T+1) the sub-tables' occupancies before it, [4T+1 .. 5T+1) pair table, [5T+1] segment + 1
                                // of a phase k_insert_phase itself posted.  An encode launch ends with owner tid's two entry counts zero;
                                // k_part_sender adds the sources' rows to them.
+  GQueue gq[2];                // deferred coding: the two queue buffers (phase parity) ...
+  u32 gq_cap, pad_gq_;         // ... and the entries per worker each holds
 };
 
 // Protocol test switches (DevCfg.dbg).  Which wave settles what depends on wave timing in the product run, so the
@@ -259,4 +272,6 @@ enum {
   FQSX_ERR_PE_READ_TOO_LONG = 7,  // (a mate longer than the scratch lines the host sized for the block: cannot happen)
   FQSX_ERR_DECODE = 8,
   FQSX_ERR_PIPE = 9,              // the coding queue between the two waves of a worker stalled
+  FQSX_ERR_CQ_FULL = 10,          // deferred coding: a launch's symbols do not fit the worker's queue in device memory (nothing is dropped:
+                                  // the worker stops and the block fails)
 };

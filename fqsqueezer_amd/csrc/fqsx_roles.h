@@ -5,9 +5,13 @@
 #pragma once
 #include "fqsx_kernels.h"
 
-template <int MODE> FQ_ROLE void role_resolve(FqArgsP ap) {
+template <int MODE, bool DEFER = false> FQ_ROLE void role_resolve(FqArgsP ap) {
   const EncArgs *a = fq_args(ap);
-  encode_segment_body<MODE, false, true>(a->cfg, fq_wg(), FQ_BLOCK, a->n_reads, a->S, a->seg, a->pad);
+  encode_segment_body<MODE, false, true, DEFER>(a->cfg, fq_wg(), FQ_BLOCK, a->n_reads, a->S, a->seg, a->pad, a->defer, a->seq);
+}
+FQ_ROLE void role_feeder(FqArgsP ap) {   // coding kernel: the queue in device memory into the LDS ring
+  const EncArgs *a = fq_args(ap);
+  feeder_segment_body(a->cfg, fq_wg(), FQ_BLOCK, a->defer - 1);
 }
 FQ_ROLE void role_models(FqArgsP ap) {
   const EncArgs *a = fq_args(ap);
@@ -51,10 +55,11 @@ FQ_DEV bool worker_elsewhere(const EncArgs &a) {
 // been stopped (fqsx_api.hip: phase_skip) -- decided ONCE per workgroup (thread 0 reads the words, every wave branches on
 // the LDS copy after the barrier), so that a word another workgroup of the same launch writes meanwhile cannot send
 // some waves of a worker home and the rest into the hand-off protocol without their partners.
-FQ_DEV bool wg_handoff_init(const EncArgs &a, bool honour_posted) {
+// stale (coding kernel): the worker's queue in device memory is not this launch's -- its encode launch was skipped
+FQ_DEV bool wg_handoff_init(const EncArgs &a, bool honour_posted, bool stale = false) {
   WgShared *sm = fq_wg();
   if (threadIdx.x == 0) {
-    sm->wg_stop = (a.cfg.err[0] | (honour_posted ? a.cfg.err[1] : 0u)) != 0 ? 1u : 0u;
+    sm->wg_stop = (a.cfg.err[0] | (honour_posted ? a.cfg.err[1] : 0u)) != 0 || stale ? 1u : 0u;
     sm->cq_tail = 0; sm->cq_head = 0; sm->cq_done = 0;
     sm->lq_target[0] = sm->lq_target[1] = 0; sm->lq_done[0] = sm->lq_done[1] = 0; sm->lq_quit = 0;
     sm->hd_ready = 0; sm->hd_taken = 0; sm->hd_early = 0;

@@ -28,6 +28,12 @@ struct DevCtx {
   DevStream stream = nullptr;
   DevEvent ev0 = nullptr, ev1 = nullptr;   // around every launch while profiling
   bool profiling = false;
+  // a second stream for work that only has to be finished at a join (dev_side_open; the DNA encoder's deferred coding):
+  // launch k (0 / 1, the two buffers it alternates between) starts behind ev_fork[k], recorded on the first stream, and ends at ev_done[k]
+  DevStream side = nullptr;
+  DevEvent ev_fork[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};   // (timing disabled)
+  bool side_used[2] = {false, false};   // ev_done[k] has been recorded and not yet been seen complete / waited for
+  int side_last = -1;                   // the k of the side stream's last launch while the first stream has not joined it
   double k_ms[3] = {0, 0, 0};   // kernel time per index: 0 encode / decode (the quality and id kernels), 1 insert phase, 2 the rest
   u64 k_n[3] = {0, 0, 0};       // ... and launches timed (the emulation build and fqsx_dna's index 0: every launch)
   std::vector<void *> allocs;
@@ -79,7 +85,69 @@ static int dev_enter(DevCtx *c) {
 }
 static int dev_sync(DevCtx *c) {
   HIPCHK(hipStreamSynchronize(c->stream));
+  if (c->side_last >= 0) {   // (work the first stream has not joined: the host waits for both)
+    HIPCHK(hipStreamSynchronize(c->side));
+    c->side_used[0] = c->side_used[1] = false;
+    c->side_last = -1;
+  }
   return FQSX_OK;
+}
+// ---- the second stream
+static int dev_side_open(DevCtx *c) {
+  if (c->side) return FQSX_OK;
+  HIPCHK(hipStreamCreate(&c->side));
+  for (int k = 0; k < 2; ++k) {
+    HIPCHK(hipEventCreateWithFlags(&c->ev_fork[k], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming));
+  }
+  return FQSX_OK;
+}
+// `launch` (which returns its hipError_t) on the second stream, behind everything the first stream holds so far
+template <class F> static int dev_side_launch(DevCtx *c, u32 k, F &&launch) {
+  HIPCHK(hipEventRecord(c->ev_fork[k], c->stream));
+  HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork[k], 0));
+  const int e = launch();
+  if (e) { g_err = std::string("kernel launch: ") + hipGetErrorString((hipError_t)e); return FQSX_E_HIP; }
+  HIPCHK(hipEventRecord(c->ev_done[k], c->side));
+  c->side_used[k] = true;
+  c->side_last = (int)k;
+  return FQSX_OK;
+}
+// What the first stream launches next comes behind side launch k.  The event is asked first: it is mostly complete, and
+// then the stream is spared the wait.
+static int dev_side_wait(DevCtx *c, u32 k) {
+  if (!c->side_used[k]) return FQSX_OK;
+  const hipError_t q = hipEventQuery(c->ev_done[k]);
+  if (q == hipErrorNotReady) {
+    (void)hipGetLastError();   // ("not ready" is an answer, not a failure to be found by the next launch check)
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_done[k], 0));
+  } else
+    HIPCHK(q);
+  c->side_used[k] = false;
+  return FQSX_OK;
+}
+// ... behind everything the second stream holds (its launches end in order)
+static int dev_side_join(DevCtx *c) {
+  if (c->side_last < 0) return FQSX_OK;
+  const int rc = dev_side_wait(c, (u32)c->side_last);
+  if (rc) return rc;
+  c->side_used[0] = c->side_used[1] = false;
+  c->side_last = -1;
+  return FQSX_OK;
+}
+// the second stream drained and handed back with its events (dev_side_open makes a new one when it is wanted again)
+static void dev_side_close(DevCtx *c) {
+  if (!c->side) return;
+  (void)hipStreamSynchronize(c->side);
+  for (int k = 0; k < 2; ++k) {
+    if (c->ev_fork[k]) (void)hipEventDestroy(c->ev_fork[k]);
+    if (c->ev_done[k]) (void)hipEventDestroy(c->ev_done[k]);
+    c->ev_fork[k] = c->ev_done[k] = nullptr;
+    c->side_used[k] = false;
+  }
+  (void)hipStreamDestroy(c->side);
+  c->side = nullptr;
+  c->side_last = -1;
 }
 static int dev_malloc(void **p, u64 bytes) {
   const hipError_t e = hipMalloc(p, bytes);
@@ -118,11 +186,15 @@ static void pinned_free(void *p) {
 static void dev_drain(DevCtx *c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  if (c->side) (void)hipStreamSynchronize(c->side);
+  c->side_used[0] = c->side_used[1] = false;
+  c->side_last = -1;
 }
 static void dev_destroy_stream(DevCtx *c) {
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipStreamDestroy(c->stream);
+  dev_side_close(c);
 }
 // One launch on the context's stream (`launch` returns its hipError_t).  While profiling it is timed between the two
 // events, waited for, and counted; `count`: counted in any case.
@@ -151,6 +223,7 @@ static int dev_open(DevCtx *c, int device, u32 = 0, u32 = 1) {
 }
 static int dev_enter(DevCtx *) { return FQSX_OK; }
 static int dev_sync(DevCtx *) { return FQSX_OK; }
+static int dev_side_join(DevCtx *) { return FQSX_OK; }   // (there is no second stream)
 static int dev_malloc(void **p, u64 bytes) {
   *p = malloc(bytes);
   if (!*p) { g_err = "host allocation failed"; return FQSX_E_NOMEM; }
