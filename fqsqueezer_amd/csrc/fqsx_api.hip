@@ -1375,7 +1375,7 @@ int block_segment(fqsx_dna *c, u32 seg) {
     LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, 0u, (u32 *)nullptr);
     if ((rc = d2h_small_end(c, c->h_demand.data(), (4 * T + 1) * sizeof(u32)))) return rc;
     if (c->h_demand[2 * T]) {
-      g_err = "device error " + std::to_string(c->h_demand[2 * T]) + " in encode kernel";
+      g_err = "device error " + std::to_string(c->h_demand[2 * T]) + " in decode kernel (block " + std::to_string(c->cur_gen) + ")";   // (only decoding reads the word back here)
       return FQSX_E_DEVICE;
     }
     if ((rc = grow_for_demand(c))) return rc;
@@ -1694,9 +1694,25 @@ int fqsx_dna_encode_block(fqsx_dna *c, const uint8_t *bases, const uint64_t *off
   return encode_block_impl(c, c->d_bases, c->d_off, off, n_reads, generation, streams, lens);
 }
 
+// What the decode kernels index with, checked before anything is sized or launched: read offsets that start at 0 and never
+// descend (the sizing subtracts them, the kernel writes between them), reads below 2^24 bases (the longest the format codes,
+// meta.cpp:69), mates in pairs, a stream pointer wherever there are bytes
+static int decode_args_ok(const fqsx_dna *c, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *off, uint32_t n_reads) {
+  if (c->paired && (n_reads & 1)) { g_err = "paired-end blocks need an even number of reads"; return FQSX_E_ARG; }
+  if (off[0] != 0) { g_err = "read offsets do not start at 0"; return FQSX_E_ARG; }
+  for (uint32_t i = 0; i < n_reads; ++i) {
+    if (off[i + 1] < off[i]) { g_err = "read offsets do not ascend"; return FQSX_E_ARG; }
+    if (off[i + 1] - off[i] >= (1ull << 24)) { g_err = "a read of 2^24 bases or more"; return FQSX_E_ARG; }
+  }
+  for (uint32_t t = 0; t < c->T; ++t)
+    if (lens[t] && !streams[t]) { g_err = "null stream"; return FQSX_E_ARG; }
+  return FQSX_OK;
+}
+
 int fqsx_dna_decode_block(fqsx_dna *c, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *off, uint32_t n_reads,
                           uint32_t generation, uint8_t *bases_out) {
   if (!c || !streams || !lens || !off || !bases_out) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (int bad = decode_args_ok(c, streams, lens, off, n_reads)) return bad;
   DEVCHK(dev_enter(c));
   int rc;
   u64 no = ((u64)n_reads + 1) * sizeof(u64);
@@ -1709,6 +1725,7 @@ int fqsx_dna_decode_block_dev(fqsx_dna *c, const uint8_t *const *streams, const 
                               uint32_t generation, const uint8_t **d_bases_out) {
   if (d_bases_out) *d_bases_out = nullptr;
   if (!c || !streams || !lens || !off || !d_bases_out) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (int bad = decode_args_ok(c, streams, lens, off, n_reads)) return bad;
   DEVCHK(dev_enter(c));
   int rc;
   u64 no = ((u64)n_reads + 1) * sizeof(u64);

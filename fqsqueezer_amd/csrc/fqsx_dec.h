@@ -337,10 +337,13 @@ FQ_DEV void suffix_dec(Wk &w, u8 *codes, u8 *p_out, u32 size, bool original_orde
   }
 }
 
-FQ_DEV void prefix_direct_dec(Wk &w, u8 *codes, u8 *p_out) {  // decompress_prefix_direct, dna.cpp:1347-1381
+// (a read shorter than the prefix -- the encoder codes such reads, padded through rd_sym -- keeps the rest of its prefix in the code
+// line only: the output beyond the read belongs to the next read, of this worker or of its neighbour, and behind a block's last
+// read there is no output at all)
+FQ_DEV void prefix_direct_dec(Wk &w, u8 *codes, u8 *p_out, u32 size) {  // decompress_prefix_direct, dna.cpp:1347-1381
   for (u32 i = 0; i < w.cfg->prefix; ++i) {
     u32 sym = dec_letter(w, codes, i, 0, 0);
-    dec_put(codes, p_out, i, sym);
+    dec_put(codes, i < size ? p_out : nullptr, i, sym);
     if (sym == 4) { sym = 0; w.cor_pos = i; }
     insert_all(w, sym);
   }
@@ -424,7 +427,7 @@ FQ_DEV u64 siv_select_equal(Wk &w, u64 lo, u64 dif, u64 flag) {
   return 0;
 }
 
-FQ_DEV void prefix_sorted_dec(Wk &w, u8 *codes, u8 *p_out) {  // decompress_prefix_sorted, dna.cpp:1384-1514
+FQ_DEV void prefix_sorted_dec(Wk &w, u8 *codes, u8 *p_out, u32 size) {  // decompress_prefix_sorted, dna.cpp:1384-1514
   const DevCfg *cfg = w.cfg;
   WState *ws = w.ws;
   u16 *sb = small_base(w);
@@ -452,6 +455,7 @@ FQ_DEV void prefix_sorted_dec(Wk &w, u8 *codes, u8 *p_out) {  // decompress_pref
     }
     const u64 prev_idx = ws->pmer_prev_cur ? ws->pmer_prev_dir >> (64 - 2 * ws->pmer_prev_cur) : 0;
     const u64 k = siv_select_equal(w, prev_idx, dif, flag);
+    if (w.err) return;   // (the search ran off the vector: no p-mer to go on with)
     w.pm.cur = cfg->pmer;  // the p-mer with index k, as insert_front would build it (dna.cpp:1439-1443)
     w.pm.dir = k << (64 - 2 * cfg->pmer);
     w.pm.rc = 0;
@@ -468,7 +472,7 @@ FQ_DEV void prefix_sorted_dec(Wk &w, u8 *codes, u8 *p_out) {  // decompress_pref
   for (u32 i = 0; i < cfg->pmer; ++i) {
     u32 sym = (u32)km_symbol(w.pm, i);
     if (was_N && sym == 3 && sm_decode(w, sb + SM_OFF_NS + (i + 1) * (SM_NS_N + 1), SM_NS_N, 1u << 12)) sym = 4;
-    dec_put(codes, p_out, i, sym);
+    dec_put(codes, i < size ? p_out : nullptr, i, sym);
     if (sym == 4) { sym = 3; w.N_run++; } else w.N_run = 0;
     km_insert(w.sm_, cfg->gs, sym); km_insert(w.bm, cfg->gb, sym);
     km_insert(w.pm_u, cfg->gp, sym); km_insert(w.sm_u, cfg->gs, sym); km_insert(w.bm_u, cfg->gb, sym);
@@ -491,8 +495,8 @@ FQ_DEV void dec_update_s_letters(Wk &w, const u8 *codes, u32 size) {
 }
 
 // DecompressSE, dna.cpp:1883-1928 (first_of_pair) / the direct second mate of DecompressPE, :2029-2033.
-// prev_out: previous first mate of this worker in the output block (read_prev), or null.
-FQ_DEV bool read_dec(Wk &w, u8 *codes, u8 *p_out, u32 size, const u8 *prev_out, bool first_of_pair) {
+// prev_out / prev_size: previous first mate of this worker in the output block (read_prev), or null / 0.
+FQ_DEV bool read_dec(Wk &w, u8 *codes, u8 *p_out, u32 size, const u8 *prev_out, u32 prev_size, bool first_of_pair) {
   const DevCfg *cfg = w.cfg;
   const bool orig = !first_of_pair || w.mode == 0 || w.mode == 2;
   if (first_of_pair) {
@@ -500,9 +504,12 @@ FQ_DEV bool read_dec(Wk &w, u8 *codes, u8 *p_out, u32 size, const u8 *prev_out, 
     const bool same = sm_decode(w, m, SM_FLAGS_N, 1u << 12) != 0;
     w.ws->ctx_flags = ((w.ws->ctx_flags << 1) + (same ? 1u : 0u)) & 0xff;
     if (same) {
+      // the encoder sets the flag for a read equal to read_prev, which has its length (dna.cpp:1521-1529; an empty read_prev at the
+      // worker's first read).  Any other length is no stream of the format: the copy would take bases from beyond the previous read
+      if (prev_size != size) { w.err = FQSX_ERR_DECODE; return true; }
       FQ_SYNC_MEM();
       for (u32 i = FQ_LANE; i < size; i += FQ_WAVE) {
-        u8 ch = prev_out ? prev_out[i] : (u8)'A';
+        u8 ch = prev_out[i];
         p_out[i] = ch;
         codes[i] = (u8)dna_code(ch);
       }
@@ -514,33 +521,56 @@ FQ_DEV bool read_dec(Wk &w, u8 *codes, u8 *p_out, u32 size, const u8 *prev_out, 
   km_reset(w.pm_u); km_reset(w.sm_u); km_reset(w.bm_u);
   w.cor_pos = 0;
   w.N_run = 0;
-  if (orig) prefix_direct_dec(w, codes, p_out); else prefix_sorted_dec(w, codes, p_out);
+  if (orig) prefix_direct_dec(w, codes, p_out, size); else prefix_sorted_dec(w, codes, p_out, size);
+  if (w.err) return false;
   suffix_dec(w, codes, p_out, size, orig, 0, false, 0);
+  if (first_of_pair && prev_out && prev_size == size && !w.err) {
+    // ... and a read equal to read_prev is coded by the flag alone, never in full (read_head compares a read with the worker's
+    // previous first mate whenever there is one): an encoder of these bases learns nothing from this read, this decoder just
+    // has.  A read with an N is let through: the encoder compares the bytes it was given, and any byte outside ACGT comes back as N.
+    FQ_SYNC_MEM();
+    bool differs = false;
+    for (u32 i = FQ_LANE; i < size; i += FQ_WAVE) differs = differs || p_out[i] != prev_out[i] || p_out[i] == (u8)'N';
+    if (!wave_any(differs)) { w.err = FQSX_ERR_DECODE; return false; }
+  }
   dec_update_s_letters(w, codes, size);
   return false;
 }
 
 // DecompressPE, dna.cpp:1931-2044
-FQ_DEV void pair_dec(Wk &w, u8 *codes, u8 *rcodes, u8 *p1, u32 size1, u8 *p2, u32 size2, const u8 *prev_out) {
+// a minimizer window cut to the mate (windows of a mate shorter than the b-mer start before it or end behind it)
+FQ_DEV void dec_window(int &off, int &size, u32 n) {
+  if (off < 0) { size += off; off = 0; }
+  if (size > (int)n - off) size = (int)n - off;
+}
+FQ_DEV u64 dec_minimizer(const DevCfg *cfg, const u8 *codes, int off, int size, u32 n) {
+  dec_window(off, size, n);
+  return pe_find_minimizer(cfg, codes, off, size);
+}
+FQ_DEV u64 dec_maximizer(const DevCfg *cfg, const u8 *codes, int off, int size, u32 n) {
+  dec_window(off, size, n);
+  return pe_find_maximizer(cfg, codes, off, size);
+}
+FQ_DEV void pair_dec(Wk &w, u8 *codes, u8 *rcodes, u8 *p1, u32 size1, u8 *p2, u32 size2, const u8 *prev_out, u32 prev_size) {
   const DevCfg *cfg = w.cfg;
   WgShared *sm = w.sm;
   const int k = (int)cfg->bmer;
   const u64 vm = pe_value_mask(cfg);
-  read_dec(w, codes, p1, size1, prev_out, true);
+  read_dec(w, codes, p1, size1, prev_out, prev_size, true);
   if (w.err) return;
   u64 m1[4], a1[3], x1;
   {
     int mss = (int)size1 - k + 1, s1 = mss / 4, s2 = 2 * mss / 4, s3 = 3 * mss / 4;
-    m1[0] = pe_find_minimizer(cfg, codes, 0, s1 + k - 1);
-    m1[1] = pe_find_minimizer(cfg, codes, s1, s2 - s1 + k - 1);
-    m1[2] = pe_find_minimizer(cfg, codes, s2, s3 - s2 + k - 1);
-    m1[3] = pe_find_minimizer(cfg, codes, s3, (int)size1 - s3);
+    m1[0] = dec_minimizer(cfg, codes, 0, s1 + k - 1, size1);
+    m1[1] = dec_minimizer(cfg, codes, s1, s2 - s1 + k - 1, size1);
+    m1[2] = dec_minimizer(cfg, codes, s2, s3 - s2 + k - 1, size1);
+    m1[3] = dec_minimizer(cfg, codes, s3, (int)size1 - s3, size1);
     int a = mss / 3, b = 2 * mss / 3;
-    a1[0] = pe_find_minimizer(cfg, codes, 0, a + k - 1);
-    a1[1] = pe_find_minimizer(cfg, codes, a, b - a + k - 1);
-    a1[2] = pe_find_minimizer(cfg, codes, b, (int)size1 - b);
+    a1[0] = dec_minimizer(cfg, codes, 0, a + k - 1, size1);
+    a1[1] = dec_minimizer(cfg, codes, a, b - a + k - 1, size1);
+    a1[2] = dec_minimizer(cfg, codes, b, (int)size1 - b, size1);
     int mid1 = ((int)size1 + k) / 2;
-    x1 = (~pe_find_maximizer(cfg, codes, mid1 - k + 1, (int)size1 - (mid1 - k + 1))) & vm;
+    x1 = (~dec_maximizer(cfg, codes, mid1 - k + 1, (int)size1 - (mid1 - k + 1), size1)) & vm;
   }
   u32 nc = 0;
   for (u32 i = 0; i < 4; ++i) ptab_find(w, cfg->g_pe, pe_owner(cfg, murmur64(m1[i])), m1[i], nc);
@@ -549,9 +579,10 @@ FQ_DEV void pair_dec(Wk &w, u8 *codes, u8 *rcodes, u8 *p1, u32 size1, u8 *p2, u3
   u32 mid = 0, mpos = 0;
   u16 *sb = small_base(w);
   if (nc) {
-    pe_merge_candidates(w, nc);
+    const u32 ntop = pe_merge_candidates(w, nc);
     mid = sm_decode(w, sb + SM_OFF_MID, SM_NIB_N, 1u << 15);
     if (mid == 15) direct = true;
+    else if (mid >= ntop) { w.err = FQSX_ERR_DECODE; return; }   // (no such candidate: pe_top[mid] is what an earlier pair left there)
     else {
       u8 *bi = cfg->byte_init + (u64)w.tid * SM_LAZY_ENTRIES + SM_BYTE_ENTRIES;
       u16 *mp = sb + SM_OFF_MPOS;
@@ -563,7 +594,7 @@ FQ_DEV void pair_dec(Wk &w, u8 *codes, u8 *rcodes, u8 *p1, u32 size1, u8 *p2, u3
     }
   }
   // second mate decoded into the same code line (the first mate's codes are no longer needed)
-  if (direct) read_dec(w, codes, p2, size2, nullptr, false);
+  if (direct) read_dec(w, codes, p2, size2, nullptr, 0, false);
   else {
     // DecompressDirectWithMinim, dna.cpp:1641-1713: the anchor b-mer is candidate `mid`
     if (mpos + (u32)k > size2) { w.err = FQSX_ERR_DECODE; return; }
@@ -584,11 +615,11 @@ FQ_DEV void pair_dec(Wk &w, u8 *codes, u8 *rcodes, u8 *p1, u32 size1, u8 *p2, u3
   u64 a2[3], x2;
   {
     int mss = (int)size2 - k + 1, a = mss / 3, b = 2 * mss / 3;
-    a2[0] = pe_find_minimizer(cfg, codes, 0, a + k - 1);
-    a2[1] = pe_find_minimizer(cfg, codes, a, b - a + k - 1);
-    a2[2] = pe_find_minimizer(cfg, codes, b, (int)size2 - b);
+    a2[0] = dec_minimizer(cfg, codes, 0, a + k - 1, size2);
+    a2[1] = dec_minimizer(cfg, codes, a, b - a + k - 1, size2);
+    a2[2] = dec_minimizer(cfg, codes, b, (int)size2 - b, size2);
     int mid2 = ((int)size2 + k) / 2;
-    x2 = (~pe_find_minimizer(cfg, codes, mid2 - k + 1, (int)size2 - (mid2 - k + 1))) & vm;
+    x2 = (~dec_minimizer(cfg, codes, mid2 - k + 1, (int)size2 - (mid2 - k + 1), size2)) & vm;
   }
   pe_push(w, a1[0], a2[0], 2); pe_push(w, a1[0], a2[2], 4); pe_push(w, a1[0], x1, 1);
   pe_push(w, a1[1], a2[0], 3); pe_push(w, a1[1], a2[2], 3);

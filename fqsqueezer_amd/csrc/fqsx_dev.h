@@ -2189,6 +2189,7 @@ FQ_DEV void insert_all(Wk &w, u64 sym) {
   km_insert(w.pm_u, cfg->gp, sym); km_insert(w.sm_u, cfg->gs, sym); km_insert(w.bm_u, cfg->gb, sym);
 }
 
+enum { FQSX_RD_PAD = 32 };   // beyond every prefix and p-mer length (fqsx_dna_create: pmer <= 18, prefix < pmer)
 FQ_DEV u32 rd_sym(Wk &w, const u8 *p, u32 i, u32 size) { return size <= FQSX_RD_LDS ? (u32)w.rdp[i] : dna_code(p[i]); }
 
 FQ_DEV void prefix_direct(Wk &w, const u8 *p, u32 size) {  // compress_prefix_direct, dna.cpp:506-546
@@ -3779,6 +3780,12 @@ FQ_DEV bool read_head(Wk &w, const u8 *p, u32 size, const u8 *prev, u32 prev_siz
     if (i < FQSX_RD_LDS) w.rdp[i] = (u8)c;
     h0 += c == 0; h1 += c == 1; h2 += c == 2; h3 += c == 3;
   }
+  // a read shorter than the prefix (sorted: than the p-mer): prefix_direct / prefix_sorted take the missing positions through
+  // rd_sym from this line, which the read has not staged -- they are code 0 (the decoder takes back whatever is coded and keeps
+  // what lies inside the read), not what an earlier read or an earlier kernel left in LDS: bytes above 4 among them are no symbol
+  // of the letter models.  (N there would make the sorted prefix of an empty read a p-mer of N flags, which the decoder refuses.)
+  if (size < FQSX_RD_PAD)
+    for (u32 i = size + FQ_LANE; i < FQSX_RD_PAD; i += FQ_WAVE) w.rdp[i] = 0;
   FQ_SYNC();
   hist[0] = wave_sum32(h0); hist[1] = wave_sum32(h1); hist[2] = wave_sum32(h2); hist[3] = wave_sum32(h3);
   bool same = !wave_any(diff);
@@ -4576,9 +4583,14 @@ FQ_DEV void encode_segment_body(const DevCfg &cfg, WgShared *sm, u32 tid, u32 n_
     for (u64 i = cur; i < stop && !w.err; i += paired ? 2 : 1) {
       const u64 o0 = cfg.read_off[i], o1 = cfg.read_off[i + 1];
       const u8 *prev_out = nullptr;
-      if (i > first) prev_out = cfg.dout + cfg.read_off[i - (paired ? 2 : 1)];
-      if (!paired) read_dec(w, codes, cfg.dout + o0, (u32)(o1 - o0), prev_out, true);
-      else if (i + 1 < stop) pair_dec(w, codes, rcodes, cfg.dout + o0, (u32)(o1 - o0), cfg.dout + o1, (u32)(cfg.read_off[i + 2] - o1), prev_out);
+      u32 prev_size = 0;
+      if (i > first) {
+        const u64 q0 = cfg.read_off[i - (paired ? 2 : 1)];
+        prev_out = cfg.dout + q0;
+        prev_size = (u32)(cfg.read_off[i - (paired ? 1 : 0)] - q0);
+      }
+      if (!paired) read_dec(w, codes, cfg.dout + o0, (u32)(o1 - o0), prev_out, prev_size, true);
+      else if (i + 1 < stop) pair_dec(w, codes, rcodes, cfg.dout + o0, (u32)(o1 - o0), cfg.dout + o1, (u32)(cfg.read_off[i + 2] - o1), prev_out, prev_size);
     }
     ws->dec_pos = w.din_pos;
     ws->dec_buffer = w.dec.buf;

@@ -93,7 +93,14 @@ int fqsx_dna_encode_block_dev(fqsx_dna *, const uint8_t *d_bases, const uint64_t
  * decoder workers, fqs/application.cpp:874-917 with CDNACompressor::DecompressSE / DecompressPE,
  * fqs/dna.h:277-278).  streams[w]/lens[w] = worker w's DNA stream of the block (host memory), read_off =
  * n_reads+1 offsets of the reads inside bases_out (the read lengths come from the meta stream).  A codec
- * instance is used either for encoding or for decoding a file, never both. */
+ * instance is used either for encoding or for decoding a file, never both.
+ * Refused with FQSX_E_ARG before anything is launched, the codec unchanged: offsets that do not start at 0 or descend, a read of
+ * 2^24 bases or more, an odd n_reads in a paired mode, a null stream with a length.
+ * A stream that leaves the format ("Where a DNA stream leaves the format") or runs a table or mailbox over:
+ * FQSX_E_DEVICE ("device error 8 in decode kernel" for the former); nothing outside bases_out[0 .. read_off[n_reads]) is written
+ * and the call returns.  A damaged stream can also decode to bases without an error: the range decoder has no check sum.
+ * After FQSX_E_DEVICE the codec's tables, models and contexts are partly updated with what the block decoded up to the error:
+ * the only call that may follow on it is fqsx_dna_destroy, and the file is decoded again from its first block with a new codec. */
 int fqsx_dna_decode_block(fqsx_dna *, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off,
                           uint32_t n_reads, uint32_t generation, uint8_t *bases_out);
 

@@ -181,6 +181,7 @@ static inline u64 murmur64(u64 h) {  // ht_kmer.h:123-127, context_hm.h:81-85
 struct Counters {
   u64 probes = 0, slots = 0, inserts = 0, siv_words = 0, ctx = 0, coded = 0, lprobes = 0, linserts = 0;
   u64 lv[6] = {0, 0, 0, 0, 0, 0};   // find_counts results per counts_level_t (none, pmer, smer, bmer, mixed, bmer_unc)
+  u64 anchor[3] = {0, 0, 0};        // anchored second mates whose position took 1 / 3 / 4 symbols (dna.cpp:1840-1868, :1985-2001)
 };
 
 struct KTable {
@@ -738,6 +739,8 @@ struct Worker {
   u64 hidden_updates = 0;
   std::vector<u8> read_prev;
   u32 pmer_mod_shift;
+  bool have_prev = false;   // read_prev holds a first mate of this block (an empty one included)
+  bool bad = false;   // decoding: the stream left the format ("Where a DNA stream leaves the format"); the block is given up
 
   void init(Shared *s, u32 tid_) {  // CDNACompressor::Init, dna.cpp:95-174; SetKmerDS :2356-2390
     sh = s; tid = tid_;
@@ -950,12 +953,12 @@ struct Worker {
     return (u8)find_leveled(m_letters, lev, 9, t_letters, avg_letters, LETTERS_THR)->encode(rc, sym, &sh->cnt.coded);
   }
 
-  void prefix_direct(u8 *p) {  // compress_prefix_direct, dna.cpp:506-546 (start_pos == 0); decompress_prefix_direct :1347-1381
+  void prefix_direct(u8 *p, u32 size) {  // compress_prefix_direct, dna.cpp:506-546 (start_pos == 0); decompress_prefix_direct :1347-1381
     ctx_letters = ~0ull;
     for (u32 i = 0; i < sh->kl.prefix; ++i) {
       u8 sym = rc.dec ? 0 : (u8)dna_code(p[i]);
       sym = code_letter(i, sym, 0);
-      if (rc.dec) p[i] = alpha(sym);
+      if (rc.dec && i < size) p[i] = alpha(sym);   // (a read shorter than the prefix: no encoder writes one; nothing is stored beyond it)
       ctx_letters = (ctx_letters << 4) + sym;
       if (sym == 4) { sym = 0; cor_pos = i; }
       pmer.insert(sym); smer.insert(sym); bmer.insert(sym);
@@ -1007,7 +1010,7 @@ struct Worker {
     push_p(pmer.aligned_rc());
   }
 
-  void prefix_sorted_dec(u8 *p) {  // decompress_prefix_sorted, dna.cpp:1384-1514
+  void prefix_sorted_dec(u8 *p, u32 size) {  // decompress_prefix_sorted, dna.cpp:1384-1514
     u64 *nc = &sh->cnt.coded;
     bool was_N = m_Ns.get(0, t_Ns)->encode(rc, 0, nc) != 0;
     ctx_ps_flags = ((ctx_ps_flags << 1) + (u64)was_N) & 0xffff;
@@ -1026,8 +1029,11 @@ struct Worker {
           dif += (u64)m_bytes.get((flag << 24) + (nb << 16) + (hi_byte << 8) + (u64)i, t_bytes)->encode(rc, 0, nc) << (i * 8);
       }
       u64 k = pmer_prev.aligned_dir() + 1;
-      for (u64 j = 0; j <= dif; ++k)
+      const u64 n_fields = 1ull << sh->siv.key_bits;
+      for (u64 j = 0; j <= dif; ++k) {
+        if (k >= n_fields) { bad = true; return; }   // fewer fields of that value behind the previous p-mer than the stream skips
         if (sh->siv.test(k) == flag) ++j;
+      }
       --k;
       for (u32 i = 0; i < sh->kl.pmer; ++i) { pmer.insert_front(k & 3); k >>= 2; }
     } else if (pmer_prev.full())
@@ -1039,8 +1045,8 @@ struct Worker {
     ctx_letters = ~0ull;
     for (u32 i = 0; i < sh->kl.pmer; ++i) {
       u8 sym = (u8)pmer.symbol(i);
-      p[i] = alpha(sym);
-      if (was_N && sym == 3 && m_Ns.get((u64)i + 1, t_Ns)->encode(rc, 0, nc)) { p[i] = 'N'; sym = 4; }
+      if (was_N && sym == 3 && m_Ns.get((u64)i + 1, t_Ns)->encode(rc, 0, nc)) sym = 4;
+      if (i < size) p[i] = alpha(sym);
       ctx_letters = (ctx_letters << 4) + sym;
       if (sym == 4) { sym = 3; N_run++; } else N_run = 0;
       smer.insert(sym); bmer.insert(sym);
@@ -1147,18 +1153,27 @@ struct Worker {
       same = m_flags.get(ctx_flags, t_flags)->encode(rc, same, &sh->cnt.coded) != 0;
       ctx_flags = ((ctx_flags << 1) + (u64)same) & 0xff;
       if (same) {
-        if (rc.dec) memcpy(p, read_prev.data(), std::min<size_t>(size, read_prev.size()));
+        if (rc.dec) {   // (the encoder sets the flag for a read equal to read_prev, length included)
+          if (read_prev.size() != size) { bad = true; return true; }
+          if (size) memcpy(p, read_prev.data(), size);
+          have_prev = true;
+        }
         return true;
       }
     }
     pmer.reset(); smer.reset(); bmer.reset();
     pmer_u.reset(); smer_u.reset(); bmer_u.reset();
     cor_pos = 0; N_run = 0;
-    if (original_order) prefix_direct(p);
-    else if (rc.dec) prefix_sorted_dec(p);
+    if (original_order) prefix_direct(p, size);
+    else if (rc.dec) prefix_sorted_dec(p, size);
     else prefix_sorted(p);
+    if (bad) return false;
     suffix(p, size, original_order);
-    if (first_of_pair) read_prev.assign(p, p + size);
+    // decoding: a read equal to the worker's previous first mate is coded by the flag alone, never in full (one with an N is let
+    // through: the encoder compares the bytes it was given, and any byte outside ACGT comes back as N); have_prev: the device
+    // encoder compares only where the worker has a previous read in the block
+    if (rc.dec && first_of_pair && have_prev && read_prev.size() == size && !memchr(p, 'N', size) && (size == 0 || !memcmp(read_prev.data(), p, size))) { bad = true; return false; }
+    if (first_of_pair) { read_prev.assign(p, p + size); have_prev = true; }
     update_s_letters(p, size);
     return false;
   }
@@ -1173,6 +1188,14 @@ struct Worker {
     void insert(u64 s) { v = ((v << 2) | s) & ((1ull << (2 * k)) - 1ull); if (cur < k) ++cur; }
     bool full() const { return cur == k; }
   };
+  // a window [off, off + size) of a mate of n bases, cut to the mate (only a mate shorter than the b-mer has windows that
+  // start before it or end behind it)
+  static void window(int &off, int &size, u32 n) {
+    if (off < 0) { size += off; off = 0; }
+    if (size > (int)n - off) size = (int)n - off;
+  }
+  u64 find_minimizer(const u8 *p, u32 n, int off, int size) const { window(off, size, n); return find_minimizer(p + off, size); }
+  u64 find_maximizer(const u8 *p, u32 n, int off, int size) const { window(off, size, n); return find_maximizer(p + off, size); }
   u64 find_minimizer(const u8 *p, int size) const {  // dna.cpp:999-1023
     DirK b; b.k = sh->kl.bmer;
     u64 best = sh->pe.value_mask;
@@ -1216,8 +1239,8 @@ struct Worker {
     v_minim_cand.clear();
     int k = (int)sh->kl.bmer, mss = (int)size - k + 1;
     int sp1 = mss / 4, sp2 = 2 * mss / 4, sp3 = 3 * mss / 4;
-    u64 m[4] = {find_minimizer(p, sp1 + k - 1), find_minimizer(p + sp1, sp2 - sp1 + k - 1),
-                find_minimizer(p + sp2, sp3 - sp2 + k - 1), find_minimizer(p + sp3, (int)size - sp3)};
+    u64 m[4] = {find_minimizer(p, size, 0, sp1 + k - 1), find_minimizer(p, size, sp1, sp2 - sp1 + k - 1),
+                find_minimizer(p, size, sp2, sp3 - sp2 + k - 1), find_minimizer(p, size, sp3, (int)size - sp3)};
     for (int i = 0; i < 4; ++i) sh->pe.find(m[i], v_minim_cand);
     for (int i = 0; i < 4; ++i) lpe.find(m[i], v_minim_cand);
     if (v_minim_cand.empty()) return false;
@@ -1261,12 +1284,12 @@ struct Worker {
   void append_pe_mers3(const u8 *p1, u32 size1, const u8 *p2, u32 size2) {  // dna.cpp:1053-1136
     const int k = (int)sh->kl.bmer;
     int mss = (int)size1 - k + 1, a = mss / 3, b = 2 * mss / 3;
-    u64 m11 = find_minimizer(p1, a + k - 1), m12 = find_minimizer(p1 + a, b - a + k - 1), m13 = find_minimizer(p1 + b, (int)size1 - b);
+    u64 m11 = find_minimizer(p1, size1, 0, a + k - 1), m12 = find_minimizer(p1, size1, a, b - a + k - 1), m13 = find_minimizer(p1, size1, b, (int)size1 - b);
     mss = (int)size2 - k + 1; a = mss / 3; b = 2 * mss / 3;
-    u64 m21 = find_minimizer(p2, a + k - 1), m22 = find_minimizer(p2 + a, b - a + k - 1), m23 = find_minimizer(p2 + b, (int)size2 - b);
+    u64 m21 = find_minimizer(p2, size2, 0, a + k - 1), m22 = find_minimizer(p2, size2, a, b - a + k - 1), m23 = find_minimizer(p2, size2, b, (int)size2 - b);
     int mid1 = ((int)size1 + k) / 2, mid2 = ((int)size2 + k) / 2;
-    u64 x1 = find_maximizer(p1 + mid1 - k + 1, (int)size1 - (mid1 - k + 1));
-    u64 x2 = find_minimizer(p2 + mid2 - k + 1, (int)size2 - (mid2 - k + 1));  // sic: minimizer (quirk 6)
+    u64 x1 = find_maximizer(p1, size1, mid1 - k + 1, (int)size1 - (mid1 - k + 1));
+    u64 x2 = find_minimizer(p2, size2, mid2 - k + 1, (int)size2 - (mid2 - k + 1));  // sic: minimizer (quirk 6)
     x1 = (~x1) & sh->pe.value_mask;
     x2 = (~x2) & sh->pe.value_mask;
     pe_push(m11, m21, 2); pe_push(m11, m23, 4); pe_push(m11, x1, 1);
@@ -1279,14 +1302,17 @@ struct Worker {
   void decompress_pair(u8 *p1, u32 size1, u8 *p2, u32 size2, bool original_order) {  // DecompressPE, dna.cpp:1931-2044
     u64 *nc = &sh->cnt.coded;
     compress_read(p1, size1, original_order, true);
+    if (bad) return;
     bool found = find_minim_cand(p1, size1);
     bool direct = !found;
     u32 mid = 0, mpos = 0;
     if (found) {
       mid = m_minim_id.encode(rc, 0, nc);
       if (mid == 15) direct = true;
+      else if (mid >= v_minim_top.size()) { bad = true; return; }   // no such candidate
       else {
         mpos = m_minim_pos.get((u64)mid, t_minim_pos)->encode(rc, 0, nc);
+        sh->cnt.anchor[mpos == 254 ? 1 : mpos == 255 ? 2 : 0] += 1;
         if (mpos == 254) {
           mpos = m_minim_pos.get((u64)mid + 0x100, t_minim_pos)->encode(rc, 0, nc) << 8;
           mpos += m_minim_pos.get((u64)mid + 0x200, t_minim_pos)->encode(rc, 0, nc);
@@ -1298,7 +1324,9 @@ struct Worker {
       }
     }
     if (direct) compress_read(p2, size2, true, false);
+    else if ((u64)mpos + sh->kl.bmer > size2) { bad = true; return; }   // the anchor does not lie inside the mate
     else compress_with_minim(p2, size2, mpos, v_minim_top[mid] & sh->pe.value_mask);
+    if (bad) return;
     append_pe_mers3(p1, size1, p2, size2);
   }
   void compress_pair(u8 *p1, u32 size1, u8 *p2, u32 size2, bool original_order) {  // CompressPE, dna.cpp:1790-1880
@@ -1329,6 +1357,7 @@ struct Worker {
       m_minim_id.encode(rc, (u32)mid, nc);
       if (mid == 15) compress_read(p2, size2, true, false);
       else {
+        sh->cnt.anchor[mpos < 254 ? 0 : mpos < 65536 ? 1 : 2] += 1;
         if (mpos < 254) m_minim_pos.get((u64)mid, t_minim_pos)->encode(rc, mpos, nc);
         else if (mpos < 65536) {
           m_minim_pos.get((u64)mid, t_minim_pos)->encode(rc, 254, nc);
@@ -1480,9 +1509,16 @@ static int run_block(fqo_codec *c, u8 *bases, const uint64_t *off, uint32_t n_re
   if (S > cap) S = cap;
   if (S) --S;
   const bool orig = s.dna_mode == 0 || s.dna_mode == 2, paired = s.dna_mode >= 2;
+  if (dec_streams) {   // what the decoder indexes with
+    if (paired && (n_reads & 1)) return 1;
+    if (off[0] != 0) return 1;
+    for (u64 i = 0; i < n_reads; ++i)
+      if (off[i + 1] < off[i] || off[i + 1] - off[i] >= (1ull << 24)) return 1;
+  }
   for (u64 t = 0; t < T; ++t) {  // application.cpp:624-628
     Worker &w = *c->w[t];
     w.read_prev.clear();
+    w.have_prev = false;
     w.rc.out.clear();
     w.rc.dec = dec_streams != nullptr;
     if (dec_streams) w.rc.start_dec(dec_streams[t], dec_lens[t]); else w.rc.start();
@@ -1503,10 +1539,11 @@ static int run_block(fqo_codec *c, u8 *bases, const uint64_t *off, uint32_t n_re
       } else stop = last[t];
       if (stop > last[t]) stop = last[t];
       if (!paired)
-        for (u64 i = cursor[t]; i < stop; ++i) w.compress_read(bases + off[i], (u32)(off[i + 1] - off[i]), orig);
+        for (u64 i = cursor[t]; i < stop && !w.bad; ++i) w.compress_read(bases + off[i], (u32)(off[i + 1] - off[i]), orig);
       else
-        for (u64 i = cursor[t]; i + 1 < stop; i += 2)
+        for (u64 i = cursor[t]; i + 1 < stop && !w.bad; i += 2)
           w.compress_pair(bases + off[i], (u32)(off[i + 1] - off[i]), bases + off[i + 1], (u32)(off[i + 2] - off[i + 1]), orig);
+      if (w.bad) return 2;   // (the codec's tables and models are partly updated: it can only be destroyed)
       if (stop > cursor[t]) cursor[t] = stop;
     }
     for (u64 t = 0; t < T; ++t) c->w[t]->insert_phase();
@@ -1532,8 +1569,9 @@ const uint8_t *fqo_stream(fqo_codec *c, uint32_t worker, uint64_t *len) {
   return c->w[worker]->rc.out.data();
 }
 
-void fqo_levels(fqo_codec *c, uint64_t o[10]) {
+void fqo_levels(fqo_codec *c, uint64_t o[13]) {
   for (int i = 0; i < 6; ++i) o[i] = c->sh.cnt.lv[i];
+  for (int i = 0; i < 3; ++i) o[10 + i] = c->sh.cnt.anchor[i];
   o[6] = o[7] = o[8] = o[9] = 0;
   for (auto *w : c->w) { o[6] += w->cinc_b.draws; o[7] += w->cinc_s.draws; o[8] += w->cinc_lb.draws; o[9] += w->cinc_ls.draws; }
 }

@@ -40,7 +40,10 @@ const uint8_t *fqo_stream(fqo_codec *, uint32_t worker, uint64_t *len);
 /* Decode one reads block (reference decoder workers, application.cpp:874-917; DecompressSE/PE,
  * dna.cpp:1883-2044): streams[w]/lens[w] = worker w's DNA stream, read_off = n_reads+1 offsets of
  * the reads inside bases_out (the read lengths come from the meta stream).  A codec object is
- * used either for encoding or for decoding, never both. */
+ * used either for encoding or for decoding, never both.
+ * Returns 1 for offsets that do not start at 0 or descend, a read of 2^24 bases or more or an odd n_reads in a paired mode
+ * (nothing done), 2 where a stream leaves the format ("Where a DNA stream leaves the format"; the codec is partly
+ * updated and can only be destroyed).  Nothing outside the streams and bases_out[0 .. read_off[n_reads]) is touched. */
 int fqo_decode_block(fqo_codec *, const uint8_t *const *streams, const uint64_t *lens, const uint64_t *read_off,
                      uint32_t n_reads, uint32_t generation, uint8_t *bases_out);
 
@@ -52,8 +55,9 @@ int fqo_decode_block(fqo_codec *, const uint8_t *const *streams, const uint64_t 
 void fqo_counters(fqo_codec *, uint64_t out[8]);
 /* Coverage of the rarely taken branches: [0..5] find_counts results per counts_level_t (none, pmer, smer, bmer,
  * mixed, bmer_unc; defs.h:45, dna.cpp:457-502), [6..9] random draws of cinc_b / cinc_s / cinc_lb / cinc_ls (counters
- * above their thresholds, utils.h:272-325). */
-void fqo_levels(fqo_codec *, uint64_t out[10]);
+ * above their thresholds, utils.h:272-325), [10..12] anchored second mates of pairs whose anchor position was coded
+ * in 1 / 3 / 4 symbols (below 254; the 254 escape, below 65536; the 255 escape; dna.cpp:1840-1868, decoding :1985-2001). */
+void fqo_levels(fqo_codec *, uint64_t out[13]);
 
 /* Quality stream (CQualityCompressor, quality.cpp:152-175): same header bytes
  * (quality_mode = byte 6, quality_thr = byte 8), same worker partition, no synchronisation points. */

@@ -92,9 +92,10 @@ class OracleCodec:
         return dict(zip(["probes", "slots", "inserts", "siv_words", "ctx", "coded", "lprobes", "linserts"], list(a)))
 
     def levels(self):
-        a = (C.c_uint64 * 10)()
+        a = (C.c_uint64 * 13)()
         lib().fqo_levels(self._h, a)
-        return dict(zip(["none", "pmer", "smer", "bmer", "mixed", "bmer_unc", "draws_b", "draws_s", "draws_lb", "draws_ls"], list(a)))
+        return dict(zip(["none", "pmer", "smer", "bmer", "mixed", "bmer_unc", "draws_b", "draws_s", "draws_lb", "draws_ls",
+                         "anchor_1", "anchor_3", "anchor_4"], list(a)))
 
     def close(self):
         if self._h:

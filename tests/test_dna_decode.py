@@ -234,3 +234,77 @@ def test_growth_posted_by_the_device_decode_side(where, name, request, monkeypat
         assert cap["growths"] >= 8 and cap["pair_slots"] > 64 * 4 and cap["pair_slots"] == enc.capacity()["pair_slots"], cap
     else:
         assert cap["growths"] >= 4, cap
+
+
+# ---- f. anchor positions of three bytes ----------------------------------------------------------------------------------------------
+_FAR = {}
+
+
+def _far_anchor_case(mode):
+    """(header, blocks, the oracle's streams, the oracle's branch counters) of the input of test_anchor_positions_of_three_bytes,
+    computed once per mode for the emulation build and the GPU"""
+    if mode not in _FAR:
+        from oracle.pyoracle import OracleCodec
+        rng = np.random.Generator(np.random.PCG64(65536))
+        acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+        mate1, tail = acgt[rng.integers(0, 4, 300)], acgt[rng.integers(0, 4, 34000)]
+        blocks = []
+        for _ in range(2):
+            reads = [r for _ in range(4) for r in (mate1, np.concatenate([acgt[rng.integers(0, 4, 66000)], tail]))]
+            off = np.zeros(len(reads) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(r) for r in reads])
+            blocks.append((np.concatenate(reads), off))
+        header = hp.make_header(2, mode, 1)
+        oc = OracleCodec(header)
+        want = [oc.encode_block(bases, off, g) for g, (bases, off) in enumerate(blocks)]
+        _FAR[mode] = (header, blocks, want, oc.levels())
+    return _FAR[mode]
+
+
+@pytest.mark.parametrize("mode", ["pe_original", "pe_sorted"])
+@pytest.mark.parametrize("where", WHERE)
+def test_anchor_positions_of_three_bytes(where, mode, request):
+    """The anchor position of a second mate is coded in one symbol, in three (the 254 escape: positions up to 65535; c20 reaches
+    it, tests/test_oracle_golden.py) or in four (the 255 escape, MPOS_ENC / MPOS_DEC classes 3-5: positions from 65536, in mates
+    of up to 2^24 - 1 bases).  8 pairs in two blocks of 4, T = 2: every first mate is the same 300 random bases, every second
+    mate 66 000 fresh random bases and one shared random tail of 34 000.  The minimizer windows of the last third of a 100 000-base
+    mate start at about 66 660, so the only minimizers of a second mate that the pair table can offer a later pair lie in the
+    shared tail, above 65 536.  That the four-symbol branch is reached is counted by the oracle (anchor_4); the encoder under
+    test writes the oracle's streams byte for byte, so it coded the same escapes, and the decoder that returns the input decoded
+    them.  Measured: a parametrisation takes 13.9 s (pe_original) / 12.8 s (pe_sorted) on the emulation build and 6.9 s / 5.4 s on
+    the MI355X, of which 2.1 s are the oracle's (once per mode).  Blocks of 3 pairs instead of 4 were tried and are no answer: 6.6 s /
+    5.1 s on the GPU, 12.3 s / 11.9 s on the emulation build -- the time is the codecs' (tables of the full default size, made and
+    compared three times) more than the bases' -- so the input stays the 8 pairs."""
+    header, blocks, want, lv = _far_anchor_case(mode)
+    assert lv["anchor_4"] > 0, lv
+    _round_trip(_codec(where, request), header, blocks, want)
+
+
+# ---- g. empty reads at a worker's start -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["se_original", "pe_original", "pe_sorted"])
+@pytest.mark.parametrize("where", WHERE)
+def test_empty_first_read_of_a_worker(where, mode, request):
+    """T = 2, blocks of four reads (two pairs): an empty read in front of three of 100 bases, an empty read at the start of either
+    worker, four empty reads, and once more the second block (an empty read whose predecessor is empty too is a duplicate).  The
+    encoder never sets the duplicate flag for a worker's first read (read_head: no previous read), so an empty first read is
+    coded in full, and the decoder must take it so; where a worker has a previous read, an empty read after an empty one is
+    coded by the flag.  In the original-order modes reads of 3 bases, shorter than every prefix, end the last block: their
+    prefix is not written past them.
+    Not covered: se_sorted, and reads shorter than the p-mer in pe_sorted.  There the encoder builds the p-mer of the sorted
+    prefix from positions beyond the read (rd_sym), and the blocks above do not come back (se_sorted: blocks 0, 1 and 3 decode
+    to other bases; the 3-base reads end in device error 8 in both sorted modes) -- before the decoder's checks on damaged
+    streams as after them, measured on the emulation build of either state.
+    On the MI355X block 1 (the empty first read of worker 1) came back wrong in se_original before read_head padded the staged
+    code line: for a read shorter than the prefix rd_sym took the missing positions from LDS that the read had not staged, and a
+    byte above 4 there is no symbol of the letter models."""
+    r = synth_reads(4, 100, 5000, 17)
+    e, s = np.zeros(0, dtype=np.uint8), r[3][:3]
+    cases = [[e, r[0], r[1], r[2]], [e, r[0], e, r[1]], [e, e, e, e], [e, r[0], e, r[1]]]
+    if mode.endswith("original"):
+        cases.append([r[2], s, r[3], s])
+    blocks = []
+    for reads in cases:
+        off = np.zeros(5, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in reads])
+        blocks.append((np.concatenate(reads), off))
+    _round_trip(_codec(where, request), hp.make_header(2, mode, 1), blocks)
