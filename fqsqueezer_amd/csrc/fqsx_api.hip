@@ -7,7 +7,7 @@
 //                     k_part_sender     (3 T workgroups: (mailbox kind, source), eight waves each: the source's list sorted by owner)
 //                     k_insert_phase    (3 T workgroups: (owner, mailbox kind), eight waves each: growth check, then the keys go in
 //                                        window by window; further workgroups clear the local tables)
-//   (decoding and the sharded drivers: k_part_count, k_part_scan, k_part_dstoff, k_part_scatter in place of k_part_sender, the
+//   (decoding and the sharded phase loop: k_part_count, k_part_scan, k_part_dstoff, k_part_scatter in place of k_part_sender, the
 //    demand read by the host in between, the local tables cleared by a launch of their own)
 //   k_finish_block
 //
@@ -356,7 +356,7 @@ FQ_KERNEL64 void k_shard_counts(DevCfg cfg, u32 *dst, u32 status) {   // grid = 
     dst[((u64)kind * T + s) * T + o] = n;
   }
 }
-// ---- native sharded driver (fqsx_shard_encode_block): the words that ride along with the collectives ------------
+// ---- the sharded phase loop (fqsx_shard_encode_block): the words that ride along with the collectives -----------
 // after the all-reduce of the counts: out[0/1] = table demand of the coming insert phase (occupied + incoming slots of the
 // fullest s- / b-mer sub-table: every rank holds a replica of every sub-table, so every rank computes the same numbers),
 // out[2] = the device error word
@@ -426,24 +426,13 @@ FQ_KERNEL64 void k_shard_pe_unpack(DevCfg cfg, const u64 *gathered, u64 stride, 
   for (u64 i = FQ_LANE; i < n; i += FQ_WAVE) dst[i] = src[i];
   if (FQ_LANE == 0) cfg.pe_n[s] = pe_cnt[s];
 }
-// p-mer vector statistics: this rank's contribution of the phase (after - before) into the payload ...
-FQ_KERNEL64 void k_shard_siv_delta(DevCfg cfg, const u64 *before, u64 *out) {
-  for (u32 i = FQ_LANE; i < 2; i += FQ_WAVE) out[i] = cfg.siv_stats[i] - before[i];
-}
-// ... and, after the all-gather, the sum over the ranks on top of the value before the phase (every rank alike)
-FQ_KERNEL64 void k_shard_siv_sum(DevCfg cfg, const u64 *before, const u64 *gathered, u64 stride, u64 off) {
-  for (u32 i = FQ_LANE; i < 2; i += FQ_WAVE) {
-    u64 v = before[i];
-    for (u32 q = 0; q < cfg.shard_world; ++q) v += gathered[(u64)q * stride + off + i];
-    cfg.siv_stats[i] = v;
-  }
-}
-// Partitioned tables: a sub-table's occupancy counter is only kept by its owner's rank, but every rank needs all of them
-// for the growth rule (k_shard_need).  They ride along with the all-gather: out[which * n_max + j] = filled of this rank's
-// j-th own sub-table of the s- (which 0) / b-mer (1) table ...
+// p-mer vector statistics: this rank's contribution of the phase (after - before) into the payload and -- behind the
+// all-gather -- the sum over the ranks on top of the value before the phase (every rank alike).
+// Partitioned tables (n_arr != 0; replicas: no fill words): a sub-table's occupancy counter is only kept by its owner's rank,
+// but every rank needs all of them for the growth rule (k_shard_need).  They ride along in the same two launches:
+// out[which * n_max + j] = filled of this rank's j-th own sub-table of the s- (which 0) / b-mer (1) table, and behind the
+// all-gather the other ranks' counters go into this rank's copy of the arrays
 // (n_arr = 3: the pair table's counters behind them -- a partitioned pair table, cfg.pe_part)
-// ... together with the statistics' delta in one launch, and -- behind the all-gather -- the sum and the other ranks'
-// counters into this rank's copy of the arrays
 FQ_KERNEL64 void k_shard_pack2(DevCfg cfg, const u64 *before, u64 *out_siv, u64 *out_fill, u32 n_max, u32 n_arr) {
   for (u32 i = FQ_LANE; i < 2; i += FQ_WAVE) out_siv[i] = cfg.siv_stats[i] - before[i];
   for (u32 i = FQ_LANE; i < n_arr * n_max; i += FQ_WAVE) {
@@ -468,17 +457,7 @@ FQ_KERNEL64 void k_shard_unpack2(DevCfg cfg, const u64 *before, const u64 *gathe
 // Received entries -> this rank's owners' groups in (owner, source, push) order (the order InsertKmersToHT drains
 // its column in).  recv = the chunks of ranks 0..G-1 one after the other; the chunk of rank q holds, for every owner
 // of this rank in ascending order, the entries of q's sources in ascending order.  C = the summed count matrix.
-// cs: the matrix's column sums (k_shard_colsum), or null (the step-wise driver: every wave sums the columns it needs itself)
-FQ_DEV void shard_merge_body(const DevCfg &cfg, u32 kind, u32 o, const u64 *recv, const u32 *C, const u32 *cs, u32 *col, u32 *pre, u32 *soff);
-FQ_KERNEL64 void k_shard_merge(DevCfg cfg, u32 kind, const u64 *recv, const u32 *C) {   // grid = T (owner)
-  FQ_SHARED u32 col[256], pre[256], soff[256];
-  shard_merge_body(cfg, kind, FQ_BLOCK, recv, C, nullptr, col, pre, soff);
-}
-FQ_KERNEL64 void k_shard_merge3(DevCfg cfg, const u64 *recv0, const u64 *recv1, const u64 *recv2, const u32 *C, const u32 *cs) {   // grid = 3 T: (kind, owner)
-  FQ_SHARED u32 col[256], pre[256], soff[256];
-  const u32 kind = FQ_BLOCK / cfg.T;
-  shard_merge_body(cfg, kind, FQ_BLOCK % cfg.T, kind == 0 ? recv0 : kind == 1 ? recv1 : recv2, C, cs, col, pre, soff);
-}
+// cs: the matrix's column sums (k_shard_colsum)
 FQ_DEV void shard_merge_body(const DevCfg &cfg, u32 kind, u32 o, const u64 *recv, const u32 *C, const u32 *cs, u32 *col, u32 *pre, u32 *soff) {
   const u32 T = cfg.T, G = cfg.shard_world, me = cfg.shard_rank;
   const Mail &m = cfg.mail[kind];
@@ -488,11 +467,7 @@ FQ_DEV void shard_merge_body(const DevCfg &cfg, u32 kind, u32 o, const u64 *recv
   u32 dst = 0, tot = 0;
   for (u32 jb = 0; jb < n_own; jb += FQ_WAVE) {
     const u32 j = jb + FQ_LANE, o2 = me + j * G;
-    u32 n = 0;
-    if (j < n_own) {
-      if (cs) n = cs[((u64)kind * (G + 1)) * T + o2];
-      else for (u32 s = 0; s < T; ++s) n += Ck[(u64)s * T + o2];
-    }
+    const u32 n = j < n_own ? cs[((u64)kind * (G + 1)) * T + o2] : 0u;
     dst += wave_sum32(j < n_own && o2 < o ? n : 0u);
     tot += wave_sum32(j < n_own && o2 == o ? n : 0u);
   }
@@ -518,11 +493,7 @@ FQ_DEV void shard_merge_body(const DevCfg &cfg, u32 kind, u32 o, const u64 *recv
     u32 before = 0, size = 0;
     for (u32 jb = 0; jb < n_own; jb += FQ_WAVE) {
       const u32 j = jb + FQ_LANE, o2 = me + j * G;
-      u32 n = 0;
-      if (j < n_own) {
-        if (cs) n = cs[((u64)kind * (G + 1) + 1 + q) * T + o2];
-        else for (u32 s = q; s < T; s += G) n += Ck[(u64)s * T + o2];
-      }
+      const u32 n = j < n_own ? cs[((u64)kind * (G + 1) + 1 + q) * T + o2] : 0u;
       before += wave_sum32(j < n_own && o2 < o ? n : 0u);
       size += wave_sum32(j < n_own ? n : 0u);
     }
@@ -545,6 +516,11 @@ FQ_DEV void shard_merge_body(const DevCfg &cfg, u32 kind, u32 o, const u64 *recv
     while (col[lo] == 0 && lo > 0) --lo;   // (not reached: pre[lo] <= x < tot means the last such source has entries; kept for safety)
     m.sorted[dst + x] = recv[soff[lo] + (x - pre[lo])];
   }
+}
+FQ_KERNEL64 void k_shard_merge3(DevCfg cfg, const u64 *recv0, const u64 *recv1, const u64 *recv2, const u32 *C, const u32 *cs) {   // grid = 3 T: (kind, owner)
+  FQ_SHARED u32 col[256], pre[256], soff[256];
+  const u32 kind = FQ_BLOCK / cfg.T;
+  shard_merge_body(cfg, kind, FQ_BLOCK % cfg.T, kind == 0 ? recv0 : kind == 1 ? recv1 : recv2, C, cs, col, pre, soff);
 }
 // After the insert phase: what the replicas on the other ranks have to take over.  One item per applied entry of this
 // rank's owners (duplicates carry the same final value): s-/b-mers the table slot (k-mer << cbits | count), p-mers
@@ -635,15 +611,13 @@ struct fqsx_dna : DevCtx {   // (a new fqsx_dna() starts with every field zero u
   u32 cur_n_reads, cur_S, cur_gen;
   u64 cur_need_lb, cur_need_ls, cur_need_lpe;
   bool cur_decode;
-  // sharded mode (fqsx_shard_*): exchange scratch
+  // sharded mode (fqsx_shard_attach / fqsx_shard_encode_block): exchange scratch
   u32 shard_rank, shard_world = 1;
   u8 *d_vmap;
   u64 *d_xbuf;        // received entries / upsert items
   u64 xbuf_cap;
   u32 *d_cglob;       // [3][T][T] (+ [T] paired-end triples per source) the all-reduced count matrix of the phase
   u32 *d_colsum;      // [3][world + 1][T] its column sums (k_shard_colsum)
-  u64 siv_before[2];
-  // native sharded driver (fqsx_shard_attach / fqsx_shard_encode_block)
   fqsx_comm comm;     // the world's collectives (RCCL on the codec's stream, or the caller's)
   bool comm_set, shard_apply_own;
   u64 *d_xrecv[3];    // received mailbox entries per kind
@@ -1101,6 +1075,16 @@ int launch_segment(fqsx_dna *c, bool decode, u32 n_reads, u32 S, u32 seg, bool d
   return rc;
 }
 
+// the two coding queues go back to the device (deferred coding)
+void gq_release(fqsx_dna *c) {
+  for (u32 b = 0; b < 2; ++b) {
+    GQueue &q = c->cfg.gq[b];
+    dfree(c, q.key); dfree(c, q.kind); dfree(c, q.rsym); dfree(c, q.n);
+    q = GQueue{};
+  }
+  c->gq_entries = c->cfg.gq_cap = 0;
+}
+
 // Sizes the per-block buffers and fixes the block's schedule (number of synchronisation points S)
 int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h_off, u32 n_reads, u32 generation,
                   const u8 *const *dec_streams = nullptr, const u64 *dec_lens = nullptr) {
@@ -1182,12 +1166,7 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
     // a block without a deferred phase (in a file: every block from generation 99 on): the second stream and the queues go back,
     // and the block runs on what a codec that never deferred holds
     dev_side_close(c);
-    for (u32 b = 0; b < 2; ++b) {
-      GQueue &q = cfg.gq[b];
-      dfree(c, q.key); dfree(c, q.kind); dfree(c, q.rsym); dfree(c, q.n);
-      q = GQueue{};
-    }
-    c->gq_entries = cfg.gq_cap = 0;
+    gq_release(c);
   }
   if (c->cur_defer && (rc = dev_side_open(c))) return rc;
 #endif
@@ -1196,12 +1175,7 @@ int block_prepare(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h
     const u64 cap = c->gq_test_cap > 1 ? c->gq_test_cap - 1 : c->gq_test_cap == 1 ? std::max<u64>(max_defer_entries, 1)
                     : need > c->gq_entries ? (need + need / 4 + 63) & ~63ull : c->gq_entries;
     if (cap != c->gq_entries) {
-      for (u32 b = 0; b < 2; ++b) {   // (handed back and forgotten before their successors are asked for, as dfit)
-        GQueue &q = cfg.gq[b];
-        dfree(c, q.key); dfree(c, q.kind); dfree(c, q.rsym); dfree(c, q.n);
-        q = GQueue{};
-      }
-      c->gq_entries = cfg.gq_cap = 0;
+      gq_release(c);   // (handed back and forgotten before their successors are asked for, as dfit)
       for (u32 b = 0; b < 2; ++b) {
         GQueue &q = cfg.gq[b];
         if ((rc = dalloc(c, &p, (u64)T * 10 * cap * sizeof(u64), false))) return rc;
@@ -1290,9 +1264,37 @@ int grow_for_demand(fqsx_dna *c) {
   }
   return FQSX_OK;
 }
+// The grouped partition (decoding, FQSX_PART_SENDER=0, the sharded phase loop): one workgroup per (source, tile) of the three mailboxes
+u32 part_grid(const fqsx_dna *c) {
+  const DevCfg &cfg = c->cfg;
+  return c->T * (cfg.mail[0].n_tiles + cfg.mail[1].n_tiles + cfg.mail[2].n_tiles);
+}
+int part_count(fqsx_dna *c) {
+  LAUNCH(c, 2, k_part_count, part_grid(c), 64, c->cfg);
+  return FQSX_OK;
+}
+// ... tile offsets, group offsets with the demand words (for a host that decides about growth), the entries into their owners' groups
+int part_scan_scatter(fqsx_dna *c) {
+  LAUNCH(c, 2, k_part_scan, 3 * c->T, 64, c->cfg);
+  LAUNCH(c, 2, k_part_dstoff, 3, 64, c->cfg, c->d_demand, 0u);
+  LAUNCH(c, 2, k_part_scatter, part_grid(c), 64, c->cfg, 0u, (u32 *)nullptr);
+  return FQSX_OK;
+}
+// paired-end: the exact demand of the phase's pair-table inserts (occupied + new slots of the fullest sub-table); the growth is the caller's.
+// d_dem: T device words for k_pe_demand's per-owner counts
+int pe_table_need(fqsx_dna *c, u32 *d_dem, u64 *need) {
+  const u32 T = c->T;
+  int rc;
+  LAUNCH(c, 2, k_pe_demand, T, 64, c->cfg, d_dem, 0u);
+  std::vector<u32> dem(T), fil(T);
+  if ((rc = d2h_sync(c, dem.data(), d_dem, T * sizeof(u32)))) return rc;
+  if ((rc = d2h_sync(c, fil.data(), c->cfg.g_pe.filled, T * sizeof(u32)))) return rc;
+  *need = 0;
+  for (u32 o = 0; o < T; ++o) *need = std::max<u64>(*need, (u64)fil[o] + dem[o]);
+  return FQSX_OK;
+}
 // The device stopped the block's queue before the inserts of segment `seg` (phase_skip): grow, then take up from there
 int pe_insert_and_clear(fqsx_dna *c);
-int pe_clear_local(fqsx_dna *c);
 int block_recover(fqsx_dna *c, u32 seg) {
   const u32 T = c->T;
   int rc;
@@ -1310,12 +1312,8 @@ int block_recover(fqsx_dna *c, u32 seg) {
   if ((rc = dzero(c, c->cfg.err + 1, sizeof(u32)))) return rc;
   if (c->paired && !pairs_done) {   // the pair table's demand again (the queued count stopped at the posted word), growth, then the phase's inserts
     if ((rc = dzero(c, c->cfg.pe_bkt_n, T * sizeof(u32)))) return rc;   // (the per-owner counts of the stopped pass: the next phase counts from zero)
-    LAUNCH(c, 2, k_pe_demand, T, 64, c->cfg, c->d_demand + 4 * T + 1, 0u);
-    std::vector<u32> dem(T), fil(T);
-    if ((rc = d2h_sync(c, dem.data(), c->d_demand + 4 * T + 1, T * sizeof(u32)))) return rc;
-    if ((rc = d2h_sync(c, fil.data(), c->cfg.g_pe.filled, T * sizeof(u32)))) return rc;
-    u64 need = 0;
-    for (u32 o = 0; o < T; ++o) need = std::max<u64>(need, (u64)fil[o] + dem[o]);
+    u64 need;
+    if ((rc = pe_table_need(c, c->d_demand + 4 * T + 1, &need))) return rc;
     if (need * 2 > c->gpe_cap && (rc = grow_gpe(c, pow2_at_least(need * 2 + 2)))) return rc;
   }
   if (c->gs_cap + c->gb_cap + c->gpe_cap == before) { g_err = "phase " + std::to_string(seg) + " posted for growth, but no table needs it"; return FQSX_E_DEVICE; }
@@ -1350,12 +1348,11 @@ int block_segment(fqsx_dna *c, u32 seg) {
     if (!defer) DEVCHK(dev_side_join(c));
     if ((rc = launch_segment(c, decode, n_reads, (u32)S, seg, defer))) return rc;
     // size the global tables for this phase's inserts (exact per-owner demand)
-    const u32 part_grid = T * (cfg.mail[0].n_tiles + cfg.mail[1].n_tiles + cfg.mail[2].n_tiles);
     if (!decode && c->part_sender) LAUNCH(c, 2, k_part_sender, 3 * T, FQSX_SND_THREADS, cfg);   // (every source for itself; k_insert_phase checks for growth)
     else {
-      LAUNCH(c, 2, k_part_count, part_grid, 64, cfg);
+      if ((rc = part_count(c))) return rc;
       LAUNCH(c, 2, k_part_scan, 3 * T, 64, cfg);
-      if (!decode) LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, seg + 1, c->d_demand);   // (FQSX_PART_SENDER=0; group offsets, demand words and growth check included)
+      if (!decode) LAUNCH(c, 2, k_part_scatter, part_grid(c), 64, cfg, seg + 1, c->d_demand);   // (FQSX_PART_SENDER=0; group offsets, demand words and growth check included)
     }
     if (!decode) {
       // encoding: nothing is read back inside a block -- the growth checks are the device's (phase_skip)
@@ -1372,7 +1369,7 @@ int block_segment(fqsx_dna *c, u32 seg) {
     LAUNCH(c, 2, k_part_dstoff, 3, 64, cfg, c->d_demand, 0u);
     // the demand travels to the host while the scatter (which does not depend on the growth decision) runs
     if ((rc = d2h_small_begin(c, c->d_demand, (4 * T + 1) * sizeof(u32)))) return rc;
-    LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, 0u, (u32 *)nullptr);
+    LAUNCH(c, 2, k_part_scatter, part_grid(c), 64, cfg, 0u, (u32 *)nullptr);
     if ((rc = d2h_small_end(c, c->h_demand.data(), (4 * T + 1) * sizeof(u32)))) return rc;
     if (c->h_demand[2 * T]) {
       g_err = "device error " + std::to_string(c->h_demand[2 * T]) + " in decode kernel (block " + std::to_string(c->cur_gen) + ")";   // (only decoding reads the word back here)
@@ -1380,11 +1377,8 @@ int block_segment(fqsx_dna *c, u32 seg) {
     }
     if ((rc = grow_for_demand(c))) return rc;
     if (c->paired) {  // pair table: size for the exact per-owner demand, then insert
-      LAUNCH(c, 2, k_pe_demand, T, 64, cfg, c->d_demand, 0u);
-      if ((rc = d2h_sync(c, c->h_demand.data(), c->d_demand, T * sizeof(u32)))) return rc;
-      if ((rc = d2h_sync(c, c->h_filled.data(), cfg.g_pe.filled, T * sizeof(u32)))) return rc;
-      u64 need = 0;
-      for (u32 o = 0; o < T; ++o) need = std::max<u64>(need, (u64)c->h_filled[o] + c->h_demand[o]);
+      u64 need;
+      if ((rc = pe_table_need(c, c->d_demand, &need))) return rc;
       if (need * 2 > c->gpe_cap && (rc = grow_gpe(c, pow2_at_least(need * 2 + 2)))) return rc;
       if ((rc = pe_insert_and_clear(c))) return rc;
     }
@@ -1442,7 +1436,7 @@ int block_finish(fqsx_dna *c, const u64 *h_off, const u8 **streams, u64 *lens, u
 int encode_block_impl(fqsx_dna *c, const u8 *d_bases, const u64 *d_off, const u64 *h_off, u32 n_reads, u32 generation,
                       const u8 **streams, u64 *lens, const u8 *const *dec_streams = nullptr, const u64 *dec_lens = nullptr,
                       u8 *bases_out = nullptr) {
-  if (c->shard_world > 1) { g_err = "a sharded codec is driven through fqsx_shard_* (fqsqueezer_amd/sharded.py)"; return FQSX_E_ARG; }
+  if (c->shard_world > 1) { g_err = "a sharded codec is driven through fqsx_shard_encode_block (fqsqueezer_amd/sharded.py)"; return FQSX_E_ARG; }
   int rc = block_prepare(c, d_bases, d_off, h_off, n_reads, generation, dec_streams, dec_lens);
   for (u32 seg = 0; !rc;) {
     for (; !rc && seg <= c->cur_S; ++seg) rc = block_segment(c, seg);
@@ -1737,10 +1731,10 @@ int fqsx_dna_decode_block_dev(fqsx_dna *c, const uint8_t *const *streams, const 
   return FQSX_OK;
 }
 
-// ---- sharded mode: one synchronisation phase in steps, with the collectives in between left to the caller ----------
-// (fqsqueezer_amd/sharded.py drives these with torch.distributed: RCCL on GPUs, gloo for the emulation build).
-// Pointers marked [codec] are in the codec's memory space: device memory for the HIP build.
-int fqsx_shard_config(fqsx_dna *c, uint32_t rank, uint32_t world) {
+// ---- sharded mode: the phase loop inside the library ------------------------------------------------------------------
+namespace {
+// the codec becomes one rank of a world: rank-major order of the mailboxes' groups, the phase loop's count matrix and small words
+int shard_config(fqsx_dna *c, uint32_t rank, uint32_t world) {
   if (!c || world == 0 || rank >= world || world > c->T) { g_err = "bad rank / world size"; return FQSX_E_ARG; }
   if (c->part && world > 1) { g_err = "a codec with chunked tables cannot be sharded afterwards (fqsx_shard_partition_tables after the attach)"; return FQSX_E_ARG; }
   DEVCHK(dev_enter(c));
@@ -1771,129 +1765,6 @@ int fqsx_shard_config(fqsx_dna *c, uint32_t rank, uint32_t world) {
   return FQSX_OK;
 }
 
-int fqsx_shard_begin_block(fqsx_dna *c, const uint8_t *bases /*[codec]*/, const uint64_t *off /*[codec]*/, const uint64_t *h_off,
-                           uint32_t n_reads, uint32_t generation, uint32_t *n_segments) {
-  if (!c || !bases || !off || !h_off || !n_segments) { g_err = "null argument"; return FQSX_E_ARG; }
-  if (c->part) { g_err = "partitioned tables are driven through fqsx_shard_encode_block"; return FQSX_E_ARG; }
-  // the step-wise driver exchanges the three k-mer mailboxes only: the pair-table triples of a paired-end file travel with
-  // the native loop's all-gather (shard_phase_native), nowhere else -- a world of several ranks would leave the pair table empty
-  if (c->paired && c->shard_world > 1) { g_err = "paired-end files are sharded through fqsx_shard_attach + fqsx_shard_encode_block (the step-wise fqsx_shard_* driver does not exchange the pair-table triples)"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  int rc = block_prepare(c, bases, off, h_off, n_reads, generation);
-  *n_segments = c->cur_S + 1;
-  return rc;
-}
-
-// encode launch of segment `seg` for this rank's workers, then the per-(source, owner) counts of their mailboxes
-int fqsx_shard_encode(fqsx_dna *c, uint32_t seg, uint32_t *counts /*[codec] [3][T][T]*/) {
-  if (!c || !counts) { g_err = "null argument"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  const u32 T = c->T;
-  DevCfg &cfg = c->cfg;
-  int rc;
-  if ((rc = launch_segment(c, false, c->cur_n_reads, c->cur_S, seg))) return rc;
-  const u32 part_grid = T * (cfg.mail[0].n_tiles + cfg.mail[1].n_tiles + cfg.mail[2].n_tiles);
-  LAUNCH(c, 2, k_part_count, part_grid, 64, cfg);
-  LAUNCH(c, 2, k_shard_counts, 3 * T + 1, 64, cfg, cfg.shard_cnt, 0u);
-  if ((rc = d2d(c, counts, cfg.shard_cnt, 3ull * T * T * sizeof(u32)))) return rc;
-  u32 err = 0;
-  if ((rc = d2h_sync(c, &err, cfg.err, sizeof(u32)))) return rc;
-  if (err) { g_err = "device error " + std::to_string(err) + " in encode kernel"; return FQSX_E_DEVICE; }
-  return FQSX_OK;
-}
-
-// the entries of this rank's workers in send order (destination rank, owner, source, push) -> send[kind]
-int fqsx_shard_pack(fqsx_dna *c, const uint32_t *counts_sum /*[codec] summed over ranks*/, uint64_t *const send[3] /*[codec]*/) {
-  if (!c || !counts_sum || !send) { g_err = "null argument"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  const u32 T = c->T;
-  DevCfg &cfg = c->cfg;
-  int rc;
-  if ((rc = d2d(c, c->d_cglob, counts_sum, 3ull * T * T * sizeof(u32)))) return rc;
-  const u32 part_grid = T * (cfg.mail[0].n_tiles + cfg.mail[1].n_tiles + cfg.mail[2].n_tiles);
-  LAUNCH(c, 2, k_part_scan, 3 * T, 64, cfg);
-  LAUNCH(c, 2, k_part_dstoff, 3, 64, cfg, c->d_demand, 0u);
-  LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, 0u, (u32 *)nullptr);
-  std::vector<u32> tot(3 * (T + 1));
-  for (u32 k = 0; k < 3; ++k)
-    if ((rc = d2h_sync(c, tot.data() + k * (T + 1), cfg.mail[k].dst_off, (T + 1) * sizeof(u32)))) return rc;
-  for (u32 k = 0; k < 3; ++k) {
-    const u64 n = tot[k * (T + 1) + T];
-    if (n && (rc = d2d(c, send[k], cfg.mail[k].sorted, n * sizeof(u64)))) return rc;
-  }
-  DEVCHK(dev_sync(c));
-  return FQSX_OK;
-}
-
-// received entries (chunks of ranks 0..G-1 back to back) -> this rank's owners' groups; need[0/1] = this rank's table
-// demand for the s- / b-mer tables (occupied + incoming slots of its fullest sub-table)
-int fqsx_shard_merge(fqsx_dna *c, const uint64_t *const recv[3] /*[codec]*/, uint64_t need[2]) {
-  if (!c || !recv || !need) { g_err = "null argument"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  const u32 T = c->T;
-  DevCfg &cfg = c->cfg;
-  int rc;
-  for (u32 k = 0; k < 3; ++k) LAUNCH(c, 2, k_shard_merge, T, 64, cfg, k, recv[k], (const u32 *)c->d_cglob);
-  need[0] = need[1] = 0;
-  std::vector<u32> tot(T), fil(T);
-  for (int which = 0; which < 2; ++which) {
-    const KTab &t = which ? cfg.g_b : cfg.g_s;
-    if ((rc = d2h_sync(c, tot.data(), cfg.mail[which ? MAIL_B : MAIL_S].dst_tot, T * sizeof(u32)))) return rc;
-    if ((rc = d2h_sync(c, fil.data(), t.filled, T * sizeof(u32)))) return rc;
-    for (u32 o = 0; o < T; ++o) need[which] = std::max<u64>(need[which], (u64)tot[o] + fil[o]);
-  }
-  return FQSX_OK;
-}
-
-// the insert phase of this rank's owners (after every rank has agreed on the tables' demand), then one item per
-// applied entry for the other ranks' replicas; siv_delta = this rank's contribution to (no_updates, no_filled)
-int fqsx_shard_insert(fqsx_dna *c, uint64_t need_s, uint64_t need_b, uint64_t *const items[3] /*[codec]*/, uint64_t siv_delta[2]) {
-  if (!c || !items || !siv_delta) { g_err = "null argument"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  const u32 T = c->T;
-  DevCfg &cfg = c->cfg;
-  int rc;
-  if (tab_over(c, need_s, c->gs_cap) && (rc = grow_global(c, cfg.g_s, c->gs_cap, tab_new_cap(c, need_s)))) return rc;
-  if (tab_over(c, need_b, c->gb_cap) && (rc = grow_global(c, cfg.g_b, c->gb_cap, tab_new_cap(c, need_b)))) return rc;
-  if ((rc = d2h_sync(c, c->siv_before, cfg.siv_stats, 2 * sizeof(u64)))) return rc;
-  LAUNCH(c, 1, k_insert_phase, 3 * T, FQSX_INS_THREADS, cfg, (u64)0, (u64)0, c->ins_win, c->ins_maxmult, 0u, 0u);
-  u64 after[2];
-  if ((rc = d2h_sync(c, after, cfg.siv_stats, 2 * sizeof(u64)))) return rc;
-  siv_delta[0] = after[0] - c->siv_before[0];
-  siv_delta[1] = after[1] - c->siv_before[1];
-  for (u32 k = 0; k < 3; ++k) LAUNCH(c, 2, k_shard_collect, REHASH_GRID, 256, cfg, k, items[k]);
-  DEVCHK(dev_sync(c));
-  return FQSX_OK;
-}
-
-// another rank's items of one kind into this rank's replica
-int fqsx_shard_apply(fqsx_dna *c, uint32_t kind, const uint64_t *items /*[codec]*/, uint64_t n) {
-  if (!c || kind > 2 || (!items && n)) { g_err = "bad argument"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  if (n) LAUNCH(c, 2, k_shard_apply, REHASH_GRID, 256, c->cfg, kind, items, (u32)n);
-  return FQSX_OK;
-}
-
-// end of the phase: the p-mer vector's statistics become the sum over the ranks, the local tables are cleared
-int fqsx_shard_end_phase(fqsx_dna *c, const uint64_t siv_delta_sum[2]) {
-  if (!c || !siv_delta_sum) { g_err = "null argument"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  int rc;
-  u64 now[2] = {c->siv_before[0] + siv_delta_sum[0], c->siv_before[1] + siv_delta_sum[1]};
-  if ((rc = h2d(c, c->cfg.siv_stats, now, 2 * sizeof(u64)))) return rc;
-  DEVCHK(dev_sync(c));
-  return clear_local_tables(c);
-}
-
-// streams of the block (only those of this rank's workers are meaningful)
-int fqsx_shard_finish_block(fqsx_dna *c, const uint64_t *h_off, const uint8_t **streams, uint64_t *lens) {
-  if (!c || !h_off || !streams || !lens) { g_err = "null argument"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(c));
-  return block_finish(c, h_off, streams, lens, nullptr);
-}
-
-// ---- the phase loop inside the library ------------------------------------------------------------------------------
-namespace {
 int xbuf_fit(fqsx_dna *c, u64 *&buf, u64 &cap, u64 words) { return dfit(c, buf, cap, words, words + words / 4 + 1024, sizeof(u64)); }
 // A collective that fails is not something the ranks can agree on any more: the transport is told to give up (RCCL:
 // ncclCommAbort, so that this rank's part of a pending collective does not keep the others' kernels spinning) and the call fails.
@@ -1930,8 +1801,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
   int rc;
   // ---- encode own workers, count what they pushed for whom
   if ((rc = launch_segment(c, false, c->cur_n_reads, c->cur_S, seg))) return rc;
-  const u32 part_grid = T * (cfg.mail[0].n_tiles + cfg.mail[1].n_tiles + cfg.mail[2].n_tiles);
-  LAUNCH(c, 2, k_part_count, part_grid, 64, cfg);
+  if ((rc = part_count(c))) return rc;
   LAUNCH(c, 2, k_shard_counts, 3 * T + 1, 64, cfg, c->d_cglob, 0u);   // (straight into the buffer the all-reduce runs on)
   COMMCHK(c->comm.allreduce_sum_u32(c->comm.ctx, c->d_cglob, NC), "all-reduce of the mailbox counts");   // collective 1
   LAUNCH(c, 2, k_shard_colsum, (3 * T + 63) / 64, 64, cfg, (const u32 *)c->d_cglob, c->d_colsum);
@@ -1951,9 +1821,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
     for (u32 s = 0; s < T; ++s)
       for (u32 o = 0; o < T; ++o) vol[((u64)k * G + s % G) * G + o % G] += C[((u64)k * T + s) * T + o];
   // ---- own entries in send order (destination rank, owner, source, push) = the partitioned mailbox with rank-major groups
-  LAUNCH(c, 2, k_part_scan, 3 * T, 64, cfg);
-  LAUNCH(c, 2, k_part_dstoff, 3, 64, cfg, c->d_demand, 0u);
-  LAUNCH(c, 2, k_part_scatter, part_grid, 64, cfg, 0u, (u32 *)nullptr);
+  if ((rc = part_scan_scatter(c))) return rc;
   std::vector<u64> sc(3ull * G), rcnt(3ull * G);
   const u64 *send[3];
   u64 *recv[3];
@@ -2019,8 +1887,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
   // ---- one all-gather
   for (u32 k = 0; k < 3; ++k)
     if (n_items[(u64)k * G + me] && !(k == MAIL_P && cfg.siv_part)) LAUNCH(c, 2, k_shard_collect, REHASH_GRID, 256, cfg, k, c->d_items + off_k[k]);
-  if (FW) LAUNCH(c, 2, k_shard_pack2, 1, 64, cfg, (const u64 *)c->d_small, c->d_items + off_siv, c->d_items + off_fill, n_own_max, n_fill);
-  else LAUNCH(c, 2, k_shard_siv_delta, 1, 64, cfg, (const u64 *)c->d_small, c->d_items + off_siv);
+  LAUNCH(c, 2, k_shard_pack2, 1, 64, cfg, (const u64 *)c->d_small, c->d_items + off_siv, c->d_items + off_fill, n_own_max, n_fill);
   if (c->paired && PM) LAUNCH(c, 2, k_shard_pe_pack, T, 64, cfg, c->d_items + off_pe);
   COMMCHK(c->comm.allgather_u64(c->comm.ctx, c->d_items, W, c->d_gathered), "all-gather of the applied items");   // collective 3
   c->sh_gather_words += W * (G - 1);
@@ -2028,18 +1895,14 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
     if (q != me || c->shard_apply_own)
       for (u32 k = 0; k < 3; ++k)
         if (n_items[(u64)k * G + q] && !(k == MAIL_P && cfg.siv_part && q == me)) LAUNCH(c, 2, k_shard_apply, REHASH_GRID, 256, cfg, k, (const u64 *)(c->d_gathered + (u64)q * W + off_k[k]), (u32)n_items[(u64)k * G + q]);
-  if (FW) LAUNCH(c, 2, k_shard_unpack2, 1, 64, cfg, (const u64 *)c->d_small, (const u64 *)c->d_gathered, W, off_siv, off_fill, n_own_max, n_fill);
-  else LAUNCH(c, 2, k_shard_siv_sum, 1, 64, cfg, (const u64 *)c->d_small, (const u64 *)c->d_gathered, W, off_siv);
+  LAUNCH(c, 2, k_shard_unpack2, 1, 64, cfg, (const u64 *)c->d_small, (const u64 *)c->d_gathered, W, off_siv, off_fill, n_own_max, n_fill);
   // ---- paired-end: every rank holds every source's triples (the all-gather above) and applies them to its replica of the pair
   // table -- or, with partitioned tables, those of its own owners to its own sub-tables (k_pe_insert; the owners' occupancy
   // counters came with the all-gather, so the growth rule below sees the same numbers on every rank)
   if (c->paired) {
     if (G > 1 && PM) LAUNCH(c, 2, k_shard_pe_unpack, T, 64, cfg, (const u64 *)c->d_gathered, W, off_pe, (const u32 *)(c->d_cglob + 3ull * T * T));
-    LAUNCH(c, 2, k_pe_demand, T, 64, cfg, c->d_demand, 0u);
-    if ((rc = d2h_sync(c, c->h_demand.data(), c->d_demand, T * sizeof(u32)))) return rc;
-    if ((rc = d2h_sync(c, c->h_filled.data(), cfg.g_pe.filled, T * sizeof(u32)))) return rc;
-    u64 need = 0;
-    for (u32 o = 0; o < T; ++o) need = std::max<u64>(need, (u64)c->h_filled[o] + c->h_demand[o]);
+    u64 need;
+    if ((rc = pe_table_need(c, c->d_demand, &need))) return rc;
     if (need * 2 > c->gpe_cap) {   // (replicas / exchanged occupancies are exact: every rank grows in the same phase, and votes on it)
       const int fail = grow_gpe(c, pow2_at_least(need * 2 + 2));
       if (fail && c->part) fqsx_vm::mesh_close(c->mesh);
@@ -2054,10 +1917,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
       COMMCHK(c->comm.allreduce_sum_u32(c->comm.ctx, c->d_cglob, 1), "barrier behind the pair-table inserts");
       c->sh_collectives += 1;
     }
-    if ((rc = dzero(c, cfg.l_pe.key, c->cur_need_lpe * T * sizeof(u64)))) return rc;
-    if ((rc = dzero(c, cfg.l_pe.val, c->cur_need_lpe * T * sizeof(u64)))) return rc;
-    if ((rc = dzero(c, cfg.l_pe.filled, T * sizeof(u32)))) return rc;
-    c->filled_valid = false;   // (h_filled was borrowed for the pair table's occupancies)
+    if ((rc = pe_clear_local(c))) return rc;
   }
   c->sh_phases += 1;
   c->sh_collectives += 3;
@@ -2067,7 +1927,7 @@ int shard_phase_native(fqsx_dna *c, u32 seg) {
 
 int fqsx_shard_attach(fqsx_dna *c, uint32_t rank, uint32_t world, const fqsx_comm *comm) {
   if (!c || !comm || !comm->allreduce_sum_u32 || !comm->alltoallv_u64 || !comm->allgather_u64) { g_err = "incomplete transport"; return FQSX_E_ARG; }
-  int rc = fqsx_shard_config(c, rank, world);
+  int rc = shard_config(c, rank, world);
   if (rc) return rc;
   c->comm = *comm;
   c->comm_set = true;

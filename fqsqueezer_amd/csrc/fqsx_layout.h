@@ -70,7 +70,7 @@ struct CtxSlot {
 //   by source  (single-GPU encoding, k_part_sender): every source sorts its own list stably by owner into its own
 //              stretch sorted[s * cap ..) and leaves the offsets in `soff`; owner o walks the sources in ascending order
 //              (MailKeys, fqsx_dev.h).  No source needs to know anything of another one: one launch.
-//   grouped    (decoding, the sharded drivers: k_part_count / _scan / _dstoff / _scatter): a GPU-wide stable partition,
+//   grouped    (decoding, the sharded phase loop: k_part_count / _scan / _dstoff / _scatter): a GPU-wide stable partition,
 //              one contiguous group per owner at dst_off[o].
 #define FQSX_TILE 2048u
 struct Mail {

@@ -139,28 +139,10 @@ int fqsx_dna_use_chunked_tables(fqsx_dna *);
 /* Sharded mode (reference: the T x T mailboxes of fqs/application.h:56-59 and their owner-side
  * application, fqs/dna.cpp:825-847, :2393-2472): logical worker w -- coder state, RNG streams, local tables and the
  * sub-tables it owns -- lives on rank w % world; every rank keeps a replica of all sub-tables for the look-ups (or maps the
- * other ranks' sub-tables: fqsx_shard_partition_tables below).  The product path is the phase loop inside the library
- * (fqsx_shard_attach + fqsx_shard_encode_block, further down).
- * The step-wise form below is the round-2 bring-up driver, kept for single-end worlds and for callers that want to run the
- * collectives themselves: one synchronisation phase = encode -> [all-reduce of the per-(source, owner) counts] -> pack ->
- * [all-to-all of the three mailboxes] -> merge -> [all-reduce(max) of the two demand words fqsx_shard_merge returns] -> insert
- * -> [all-gather of the applied items] -> apply -> [all-reduce of the p-mer statistics] -> end_phase; the bracketed collectives
- * are the caller's (fqsqueezer_amd/sharded.py: ShardedDnaCodec over torch.distributed).  It does not exchange the pair-table
- * triples: fqsx_shard_begin_block refuses a paired-end codec in a world of more than one rank (FQSX_E_ARG).
- * The streams are bit-identical to the one-GPU run's.  Pointers marked [codec] are in the codec's memory space (device memory). */
-int fqsx_shard_config(fqsx_dna *, uint32_t rank, uint32_t world);
-int fqsx_shard_begin_block(fqsx_dna *, const uint8_t *bases /*[codec]*/, const uint64_t *read_off /*[codec]*/, const uint64_t *h_read_off,
-                           uint32_t n_reads, uint32_t generation, uint32_t *n_segments);
-int fqsx_shard_encode(fqsx_dna *, uint32_t seg, uint32_t *counts /*[codec] [3][T][T]*/);
-int fqsx_shard_pack(fqsx_dna *, const uint32_t *counts_sum /*[codec]*/, uint64_t *const send[3] /*[codec]*/);
-int fqsx_shard_merge(fqsx_dna *, const uint64_t *const recv[3] /*[codec]*/, uint64_t need[2]);
-int fqsx_shard_insert(fqsx_dna *, uint64_t need_s, uint64_t need_b, uint64_t *const items[3] /*[codec]*/, uint64_t siv_delta[2]);
-int fqsx_shard_apply(fqsx_dna *, uint32_t kind, const uint64_t *items /*[codec]*/, uint64_t n);
-int fqsx_shard_end_phase(fqsx_dna *, const uint64_t siv_delta_sum[2]);
-int fqsx_shard_finish_block(fqsx_dna *, const uint64_t *h_read_off, const uint8_t **streams, uint64_t *lens);
-
-/* The same phase loop inside the library (the reference's phase is three barrier waits, fqs/application.cpp:643-655):
- * fqsx_shard_attach = fqsx_shard_config + the transport; fqsx_shard_encode_block runs a whole reads block -- per phase three
+ * other ranks' sub-tables: fqsx_shard_partition_tables below).  The streams are bit-identical to the one-GPU run's.
+ * There is one driver, the phase loop inside the library (the reference's phase is three barrier waits,
+ * fqs/application.cpp:643-655): fqsx_shard_attach makes the codec one rank of the world and hands it the transport (the world's
+ * collectives, fqsx_comm); fqsx_shard_encode_block runs a whole reads block -- per phase three
  * collectives (all-reduce of the count matrix; the three mailboxes in one grouped all-to-all; one all-gather carrying the
  * applied items, the p-mer statistics and, paired-end, the pair-table triples) and one host round trip (transfer sizes,
  * table demand, error word).  All four dna_modes.  bases / read_off: the block in the codec's memory space, the same on

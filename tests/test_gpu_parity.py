@@ -237,34 +237,13 @@ def test_gpu_encode_decode_round_trip_many_workers():
         assert np.array_equal(dec.decode_block(streams, off, g), np.asarray(bases)), f"block {g} did not round-trip"
 
 
-def test_sharded_path_on_the_gpu_matches_plain_run():
-    """The sharded mode's kernels (count matrix, rank-major pack, merge, item collection, replica update) on the real GPU:
-    a world of one rank over RCCL -- every collective degenerates, every kernel runs (the replica update on the rank's
-    own items, which must change nothing).  The multi-rank exchange itself is covered on CPU (tests/test_sharded_cpu.py)."""
-    import torch
-    import torch.distributed as dist
-    from fqsqueezer_amd.sharded import ShardedDnaCodec
-    from fqsqueezer_amd.synth import synth_reads
-    if not dist.is_initialized():
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29541")
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    reads = synth_reads(20000, 100, 150000, 37)
-    rec = hp.Records([b"@r%d" % i for i in range(len(reads))], reads, reads)
-    header = hp.make_header(16, "se_sorted", 1)
-    sh, one = ShardedDnaCodec(header, 0, 1, device=0, apply_own=True), gpu(header)
-    for g, idx in enumerate(hp.form_blocks(rec, "se_sorted")[:60]):
-        bases, off = hp.block_arrays(rec, idx)
-        mine, ref = sh.encode_block(bases, off, g), one.encode_block(bases, off, g)
-        assert [mine[w] for w in range(16)] == ref, f"block {g}"
-    assert sh.traffic["phases"] >= 60
-    dist.destroy_process_group()
-
-
 def test_native_sharded_driver_on_the_gpu_over_rccl():
     """fqsx_shard_encode_block with the RCCL transport inside the library (a world of one rank: every collective runs through
     librccl on the codec's stream, every kernel of the native phase loop runs), single- and paired-end, with the replica
-    update on the rank's own items switched on.  The multi-rank exchange is covered on CPU (tests/test_sharded_cpu.py)."""
+    update on the rank's own items switched on (it must change nothing).  The only GPU cover of the replicated-table phase's
+    kernels: count matrix (k_shard_counts, k_shard_colsum, k_shard_need), rank-major grouped partition, k_shard_merge3, item
+    collection (k_shard_collect), replica update (k_shard_apply), k_shard_pack2 / k_shard_unpack2 with no fill words.
+    The multi-rank exchange is covered on CPU (tests/test_sharded_cpu.py)."""
     from fqsqueezer_amd.sharded import NativeShardedDnaCodec
     from fqsqueezer_amd.synth import synth_reads
     os.environ["FQSX_SHARD_APPLY_OWN"] = "1"

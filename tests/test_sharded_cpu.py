@@ -9,55 +9,6 @@ import pytest
 
 from conftest import ROOT
 
-WORKER = r'''
-import os, sys, hashlib
-sys.path.insert(0, os.environ["FQSX_ROOT"])
-import numpy as np, torch, torch.distributed as dist
-from fqsqueezer_amd import hostpipe as hp
-from fqsqueezer_amd.codec import DnaCodec
-from fqsqueezer_amd.sharded import ShardedDnaCodec
-from fqsqueezer_amd.synth import synth_reads
-dist.init_process_group("gloo")
-rank, world = dist.get_rank(), dist.get_world_size()
-lib = os.environ["FQSX_EMU_LIB"]
-T, mode = int(os.environ["FQSX_T"]), os.environ["FQSX_MODE"]
-reads = synth_reads(6000, 90, 40000, 31)           # ~13x coverage: misses, hits, corrections, table growth
-rec = hp.Records([b"@r%d" % i for i in range(len(reads))], reads, reads)
-header = hp.make_header(T, mode, 1)
-order = np.concatenate(hp.sorted_order(rec)) if mode == "se_sorted" else np.arange(len(reads))
-blocks = [order[lo:lo + 600] for lo in range(0, len(order), 600)]        # ten blocks, several segments each
-sh = ShardedDnaCodec(header, rank, world, lib_path=lib, tensor_device=torch.device("cpu"))
-one = DnaCodec(header, lib_path=lib)                # the one-process run, for comparison (every rank runs it)
-h = hashlib.sha256()
-for g, idx in enumerate(blocks):
-    bases, off = hp.block_arrays(rec, idx)
-    mine = sh.encode_block(bases, off, g)
-    ref = one.encode_block(bases, off, g)
-    assert sorted(mine) == list(range(rank, T, world))
-    for w, s in mine.items():
-        assert s == ref[w], f"rank {rank}: block {g} worker {w} differs from the one-process run"
-        h.update(s)
-lst = [None] * world
-dist.all_gather_object(lst, (h.hexdigest(), sh.traffic))
-if rank == 0:
-    assert sh.traffic["phases"] > len(blocks) and sh.traffic["all_to_all_bytes"] > 0
-    print("SHARDED_OK", world, T, mode, lst[0][1])
-dist.destroy_process_group()
-'''
-
-
-@pytest.mark.parametrize("world,T,mode,port", [(2, 5, "se_sorted", 29531), (3, 4, "se_original", 29532)])
-def test_sharded_streams_identical_to_one_process_run(tmp_path, built, world, T, mode, port):
-    script = tmp_path / "w.py"
-    script.write_text(WORKER)
-    env = dict(os.environ, FQSX_ROOT=ROOT, FQSX_EMU_LIB=os.path.join(ROOT, "tests", "emu", "libfqsx_emu.so"), FQSX_T=str(T), FQSX_MODE=mode)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), str(script)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert "SHARDED_OK" in r.stdout
-
-
 # ---- the native driver (fqsx_shard_encode_block: phase loop inside the library, three collectives per phase) over a
 # callback transport into torch.distributed / gloo, single- and paired-end
 NATIVE_WORKER = r'''
@@ -155,7 +106,7 @@ sys.path.insert(0, os.environ["FQSX_ROOT"])
 import numpy as np, torch, torch.distributed as dist
 from fqsqueezer_amd import hostpipe as hp
 from fqsqueezer_amd.codec import FqsxError
-from fqsqueezer_amd.sharded import NativeShardedDnaCodec, ShardedDnaCodec
+from fqsqueezer_amd.sharded import NativeShardedDnaCodec
 from fqsqueezer_amd.synth import synth_reads
 dist.init_process_group("gloo")
 rank, world = dist.get_rank(), dist.get_world_size()
@@ -179,12 +130,6 @@ if rank == 1:
 else:
     assert ": -6:" in msg and "another rank" in msg, msg        # FQSX_E_PEER
 assert sh.traffic["phases"] == 7, sh.traffic                    # both left in the same phase
-# the step-wise driver refuses paired-end worlds (it does not exchange the pair-table triples)
-try:
-    ShardedDnaCodec(hp.make_header(4, "pe_sorted", 1), rank, world, lib_path=lib, tensor_device=torch.device("cpu"))
-    raise SystemExit("paired-end step-wise world accepted")
-except ValueError:
-    pass
 dist.barrier()
 if rank == 0:
     print("FAIL_VOTE_OK")
@@ -205,17 +150,17 @@ def test_a_failing_rank_takes_the_world_out_of_the_phase(tmp_path, built, partit
     assert "FAIL_VOTE_OK" in r.stdout
 
 
-def test_stepwise_library_entry_refuses_paired_end_worlds(built):
+def test_block_call_without_a_transport_is_refused(built):
+    """fqsx_shard_encode_block on a codec nobody attached a transport to: FQSX_E_ARG, not a call through an empty fqsx_comm"""
     import ctypes as C
     from fqsqueezer_amd import hostpipe as hp
     lib = C.CDLL(os.path.join(ROOT, "tests", "emu", "libfqsx_emu.so"))
     lib.fqsx_last_error.restype = C.c_char_p
     h = C.c_void_p()
-    assert lib.fqsx_dna_create(hp.make_header(4, "pe_sorted", 1), 0, C.byref(h)) == 0
-    assert lib.fqsx_shard_config(h, C.c_uint32(1), C.c_uint32(2)) == 0
+    assert lib.fqsx_dna_create(hp.make_header(2, "se_sorted", 1), 0, C.byref(h)) == 0
     off = (C.c_uint64 * 3)(0, 50, 100)
     bases = C.create_string_buffer(b"A" * 100)
-    nseg = C.c_uint32()
-    rc = lib.fqsx_shard_begin_block(h, bases, off, off, C.c_uint32(2), C.c_uint32(0), C.byref(nseg))
-    assert rc == -1 and b"pair-table triples" in lib.fqsx_last_error()
+    streams, lens = (C.c_void_p * 2)(), (C.c_uint64 * 2)()
+    rc = lib.fqsx_shard_encode_block(h, bases, off, off, C.c_uint32(2), C.c_uint32(0), streams, lens)
+    assert rc == -1 and b"no transport attached" in lib.fqsx_last_error()
     lib.fqsx_dna_destroy(h)
