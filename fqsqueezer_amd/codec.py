@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import zlib
 from typing import List, Optional
 
 import numpy as np
@@ -22,6 +23,10 @@ STAT_NAMES = ["gprobe", "gslot", "lprobe", "lslot", "gins", "gins_slot", "siv_wo
 
 class FqsxError(RuntimeError):
     pass
+
+
+class LengthMismatch(ValueError):
+    """a record whose quality line differs in length from its base line, where that cannot be held"""
 
 
 _P, _INT, _U32, _U64, _HDR = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_char_p
@@ -84,6 +89,10 @@ _ABI = {
     "fqsx_fastq_columns_into": (_INT, [_P] * 6),
     "fqsx_fastq_set_profiling": (_INT, [_P, _INT]),
     "fqsx_fastq_kernel_times": (_INT, [_P, _MS]),
+    "fqsx_bgzf_scan": (_INT, [_P, _U64, _U32, _P, _P, _U64S]),
+    "fqsx_bgzf_inflate": (_INT, [_P, _P, _U64, _P, _U32, _P, _U64S]),
+    "fqsx_fastq_index_bgzf": (_INT, [_P, _P, _U64, _P, _U32, _U64, _U64S, _U64S]),
+    "fqsx_fastq_inflate_times": (_INT, [_P, _MS]),
     "fqsx_cols_create": (_INT, [_INT, _OUT]),
     "fqsx_cols_destroy": (None, [_P]),
     "fqsx_cols_info": (_INT, [_P, _U64S]),
@@ -541,6 +550,27 @@ class FastqParser(_Handle):
         return {"records": int(a[0]), "consumed": int(a[1]), "id_bytes": int(a[2]), "bases": int(a[3]), "quals": int(a[4]),
                 "max_id_line": int(a[5]), "length_mismatch": bool(a[6]), "line_feeds": int(a[7])}
 
+    def index_bgzf(self, members: np.ndarray, member_off: np.ndarray, carry: int = 0) -> dict:
+        """index() of the chunk that is the last `carry` bytes of the previous chunk's text, kept on the device, followed by the
+        text of the BGZF members `members` (uint8; member i begins at member_off[i], uint64), inflated on the GPU.  The dict also
+        has "text_bytes", the chunk's size.  A damaged member: FqsxError with `.member` (its index) and `.kind` (INFLATE_KINDS)."""
+        a, info = (C.c_uint64 * 8)(), (C.c_uint64 * 4)()
+        member_off = np.ascontiguousarray(member_off, dtype=np.uint64)
+        try:
+            self._call("fqsx_fastq_index_bgzf", self._h, members.ctypes.data if len(members) else None, len(members),
+                       member_off.ctypes.data if len(member_off) else None, len(member_off), carry, a, info)
+        except FqsxError as e:
+            if info[1]:
+                e.member, e.kind = int(info[0]), INFLATE_KINDS[int(info[1])]
+            raise
+        return {"records": int(a[0]), "consumed": int(a[1]), "id_bytes": int(a[2]), "bases": int(a[3]), "quals": int(a[4]),
+                "max_id_line": int(a[5]), "length_mismatch": bool(a[6]), "line_feeds": int(a[7]), "text_bytes": carry + int(info[2])}
+
+    def inflate_times(self) -> dict:
+        a = (C.c_double * 2)()
+        self._lib.fqsx_fastq_inflate_times(self._h, a)
+        return {"ms": a[0], "launches": int(a[1])}
+
     def columns(self, info: dict):
         """(ids, id_off, bases, read_off, quals, qual_off, plus_len) of the chunk indexed last."""
         n = info["records"]
@@ -571,6 +601,11 @@ class FastqParser(_Handle):
         self._lib.fqsx_fastq_kernel_times(self._h, a)
         return {name: {"ms": a[k], "launches": int(a[7 + k])} for k, name in enumerate(FASTQ_PASSES)}
 
+
+# the kinds of damage the inflate kernel tells apart (csrc/fqsx_inflate.h: INF_E_*), by their number
+INFLATE_KINDS = ["none", "reserved block type", "stored LEN/NLEN mismatch", "over-subscribed or incomplete code", "invalid symbol",
+                 "distance before the member's start", "output beyond ISIZE", "input exhausted", "ISIZE mismatch", "CRC mismatch",
+                 "no BGZF member header"]
 
 FQTEXT_PASSES = ["sizes", "scan_tiles", "offsets", "scatter"]
 
@@ -810,59 +845,235 @@ def _chunk_source(src):
     return readinto, lambda: None
 
 
+def bgzf_scan(data: np.ndarray, lib_path: Optional[str] = None, max_members: Optional[int] = None):
+    """The BGZF members of `data` (uint8 array): (member_off, isize, bytes they span, bytes behind them, not_bgzf) --
+    fqsx_bgzf_scan.  not_bgzf: what follows the members is no BGZF member header."""
+    lib = load_library(lib_path)
+    cap = len(data) // 28 + 1 if max_members is None else max_members   # (a member is 28 bytes at least)
+    off, isize, out = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint32), (C.c_uint64 * 4)()
+    rc = lib.fqsx_bgzf_scan(data.ctypes.data if len(data) else None, len(data), cap, off.ctypes.data, isize.ctypes.data, out)
+    if rc:
+        raise _error(lib, "fqsx_bgzf_scan", rc, "bad argument")
+    return off[:out[0]], isize[:out[0]], int(out[1]), int(out[2]), bool(out[3])
+
+
+def bgzf_inflate(parser: FastqParser, members: np.ndarray, member_off: np.ndarray, text_bytes: int) -> np.ndarray:
+    """The text of the BGZF members (as FastqParser.index_bgzf takes them; text_bytes: the sum of their ISIZE) inflated on the
+    GPU and brought to the host -- fqsx_bgzf_inflate.  A damaged member: FqsxError with `.member` and `.kind`."""
+    text, info = np.empty(text_bytes, dtype=np.uint8), (C.c_uint64 * 4)()
+    member_off = np.ascontiguousarray(member_off, dtype=np.uint64)
+    try:
+        parser._call("fqsx_bgzf_inflate", parser._h, members.ctypes.data if len(members) else None, len(members),
+                     member_off.ctypes.data if len(member_off) else None, len(member_off), text.ctypes.data, info)
+    except FqsxError as e:
+        if info[1]:
+            e.member, e.kind = int(info[0]), INFLATE_KINDS[int(info[1])]
+        raise
+    return text
+
+
+def _read_full(readinto, view) -> int:
+    """fills view unless the source ends (a raw file may return fewer bytes than asked for)"""
+    have = 0
+    while have < len(view):
+        k = readinto(view[have:])
+        if not k:
+            break
+        have += k
+    return have
+
+
+def _sniffed(readinto, n: int = 2):
+    """(the source's first n bytes, a readinto that begins with them again)"""
+    head = bytearray(n)
+    pending = [bytes(head[:_read_full(readinto, memoryview(head))])]
+
+    def again(view) -> int:
+        if pending[0]:
+            k = min(len(view), len(pending[0]))
+            view[:k] = pending[0][:k]
+            pending[0] = pending[0][k:]
+            return k
+        return readinto(view)
+    return pending[0], again
+
+
+class _Gunzip:
+    """readinto over the text of a gzip source (zlib on the host): member after member, so that concatenated gzip files -- BGZF
+    among them -- read as one text.  ValueError: bytes behind the last member that are no gzip member, a source that ends inside one."""
+
+    def __init__(self, readinto):
+        self._src, self._buf, self._pend = readinto, bytearray(1 << 20), b""
+        self._d, self._fresh, self._done = zlib.decompressobj(31), True, False
+        self.members = self.compressed_bytes = 0
+
+    def readinto(self, view) -> int:
+        while not self._done:
+            if not self._pend:
+                k = self._src(memoryview(self._buf))
+                if not k:
+                    if not self._fresh:
+                        raise ValueError("gzip input cut short inside member %d (after %d compressed bytes)" % (self.members, self.compressed_bytes))
+                    self._done = True
+                    break
+                self._pend = bytes(self._buf[:k])
+                self.compressed_bytes += k
+            try:
+                out = self._d.decompress(self._pend, len(view))
+            except zlib.error as e:
+                what = "bytes behind gzip member %d that are no gzip member" % (self.members - 1) if self._fresh and self.members else "damaged gzip member %d" % self.members
+                raise ValueError("gzip input: %s (%s)" % (what, e)) from None
+            self._fresh = False
+            if self._d.eof:
+                self.members += 1
+                self._pend, self._d, self._fresh = self._d.unused_data, zlib.decompressobj(31), True
+            else:
+                self._pend = self._d.unconsumed_tail
+            if out:
+                view[:len(out)] = out
+                return len(out)
+        return 0
+
+
+# What inflate="auto" does with a BGZF file: the GPU path, which tools/bgzf_inflate_bench.py measures against zlib on the host
+# (profiles/bgzf_inflate.json)
+BGZF_AUTO = "device"
+
+
 def parse_fastq(text_or_path, device: int = 0, lib_path: Optional[str] = None, max_chunk_bytes: int = 0, stats: Optional[dict] = None,
-                profile: bool = False, resident: bool = False, resident_ids: bool = False):
+                profile: bool = False, resident: bool = False, resident_ids: bool = False, inflate: str = "auto"):
     """FASTQ text (bytes / uint8 array) or a file (path) to hostpipe.Columns, parsed on the GPU chunk by chunk: a file is read in
     chunk-sized pieces into one reused buffer, the partial record at the end of a chunk is carried to the front of the next, and a
     chunk that holds no complete record doubles the chunk size.  What follows the last complete record (the reference drops an
     unterminated last record too) is not returned; its size is stats["tail_bytes"].  stats: also "chunks", "consumed",
-    "max_id_line", "length_mismatch" and -- profile -- "kernels".
+    "max_id_line", "length_mismatch", "inflate" and -- profile -- "kernels".
+    The input may be gzip, told by its first bytes (1f 8b), not by its name.  A BGZF file (bgzip) is inflated on the GPU, a
+    chunk's worth of whole members at a time, straight into the buffer the parser reads: the compressed bytes are read in pieces,
+    the partial member at the end of a piece is carried on the host and the partial record on the device, and no byte of the
+    text comes to the host.  Any other gzip file -- several concatenated too -- is inflated by zlib on the host and parsed like
+    text.  inflate: "device" (ValueError unless the file is BGZF), "host" (zlib for every gzip file) or "auto" (BGZF_AUTO for
+    BGZF).  ValueError: a damaged BGZF member (its index, its offset in the file and the kind of damage), a file that ends inside
+    a member, bytes behind the last member that are no member.  stats["inflate"]: "format" ("none", "gzip", "bgzf"), "where"
+    ("host", "device"), "members", "compressed_bytes" and -- profile, on the device -- the kernel's "ms" and "launches".
     resident: a DeviceColumns instead -- the base and quality columns never come to the host (the caller closes it); ValueError
     for a record whose quality line differs in length from its base line, which resident columns cannot hold.
     resident_ids (with resident): the id column stays in device memory too (DeviceColumns.keep_ids): the store's `ids` is empty."""
     from . import hostpipe as hp
     if resident_ids and not resident:
         raise ValueError("resident_ids needs resident: the id column stays beside the two others")
+    if inflate not in ("auto", "device", "host"):
+        raise ValueError("inflate is 'auto', 'device' or 'host'")
     p = FastqParser(device, lib_path, max_chunk_bytes)
     store = DeviceColumns(device, lib_path) if resident else None
     readinto, close = _chunk_source(text_or_path)
-    parts, n_chunks, consumed, max_id, mismatch = [], 0, 0, 0, False
-    try:
-        if resident_ids:
-            store.keep_ids()
-        p.set_profiling(profile)
+    parts = []
+    tot = {"chunks": 0, "consumed": 0, "max_id_line": 0, "length_mismatch": False}
+    inf = {"format": "none", "where": "host", "members": 0, "compressed_bytes": 0}
+
+    def take(info: dict) -> int:
+        """the columns of the chunk indexed last; the bytes of it that its records are"""
+        tot["chunks"] += 1
+        if not info["records"]:
+            return 0
+        if resident and info["length_mismatch"]:
+            raise LengthMismatch("a record's quality line differs in length from its base line: resident columns keep one offset array")
+        parts.append(p.columns_into(info, store) if resident else p.columns(info))
+        tot["max_id_line"] = max(tot["max_id_line"], info["max_id_line"])
+        tot["length_mismatch"] |= info["length_mismatch"]
+        tot["consumed"] += info["consumed"]
+        return info["consumed"]
+
+    def grown(size: int) -> int:
+        if 2 * size >= 1 << 32:
+            raise FqsxError("a FASTQ record of 2 GiB or more")
+        return 2 * size
+
+    def text_chunks(readinto) -> int:
+        """chunks of text from the host; returns the bytes behind the last record"""
         size = p.max_chunk_bytes
         buf = np.empty(size, dtype=np.uint8)
         have, eof = 0, False
         while True:
-            while have < size and not eof:   # (a raw file may return fewer bytes than asked for)
-                k = readinto(memoryview(buf)[have:size])
-                if not k:
-                    eof = True
-                have += k or 0
+            k = _read_full(readinto, memoryview(buf)[have:size]) if not eof else 0
+            eof = eof or have + k < size
+            have += k
             if have == 0:
                 break
-            info = p.index(buf[:have])
-            n_chunks += 1
-            if info["records"]:
-                if resident and info["length_mismatch"]:
-                    raise ValueError("a record's quality line differs in length from its base line: resident columns keep one offset array")
-                parts.append(p.columns_into(info, store) if resident else p.columns(info))
-                max_id = max(max_id, info["max_id_line"])
-                mismatch |= info["length_mismatch"]
-                used = info["consumed"]
-                consumed += used
+            used = take(p.index(buf[:have]))
+            if used:
                 buf[:have - used] = buf[used:have]   # the partial record goes to the front of the next chunk
                 have -= used
             elif not eof:   # not one complete record in the chunk: a longer one
-                if 2 * size >= 1 << 32:
-                    raise FqsxError("a FASTQ record of 2 GiB or more")
-                size *= 2
+                size = grown(size)
                 buf = np.concatenate([buf[:have], np.empty(size - have, dtype=np.uint8)])
             if eof:   # (the chunk held everything that was left: what it did not consume is no record)
                 break
+        return have
+
+    def bgzf_chunks(readinto) -> int:
+        """chunks of whole BGZF members, inflated on the device behind the partial record the chunk before left there"""
+        limit = p.max_chunk_bytes                   # text per chunk
+        piece = max(1 << 17, min(limit, 1 << 28) // 2)   # compressed bytes read at a time: two members at least
+        buf = np.empty(piece, dtype=np.uint8)
+        have, eof, base, carry = 0, False, 0, 0     # base: the file offset of buf[0]; carry: text kept on the device
+        while True:
+            if not eof:
+                k = _read_full(readinto, memoryview(buf)[have:])
+                eof = have + k < len(buf)
+                have += k
+                inf["compressed_bytes"] += k
+            if have == 0:
+                break
+            off, isize, whole, _, not_bgzf = bgzf_scan(buf[:have], lib_path, max_members=min(have // 28 + 1, 1 << 20))
+            if len(off) == 0:
+                if not_bgzf:
+                    raise ValueError("BGZF input: no BGZF member at offset %d (behind member %d)" % (base, inf["members"] - 1))
+                if eof:
+                    raise ValueError("BGZF input cut short inside member %d at offset %d" % (inf["members"], base))
+                if have == len(buf):
+                    raise ValueError("BGZF input: member %d at offset %d is longer than a member can be" % (inf["members"], base))
+                continue
+            n = max(1, int(np.searchsorted(carry + np.cumsum(isize.astype(np.int64)), limit, side="right")))
+            span = int(off[n]) if n < len(off) else whole
+            try:
+                info = p.index_bgzf(buf[:span], off[:n], carry)
+            except FqsxError as e:
+                if getattr(e, "kind", None) is None:
+                    raise
+                raise ValueError("BGZF input: member %d at offset %d is damaged: %s" % (inf["members"] + e.member, base + int(off[e.member]), e.kind)) from None
+            inf["members"] += n
+            carry = info["text_bytes"] - take(info)
+            if not info["records"] and carry >= limit:   # not one complete record in the chunk: a longer one
+                limit = grown(limit)
+            buf[:have - span] = buf[span:have]           # the partial member goes to the front of the next piece
+            have -= span
+            base += span
+        return carry
+
+    try:
+        if resident_ids:
+            store.keep_ids()
+        p.set_profiling(profile)
+        head, readinto = _sniffed(readinto)
+        if head == b"\x1f\x8b":
+            first, readinto = _sniffed(readinto, 1 << 16)   # (a BGZF header is 18 bytes unless it has further subfields)
+            is_bgzf = len(bgzf_scan(np.frombuffer(first, dtype=np.uint8), lib_path, max_members=1)[0]) == 1
+            if inflate == "device" and not is_bgzf:
+                raise ValueError("inflate='device' needs BGZF input (bgzip): this gzip file's first member is none")
+            inf["format"] = "bgzf" if is_bgzf else "gzip"
+            inf["where"] = (BGZF_AUTO if inflate == "auto" else inflate) if is_bgzf else "host"
+        if inf["where"] == "device":
+            tail = bgzf_chunks(readinto)
+            if profile:
+                inf.update(p.inflate_times())
+        elif inf["format"] != "none":
+            gz = _Gunzip(readinto)
+            tail = text_chunks(gz.readinto)
+            inf.update(members=gz.members, compressed_bytes=gz.compressed_bytes)
+        else:
+            tail = text_chunks(readinto)
         if stats is not None:
-            stats.update(chunks=n_chunks, consumed=consumed, tail_bytes=have, max_id_line=max_id, length_mismatch=mismatch)
+            stats.update(tot, tail_bytes=tail, inflate=inf)
             if profile:
                 stats["kernels"] = p.kernel_times()
     except BaseException:
@@ -876,3 +1087,4 @@ def parse_fastq(text_or_path, device: int = 0, lib_path: Optional[str] = None, m
         store.set_host_columns(parts)
         return store
     return hp.Columns.from_chunks(parts)
+

@@ -3187,6 +3187,7 @@ extern "C" int fqsx_sort_order(const uint8_t *bases, const uint64_t *read_off, u
 // FASTQ text -> columns (csrc/fqsx_fastq.h): what `fqs e` does first, reads_block.h:35-76 / io.h:451-482
 // =======================================================================================================
 #include "fqsx_fastq.h"
+#include "fqsx_inflate.h"
 
 enum { FQ_PASS_COUNT = 0, FQ_PASS_SCAN_TILES, FQ_PASS_INDEX, FQ_PASS_LENGTHS, FQ_PASS_SCAN_RTILES, FQ_PASS_OFFSETS, FQ_PASS_GATHER, FQ_N_PASS };
 
@@ -3207,6 +3208,17 @@ struct fqsx_fastq : DevCtx {
   bool indexed = false;
   double pass_ms[FQ_N_PASS] = {0, 0, 0, 0, 0, 0, 0};
   u64 pass_n[FQ_N_PASS] = {0, 0, 0, 0, 0, 0, 0};
+  // BGZF input (csrc/fqsx_inflate.h): the compressed members, their offsets (in_off, then out_off, n + 1 entries each) and
+  // status words; the partial record between two chunks
+  u64 text_n = 0;                                 // bytes of d_text that are the chunk indexed last
+  u8 *d_gz = nullptr; u64 gz_cap = 0;
+  u64 *d_moff = nullptr; u64 moff_cap = 0;
+  u32 *d_mstat = nullptr; u64 mstat_cap = 0;
+  u8 *d_carry = nullptr; u64 carry_cap = 0;
+  std::vector<u64> h_moff;
+  std::vector<u32> h_mstat;
+  double inf_ms = 0;
+  u64 inf_n = 0;
 };
 
 // one parser kernel on the handle's chunk, its time (while profiling) booked under `pass`
@@ -3243,11 +3255,12 @@ int fqsx_fastq_create(int device, uint64_t max_chunk_bytes, fqsx_fastq **out) {
 
 uint64_t fqsx_fastq_max_chunk(fqsx_fastq *h) { return h ? h->max_chunk : 0; }
 
-int fqsx_fastq_index(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t out[8]) {
-  if (!h || !out || (n && !text)) { g_err = "null argument"; return FQSX_E_ARG; }
-  if (n >> 32) { g_err = "a chunk of FASTQ text must be below 4 GiB: parse the file chunk by chunk"; return FQSX_E_ARG; }
-  DEVCHK(dev_enter(h));
+}  // extern "C"
+
+// The index of a chunk: text[0 .. n) from the host, or -- text null -- the n bytes that lie in d_text already (BGZF input)
+static int fq_index_chunk(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t out[8]) {
   h->indexed = false;
+  h->text_n = 0;
   for (u32 k = 0; k < 8; ++k) out[k] = h->sum[k] = 0;
   FqCfg &c = h->cfg;
   memset(&c, 0, sizeof(c));
@@ -3255,10 +3268,11 @@ int fqsx_fastq_index(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t ou
   c.n_tiles = (u32)((n + FQSX_FQ_TILE - 1) / FQSX_FQ_TILE);
   c.summary = h->d_summary;
   if (n == 0) { h->indexed = true; return FQSX_OK; }
-  DEVCHK(dfit(h, h->d_text, h->text_cap, n, n, 1));
+  if (text) DEVCHK(dfit(h, h->d_text, h->text_cap, n, n, 1));
   DEVCHK(dfit(h, h->d_tile_cnt, h->tile_cap, c.n_tiles, c.n_tiles, sizeof(u32)));
   DEVCHK(dfit(h, h->d_tile_pre, h->tile_pre_cap, (u64)c.n_tiles + 1, (u64)c.n_tiles + 1, sizeof(u64)));
-  DEVCHK(h2d(h, h->d_text, text, n));
+  if (text) DEVCHK(h2d(h, h->d_text, text, n));
+  h->text_n = n;
   c.text = h->d_text; c.tile_cnt = h->d_tile_cnt; c.tile_pre = h->d_tile_pre;
   FQ_LAUNCH(h, FQ_PASS_COUNT, k_fq_count, c.n_tiles);
   FQ_LAUNCH(h, FQ_PASS_SCAN_TILES, k_fq_scan_tiles, 1);
@@ -3288,6 +3302,111 @@ int fqsx_fastq_index(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t ou
   }
   for (u32 k = 0; k < 8; ++k) out[k] = h->sum[k];
   h->indexed = true;
+  return FQSX_OK;
+}
+
+static const char *const INF_KIND_TEXT[INF_N_KINDS] = {
+    "no error", "reserved block type", "stored LEN/NLEN mismatch", "over-subscribed or incomplete code",
+    "invalid symbol", "distance before the member's start", "output beyond ISIZE", "input exhausted", "ISIZE mismatch",
+    "CRC mismatch", "no BGZF member header"};
+
+// Members [member_off[i], member_off[i + 1]) of members[0 .. n_bytes) (the last one ends at n_bytes) inflated into d_text behind
+// `carry` bytes, which are the end of the text that lies there now.  info: [0] the first damaged member (n_members: none)
+// [1] its kind (INF_E_*)  [2] bytes of text the members hold  [3] 0.  *total = carry + info[2].
+static int fq_inflate(fqsx_fastq *h, const uint8_t *members, uint64_t n_bytes, const uint64_t *member_off, uint32_t n, uint64_t carry,
+                      uint64_t info[4], u64 *total) {
+  info[0] = n; info[1] = info[2] = info[3] = 0;
+  if (carry > h->text_n) { g_err = "carry beyond the text of the chunk before"; return FQSX_E_ARG; }
+  auto damaged = [&](u32 i, u32 kind) {
+    info[0] = i; info[1] = kind;
+    h->text_n = 0;
+    g_err = "BGZF member " + std::to_string(i) + " is damaged: " + INF_KIND_TEXT[kind < INF_N_KINDS ? kind : 0];
+    return FQSX_E_DEVICE;
+  };
+  std::vector<u64> &off = h->h_moff;
+  off.assign(2 * ((size_t)n + 1), 0);
+  u64 *in_off = off.data(), *out_off = in_off + n + 1;
+  out_off[0] = carry;
+  for (u32 i = 0; i < n; ++i) {
+    const u64 lo = member_off[i], hi = i + 1 < n ? member_off[i + 1] : n_bytes;
+    if (lo > hi || hi > n_bytes) { g_err = "member offsets that do not ascend inside the buffer"; return FQSX_E_ARG; }
+    if (hi - lo < 20) return damaged(i, INF_E_HEADER);
+    const u8 *t = members + hi - 4;
+    const u32 isize = (u32)t[0] | ((u32)t[1] << 8) | ((u32)t[2] << 16) | ((u32)t[3] << 24);
+    if (isize > INF_WINDOW) return damaged(i, INF_E_ISIZE);   // (a BGZF member holds at most 64 KiB)
+    in_off[i] = lo;
+    out_off[i + 1] = out_off[i] + isize;
+  }
+  in_off[n] = n_bytes;
+  *total = out_off[n];
+  info[2] = *total - carry;
+  if (*total >> 32) { g_err = "a chunk of FASTQ text must be below 4 GiB: fewer members at a time"; return FQSX_E_ARG; }
+  // the partial record leaves the text before the text's buffer may move
+  if (carry) {
+    DEVCHK(dfit(h, h->d_carry, h->carry_cap, carry, carry + carry / 8, 1));
+    DEVCHK(d2d(h, h->d_carry, h->d_text + (h->text_n - carry), carry));
+    DEVCHK(dev_sync(h));
+  }
+  h->text_n = 0;
+  DEVCHK(dfit(h, h->d_text, h->text_cap, *total, *total + *total / 8, 1));
+  if (carry) DEVCHK(d2d(h, h->d_text, h->d_carry, carry));
+  if (n == 0) { h->text_n = *total; return FQSX_OK; }
+  DEVCHK(dfit(h, h->d_gz, h->gz_cap, n_bytes, n_bytes + n_bytes / 8, 1));
+  DEVCHK(dfit(h, h->d_moff, h->moff_cap, off.size(), off.size() + off.size() / 8, sizeof(u64)));
+  DEVCHK(dfit(h, h->d_mstat, h->mstat_cap, n, (u64)n + n / 8, sizeof(u32)));
+  DEVCHK(h2d(h, h->d_gz, members, n_bytes));
+  DEVCHK(h2d(h, h->d_moff, off.data(), off.size() * sizeof(u64)));
+  DEVCHK(dfill_ff(h, h->d_mstat, (u64)n * sizeof(u32)));
+  InfCfg ic;
+  ic.in = h->d_gz; ic.in_off = h->d_moff; ic.out = h->d_text; ic.out_off = h->d_moff + n + 1; ic.out_cap = *total;
+  ic.status = h->d_mstat; ic.n = n;
+  const double t0 = h->k_ms[2];
+  LAUNCH(h, 2, k_bgzf_inflate, n, 64, ic);
+  h->inf_ms += h->k_ms[2] - t0;
+  h->inf_n += 1;
+  h->h_mstat.assign(n, 0);
+  DEVCHK(d2h_sync(h, h->h_mstat.data(), h->d_mstat, (u64)n * sizeof(u32)));
+  for (u32 i = 0; i < n; ++i)
+    if (h->h_mstat[i]) return damaged(i, h->h_mstat[i] < INF_N_KINDS ? h->h_mstat[i] : (u32)INF_E_HEADER);
+  h->text_n = *total;
+  return FQSX_OK;
+}
+
+extern "C" {
+
+int fqsx_fastq_index(fqsx_fastq *h, const uint8_t *text, uint64_t n, uint64_t out[8]) {
+  if (!h || !out || (n && !text)) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (n >> 32) { g_err = "a chunk of FASTQ text must be below 4 GiB: parse the file chunk by chunk"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(h));
+  return fq_index_chunk(h, n ? text : nullptr, n, out);
+}
+
+int fqsx_bgzf_inflate(fqsx_fastq *h, const uint8_t *members, uint64_t n_bytes, const uint64_t *member_off, uint32_t n_members,
+                      uint8_t *text_out, uint64_t info[4]) {
+  if (!h || !info || (n_members && (!members || !member_off))) { g_err = "null argument"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(h));
+  h->indexed = false;
+  u64 total = 0;
+  DEVCHK(fq_inflate(h, members, n_bytes, member_off, n_members, 0, info, &total));
+  if (total && !text_out) { g_err = "null argument"; return FQSX_E_ARG; }
+  if (total) DEVCHK(d2h_sync(h, text_out, h->d_text, total));
+  return FQSX_OK;
+}
+
+int fqsx_fastq_index_bgzf(fqsx_fastq *h, const uint8_t *members, uint64_t n_bytes, const uint64_t *member_off, uint32_t n_members,
+                          uint64_t carry, uint64_t out[8], uint64_t info[4]) {
+  if (!h || !out || !info || (n_members && (!members || !member_off))) { g_err = "null argument"; return FQSX_E_ARG; }
+  DEVCHK(dev_enter(h));
+  h->indexed = false;
+  u64 total = 0;
+  DEVCHK(fq_inflate(h, members, n_bytes, member_off, n_members, carry, info, &total));
+  return fq_index_chunk(h, nullptr, total, out);
+}
+
+int fqsx_fastq_inflate_times(fqsx_fastq *h, double out[2]) {
+  if (!h || !out) return FQSX_E_ARG;
+  out[0] = h->inf_ms;
+  out[1] = (double)h->inf_n;
   return FQSX_OK;
 }
 

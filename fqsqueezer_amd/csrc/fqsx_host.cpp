@@ -630,4 +630,47 @@ int fqsx_id_decode_block(fqsx_id *h, const uint8_t *const *streams, const uint64
   *id_off_out = h->off.data();
   return FQSX_OK;
 }
+
+// The gzip member headers of buf[0 .. n_bytes) as bgzip writes them (RFC 1952; SAM specification, section 4.1): magic 1f 8b,
+// CM 8, FLG = FEXTRA, XLEN at byte 10, among the extra subfields `BC` with a 2-byte BSIZE = member size - 1; the deflate data
+// lies between the 12 + XLEN header bytes and the 8 trailer bytes (CRC-32, ISIZE).  The walk ends at the first member that is
+// not whole in the buffer, at max_members, or at bytes that are no such header.
+int fqsx_bgzf_scan(const uint8_t *buf, uint64_t n_bytes, uint32_t max_members, uint64_t *member_off, uint32_t *isize, uint64_t out[4]) {
+  if (!out || (n_bytes && !buf) || (max_members && (!member_off || !isize))) return FQSX_E_ARG;
+  u64 pos = 0, n = 0, not_bgzf = 0;
+  while (n < max_members && pos < n_bytes) {
+    const u8 *h = buf + pos;
+    const u64 left = n_bytes - pos;
+    // (what is there of the fixed part decides as early as it can: a file that is no BGZF is told from its first bytes)
+    static const u8 want[4] = {0x1f, 0x8b, 8, 4};
+    bool bad = false;
+    for (u32 k = 0; k < 4 && k < left; ++k) bad |= k < 3 ? h[k] != want[k] : (h[k] & 0x1eu) != want[k];
+    if (bad) { not_bgzf = 1; break; }
+    if (left < 12) break;
+    const u64 xlen = (u64)h[10] | ((u64)h[11] << 8);
+    if (left < 12 + xlen) break;
+    u64 bsize = 0, q = 12;
+    bool found = false;
+    while (q + 4 <= 12 + xlen) {
+      const u64 slen = (u64)h[q + 2] | ((u64)h[q + 3] << 8);
+      if (h[q] == 'B' && h[q + 1] == 'C' && slen == 2 && q + 6 <= 12 + xlen) {
+        bsize = ((u64)h[q + 4] | ((u64)h[q + 5] << 8)) + 1;
+        found = true;
+        break;
+      }
+      q += 4 + slen;
+    }
+    if (!found || bsize < 12 + xlen + 8) { not_bgzf = 1; break; }
+    if (left < bsize) break;
+    member_off[n] = pos;
+    isize[n] = (u32)h[bsize - 4] | ((u32)h[bsize - 3] << 8) | ((u32)h[bsize - 2] << 16) | ((u32)h[bsize - 1] << 24);
+    n += 1;
+    pos += bsize;
+  }
+  out[0] = n;
+  out[1] = pos;
+  out[2] = n_bytes - pos;
+  out[3] = not_bgzf;
+  return FQSX_OK;
+}
 }

@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import hostpipe as hp
-from .codec import DeviceBlock, DeviceColumns, DeviceIds, DnaCodec, IdFallback, MetaCodec, QualCodec, parse_fastq, sort_order
+from .codec import DeviceBlock, DeviceColumns, DeviceIds, DnaCodec, IdFallback, LengthMismatch, MetaCodec, QualCodec, parse_fastq, sort_order
 
 
 def _gpu_groups(rec, device: int, lib_path: Optional[str], stats: Optional[dict] = None):
@@ -258,9 +258,10 @@ def _id_columns_fit_the_kernel(cols: hp.Columns, max_id_line: int, id_mode: str)
 def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: str = "s", genome_size_mbp: int = 3100,
                    quality_mode: str = "illumina_8", id_mode: str = "instrument", quality_thr: int = 20, device: int = 0,
                    lib_path: Optional[str] = None, as_blocks: bool = False, gpu_ids: Optional[bool] = None, stats: Optional[dict] = None,
-                   max_chunk_bytes: int = 0, resident: bool = False, profile: bool = False, resident_ids: bool = False):
+                   max_chunk_bytes: int = 0, resident: bool = False, profile: bool = False, resident_ids: bool = False, inflate: str = "auto"):
     """`fqs e` on FASTQ files: `-s` with one input, `-p` with two (text as bytes / uint8 array, or a path; the defaults are the
-    reference's, params.h:53-78).  The text is parsed on the GPU into columns (codec.parse_fastq), the sort pre-pass runs on the
+    reference's, params.h:53-78; either input may be gzip, each on its own: BGZF is inflated on the GPU, other gzip by zlib on the
+    host -- inflate, as codec.parse_fastq takes it, and stats["parse"][k]["inflate"]).  The text is parsed on the GPU into columns (codec.parse_fastq), the sort pre-pass runs on the
     base column, and the blocks are cut from the columns with vectorised gathers.  Returns what compress_records* return.
     ValueError: a record whose quality line differs in length from its base line; mate files with different numbers of records.
     gpu_ids: see compress_records.  stats: "parse" (one dict per input), "sort" (sorted order: what _gpu_groups reports of the
@@ -283,8 +284,8 @@ def compress_fastq(text_or_path, text2_or_path2=None, threads: int = 1, order: s
             st = {}
             try:
                 cols.append(parse_fastq(src, device=device, lib_path=lib_path, max_chunk_bytes=max_chunk_bytes, stats=st, resident=resident,
-                                        resident_ids=resident_ids))
-            except ValueError:   # (resident columns cannot hold such a record: parse_fastq stops at its chunk)
+                                        resident_ids=resident_ids, inflate=inflate))
+            except LengthMismatch:   # (resident columns cannot hold such a record: parse_fastq stops at its chunk)
                 st["length_mismatch"] = True
             parse_stats.append(st)
             if st["length_mismatch"]:
@@ -343,6 +344,8 @@ def main(argv=None) -> int:
     ap.add_argument("-resident", action="store_true", help="keep the base and quality columns in device memory and cut the blocks there")
     ap.add_argument("-resident-ids", dest="resident_ids", action="store_true",
                     help="keep the id column in device memory too and cut the id lines there (implies -resident)")
+    ap.add_argument("-inflate", choices=["auto", "device", "host"], default="auto",
+                    help="gzip input: BGZF members on the GPU (device), zlib on the host (host), or the faster of the two for the file's kind (auto)")
     ap.add_argument("inputs", nargs="+")
     a = ap.parse_args(argv)
     if len(a.inputs) != (2 if a.paired else 1):
@@ -350,7 +353,7 @@ def main(argv=None) -> int:
     header, blocks = compress_fastq(a.inputs[0], a.inputs[1] if a.paired else None, threads=min(max(a.t, 1), 64), order=a.om,
                                     genome_size_mbp=min(max(a.gs, 1), 32768), quality_mode=_QM[a.qm], id_mode=_IM[a.im], quality_thr=a.qt,
                                     device=a.device, lib_path=a.lib, as_blocks=True, resident=a.resident or a.resident_ids,
-                                    resident_ids=a.resident_ids)
+                                    resident_ids=a.resident_ids, inflate=a.inflate)
     with open(a.out, "wb") as f:
         for chunk in hp.fqs_chunks(header, blocks):   # block by block: the file is never held whole
             f.write(chunk)

@@ -369,6 +369,36 @@ int fqsx_fastq_columns(fqsx_fastq *, uint8_t *ids, uint64_t *id_off, uint8_t *ba
 int fqsx_fastq_set_profiling(fqsx_fastq *, int enable);
 int fqsx_fastq_kernel_times(fqsx_fastq *, double out[14]);
 
+/* BGZF input (csrc/fqsx_inflate.h): gzip cut into members that do not depend on one another, each at most 64 KiB of text as
+ * one raw DEFLATE stream with its own CRC-32 and ISIZE, inflated on the GPU -- one wavefront per member -- into the device
+ * buffer the parser reads.  Stored, fixed and dynamic blocks, any number per member; what zlib's inflate accepts is accepted.
+ * fqsx_bgzf_scan (host only): walks the member headers of buf[0 .. n_bytes): magic 1f 8b 08, FLG = FEXTRA, the `BC` subfield
+ *   with BSIZE = member size - 1.  member_off[i] / isize[i]: offset and ISIZE of the i-th whole member, up to max_members.
+ *   out[0] members found  out[1] bytes they span (the first byte behind them)  out[2] bytes behind them (an incomplete member,
+ *   or members beyond max_members: the caller carries them into its next read)  out[3] 1 if the bytes at out[1] are no BGZF
+ *   member header (a gzip member without `BC`, other flags, no gzip at all), as far as they are there to be judged.  The 28-byte
+ *   empty member at a file's end is a member like any other.
+ * fqsx_bgzf_inflate: member i is members[member_off[i] .. member_off[i + 1]), the last one ends at n_bytes; uploads them,
+ *   inflates them and returns their text back to back in text_out (the sum of their ISIZE bytes, below 4 GiB).
+ *   info[0] the first damaged member (n_members: none)  info[1] its kind  info[2] bytes of text  info[3] 0.
+ *   Kinds: 1 reserved block type  2 stored LEN / NLEN mismatch  3 over-subscribed or incomplete code (or too many codes, no
+ *   end-of-block code)  4 invalid symbol  5 distance before the member's start  6 output beyond ISIZE  7 input exhausted
+ *   8 ISIZE mismatch (also an ISIZE above 65536)  9 CRC mismatch  10 no BGZF member header.  A damaged member: FQSX_E_DEVICE,
+ *   info and fqsx_last_error name its index and kind, text_out is not written.  The kernel reads nothing outside a member's
+ *   bytes and writes nothing outside its ISIZE bytes of text, whatever the member holds.
+ * fqsx_fastq_index_bgzf: fqsx_fastq_index on a chunk that is `carry` bytes kept from the end of the previous chunk's text in
+ *   device memory (its unconsumed partial record, moved to the front on the device) followed by the inflated members;
+ *   carry + the members' text stays below 4 GiB.  out as fqsx_fastq_index (out[1] counts from the carried bytes), info as
+ *   fqsx_bgzf_inflate.  fqsx_fastq_columns and fqsx_fastq_columns_into work on the chunk as on any other.  After an error
+ *   nothing can be carried: the next chunk starts with carry 0.
+ * fqsx_fastq_inflate_times (after fqsx_fastq_set_profiling): out[0] milliseconds, out[1] launches of the inflate kernel. */
+int fqsx_bgzf_scan(const uint8_t *buf, uint64_t n_bytes, uint32_t max_members, uint64_t *member_off, uint32_t *isize, uint64_t out[4]);
+int fqsx_bgzf_inflate(fqsx_fastq *, const uint8_t *members, uint64_t n_bytes, const uint64_t *member_off, uint32_t n_members,
+                      uint8_t *text_out, uint64_t info[4]);
+int fqsx_fastq_index_bgzf(fqsx_fastq *, const uint8_t *members, uint64_t n_bytes, const uint64_t *member_off, uint32_t n_members,
+                          uint64_t carry, uint64_t out[8], uint64_t info[4]);
+int fqsx_fastq_inflate_times(fqsx_fastq *, double out[2]);
+
 /* Device-resident columns (csrc/fqsx_cols.h): a store keeps the base column and the quality column of one input file in
  * device memory, chunk by chunk as the parser produces them -- one allocation per chunk that never moves, so the file is
  * never held twice -- and cuts container blocks out of them by read index.  Ids stay host columns unless the store keeps
